@@ -13,13 +13,17 @@ device (12 B per key: 213 GB for Swiss-Prot on one MI355X); otherwise calls of 2
 merged on the device into ONE resident index (fdgpu_index_merge), byte-identical to a single build.
 value = 542,000 * steps / time (max over ranks).
 
-After the timed build: the export-inclusive rate (one more step + fdgpu_index_export D2H), the per-kernel HIP-event
+With --full, after the timed build: the export-inclusive rate (one more step + fdgpu_index_export D2H), the per-kernel HIP-event
 timings of one step (roofline of the dominant kernel), the motif-query leg against the resident index (folddisco_amd/
 querybench.py: queries/s, the scoring kernels' roofline and the oracle's count_query + retrieval on the host cores) and,
-on rank 0 at N=1, the CPU restatement of the index build on a bounded sample.
+on rank 0 at N=1, the CPU restatement of the index build on a bounded sample.  Without --full those fields of the line are null:
+a plain run generates the database, warms up, times the steps and prints the line.
 
-Contract: python bench.py --gpus N --steps K --warmup W  -> one JSON line on rank 0.  With N > 1 and no WORLD_SIZE in the
-environment the script re-executes itself under torch.distributed.run (one rank per GPU, nccl = RCCL).
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step computed (the resident index of its shard as
+fdgpu_index_export hands it to the host) as DIR/<name>.npy in float64 / float32, a fixed seeded sample of it (dump_outputs).
+
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]  -> one JSON line on rank 0.  With N > 1 and
+no WORLD_SIZE in the environment the script re-executes itself under torch.distributed.run (one rank per GPU, nccl = RCCL).
 """
 from __future__ import annotations
 
@@ -58,7 +62,39 @@ def parse_args():
                     "device, else calls of 3 blocks.  N > 0: N generated blocks of 67,750 structures per call (3: 203,250 structures, ~6.7e9 keys; 1: as in rounds 1-2)")
     ap.add_argument("--no-cli-index", action="store_true", help="skip the drop-in `index` leg (20,500 structures as .pdb.gz files and as a Foldcomp database)")
     ap.add_argument("--no-replicas", action="store_true", help="skip the query-replica leg of --gpus N > 1 (index replicated, queries sharded)")
+    ap.add_argument("--full", action="store_true", help="also run the legs behind the timed build (export / single-index / on-disk inclusive steps, per-kernel "
+                    "roofline, motif queries, drop-in `index`, CPU baselines); the --no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed seeded sample of the index the last timed step built to DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_HASHES = 1 << 19       # --dump-outputs: posting lists sampled by position (hash, start offset, byte length of each)
+DUMP_VALUE_BYTES = 1 << 21  # value bytes sampled by position
+DUMP_IDS = 1 << 21          # decoded structure ids at most, from the first lists of the sample
+
+
+def dump_outputs(ix, out_dir, seed):
+    """--dump-outputs: the index the last timed step built, as a caller receives it from fdgpu_index_export (hashes u32[H], offsets u64[H+1]
+    into the value bytes, value u8[]), plus the structure ids that fdgpu_get_entries decodes from some of its lists.  Swiss-Prot's index is
+    26 GB: the arrays are sampled at positions drawn from `seed` (the same positions for the same index), ~36 MB of .npy in all.  Every
+    value is an integer below 2^53, exact in float64 (value bytes: float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    v, h, o = ix.export_view()
+    H, V = len(h), len(v)
+    rng = np.random.default_rng(seed)
+    pick = np.unique(rng.integers(0, H, DUMP_HASHES)) if H > DUMP_HASHES else np.arange(H)
+    vpick = np.unique(rng.integers(0, V, DUMP_VALUE_BYTES)) if V > DUMP_VALUE_BYTES else np.arange(V)
+    lens = ix.posting_lengths(h[pick]).astype(np.int64)
+    n_dec = int(np.searchsorted(np.cumsum(lens), DUMP_IDS, side="right"))
+    ids = ix.get_entries(h[pick[:n_dec]])
+    out = {"index_counts": np.array([H, V, ix.num_postings, ix.n_structures, ix.first_id], np.float64),
+           "hashes": h[pick].astype(np.float64), "offsets": o[pick].astype(np.float64), "list_bytes": (o[pick + 1] - o[pick]).astype(np.float64),
+           "posting_lengths": lens.astype(np.float64), "value_bytes": v[vpick].astype(np.float32),
+           "posting_ids": np.concatenate(ids).astype(np.float64) if ids else np.zeros(0, np.float64)}
+    del v, h, o
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def respawn_under_torchrun(args):
@@ -415,6 +451,9 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     value = S_total * args.steps / dt
     n_post, n_hash, vlen = ix.num_postings, ix.num_hashes, ix.value_len
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ix, args.dump_outputs, args.seed)
+    R_tot, post_tot, vlen_tot, hash_tot = (sum_over_ranks(x) for x in (R, n_post, vlen, n_hash))
 
     progress("timed build done")
     # ---- N > 1: the legs behind this point (single index over ncclSend / ncclRecv, sharded queries with RCCL exchanges, replicas) run collectives that no
@@ -460,7 +499,7 @@ def main():
         threading.Thread(target=watchdog, daemon=True).start()
     # ---- export-inclusive: one more step that also brings the index to the host in the on-disk layout (fdgpu_index_export)
     export = None
-    if not args.no_export:
+    if args.full and not args.no_export:
         import ctypes as C
         from folddisco_amd._lib import u8p, u32p, u64p
         ix = None
@@ -484,7 +523,7 @@ def main():
     # above times independent shard builds and contains no exchange: this is the number that does.  Expected bytes leaving a rank:
     # (its value bytes + 12 B per hash) x (N - 1) / N.
     single_index = None
-    if world > 1 and not args.no_export:
+    if args.full and world > 1 and not args.no_export:
         try:
             from folddisco_amd import dist as fdist
             comm_si = fdist.Comm(ctx, rank, world) if dist.get_backend() == "nccl" else None
@@ -514,7 +553,7 @@ def main():
     # hash ranges of equal posting bytes, piece j of every rank's sub-index to rank j (ncclSend / ncclRecv under nccl), per-range device merge, every rank
     # writes its regions of the two files.  Never `value`.
     on_disk = None
-    if not args.no_export and not args.no_on_disk:
+    if args.full and not args.no_export and not args.no_on_disk:
         import shutil
         import tempfile
         try:
@@ -561,43 +600,44 @@ def main():
             on_disk = {"error": repr(e)[:300]}
 
     # ---- per-kernel timings of one more (untimed) step with HIP events on the build stream -> roofline
-    ctx.enable_timing(True)
-    ix = None
-    stages, parts, fid = [], [], lo
-    for cb in chunk_batches:
-        parts.append(fd.FolddiscoIndex.build(ctx, cb, first_id=fid))
-        ctx.synchronize()
-        stages += ctx.last_timings()
-        fid += cb.n_struct
-    if len(parts) > 1:
-        ix = fd.FolddiscoIndexSet(parts).merge()
-        ctx.synchronize()
-        stages += ctx.last_timings()
-    else:
-        ix = parts[0]
-    parts = None
-    ctx.enable_timing(False)
-    agg = {}
-    for name, ms, by in stages:
-        a = agg.setdefault(name, [0.0, 0, 0])
-        a[0] += ms; a[1] += by; a[2] += 1
-    dom_name, (dom_ms, dom_bytes, dom_n) = max(agg.items(), key=lambda kv: kv[1][0])
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    tag = f"S{S_total}" if world == 1 else f"S{S_total}_N{world}"
-    tr = pmc_traffic(dom_name, tag)
-    if tr and dom_n and not (0.5 < tr["bytes_per_launch"] / (dom_bytes / dom_n) < 2.0):
-        tr = None      # the committed PMC passes are of another call plan (launch sizes differ): no traffic figure rather than a wrong one
-    R_tot, post_tot, vlen_tot, hash_tot = (sum_over_ranks(x) for x in (R, n_post, vlen, n_hash))
-    b_idx = 37.0 * R_tot / S_total + 8.0 * post_tot / S_total + vlen_tot / S_total + 12.0 * hash_tot / S_total
-    roofline = {"bound": "hbm", "kernel": dom_name, "launches_per_step": dom_n, "avg_ms": dom_ms / max(dom_n, 1),
-                "algorithmic_bytes_per_launch": dom_bytes / max(dom_n, 1),
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "traffic": tr["bytes_per_launch"] if tr else None, "traffic_detail": tr,
-                # SURVEY §8(d) end-to-end figure: B_idx = 37 R + 4 U + 4 U + v U + 12 H/S bytes per structure, per GPU
-                "end_to_end": {"algorithmic_bytes_per_structure": b_idx, "achieved": value / world * b_idx / 1e9, "unit": "GB/s",
-                               "frac": value / world * b_idx / 1e9 / HBM_PEAK_GBS},
-                "stages_ms": {k: round(v[0], 3) for k, v in agg.items()},
-                "stages_gbs": {k: round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0 for k, v in agg.items()}}
+    roofline = None
+    if args.full:
+        ctx.enable_timing(True)
+        ix = None
+        stages, parts, fid = [], [], lo
+        for cb in chunk_batches:
+            parts.append(fd.FolddiscoIndex.build(ctx, cb, first_id=fid))
+            ctx.synchronize()
+            stages += ctx.last_timings()
+            fid += cb.n_struct
+        if len(parts) > 1:
+            ix = fd.FolddiscoIndexSet(parts).merge()
+            ctx.synchronize()
+            stages += ctx.last_timings()
+        else:
+            ix = parts[0]
+        parts = None
+        ctx.enable_timing(False)
+        agg = {}
+        for name, ms, by in stages:
+            a = agg.setdefault(name, [0.0, 0, 0])
+            a[0] += ms; a[1] += by; a[2] += 1
+        dom_name, (dom_ms, dom_bytes, dom_n) = max(agg.items(), key=lambda kv: kv[1][0])
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        tag = f"S{S_total}" if world == 1 else f"S{S_total}_N{world}"
+        tr = pmc_traffic(dom_name, tag)
+        if tr and dom_n and not (0.5 < tr["bytes_per_launch"] / (dom_bytes / dom_n) < 2.0):
+            tr = None      # the committed PMC passes are of another call plan (launch sizes differ): no traffic figure rather than a wrong one
+        b_idx = 37.0 * R_tot / S_total + 8.0 * post_tot / S_total + vlen_tot / S_total + 12.0 * hash_tot / S_total
+        roofline = {"bound": "hbm", "kernel": dom_name, "launches_per_step": dom_n, "avg_ms": dom_ms / max(dom_n, 1),
+                    "algorithmic_bytes_per_launch": dom_bytes / max(dom_n, 1),
+                    "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": tr["bytes_per_launch"] if tr else None, "traffic_detail": tr,
+                    # SURVEY §8(d) end-to-end figure: B_idx = 37 R + 4 U + 4 U + v U + 12 H/S bytes per structure, per GPU
+                    "end_to_end": {"algorithmic_bytes_per_structure": b_idx, "achieved": value / world * b_idx / 1e9, "unit": "GB/s",
+                                   "frac": value / world * b_idx / 1e9 / HBM_PEAK_GBS},
+                    "stages_ms": {k: round(v[0], 3) for k, v in agg.items()},
+                    "stages_gbs": {k: round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0 for k, v in agg.items()}}
 
     n_calls = len(chunk_batches)
     if n_calls == 1 and n_blocks > 3:
@@ -605,7 +645,7 @@ def main():
     progress("stage timings done, query leg starts")
     # ---- motif queries against the resident index of the shard
     query = None
-    if not args.no_query:
+    if args.full and not args.no_query:
         try:
             from folddisco_amd import querybench
             d_all = {k: (torch.cat([b[k] for b in blocks]) if k != "res_off" else None) for k in blocks[0]}
@@ -658,7 +698,7 @@ def main():
                 query["replicas"] = {"error": repr(e), "trace": traceback.format_exc()[-1500:]}
 
     cli_index = None
-    if rank == 0 and world == 1 and not args.no_cli_index:
+    if args.full and rank == 0 and world == 1 and not args.no_cli_index:
         try:
             ix = None; db = None
             torch.cuda.empty_cache()
@@ -667,7 +707,7 @@ def main():
             cli_index = {"error": repr(e)}
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             d0 = d_all if query is not None and "error" not in query else synth.generate(min(GEN_BLOCK, S_total), seed=args.seed, device=dev)
             ns = min(args.cpu_sample, len(d0["res_off"]) - 1)
             off = d0["res_off"][: ns + 1].cpu().numpy().astype(np.uint64)
@@ -707,7 +747,7 @@ def main():
         out = {
             "metric": "structures/sec indexed", "value": value, "unit": "structures/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32+u32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32+u32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"Swiss-Prot scale: {S_total} synthetic AFDB-shaped structures ({int(R_tot)} residues, {int(post_tot)} postings, "
                                    f"{int(vlen_tot)} value bytes) index build, PDBTrRosetta default; {world} rank(s), contiguous id ranges, "
                                    f"per rank {n_calls} build call(s) of <= {CALL_MAX} structures" + (" merged on the device into one resident index" if n_calls > 1 else ": one resident index, no merge"),

@@ -428,7 +428,7 @@ def test_bench_n_gt_1_path_runs_with_two_gloo_ranks_on_one_gpu():
     env = dict(os.environ, FD_BENCH_BACKEND="gloo", PYTHONPATH=root)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--structures", "8000", "--steps", "1", "--warmup", "1", "--queries", "64",
-                        "--no-cpu-baseline", "--no-cli-index"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--no-cli-index", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -451,7 +451,7 @@ def test_bench_n_gt_1_path_runs_with_two_gloo_ranks_on_one_gpu():
     # the N > 1 watchdog: with a limit shorter than the legs behind the timed build, rank 0 prints the line with the completed measurement and every
     # rank leaves with status 0 — what keeps a rank stuck in a never-executed collective from taking the headline with it
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--structures", "8000", "--steps", "1", "--warmup", "0", "--queries", "64",
-                        "--no-cpu-baseline", "--no-cli-index"], cwd=root, env=dict(env, FD_BENCH_WATCHDOG_S="0.05"), capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--no-cli-index", "--full"], cwd=root, env=dict(env, FD_BENCH_WATCHDOG_S="0.05"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

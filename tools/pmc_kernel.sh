@@ -3,7 +3,7 @@
 REGEX=${1:-k_pair_emit2.*}; TAG=${2:-emit}; S=${3:-16384}
 REPO=$(pwd); OUT=$REPO/gpurun_out; RAW=/tmp/fdpmc_$TAG; rm -rf $RAW; mkdir -p $OUT $RAW
 export TMPDIR=/tmp; cd /tmp
-CMD="python $REPO/bench.py --structures $S --steps 1 --warmup 0 --no-query --no-cpu-baseline"
+CMD="python $REPO/bench.py --structures $S --steps 1 --warmup 0 --no-query --no-cpu-baseline --full"
 run() { name=$1; shift; timeout 180 rocprofv3 --output-format csv --kernel-include-regex "$REGEX" --pmc "$@" -d $RAW/$name -o $name -- $CMD > $OUT/pmc_${TAG}_$name.log 2>&1; }
 run sq SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM
 run sq2 SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVES SQ_INSTS_BRANCH
