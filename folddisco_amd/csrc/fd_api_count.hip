@@ -24,32 +24,27 @@ int fd_posting_lengths_dev(fdgpu_ctx *c, const fdgpu_index *ix, const uint32_t *
     HIPCHK(c, hipMemcpyAsync(c->ws[WS_MISC0].p, q_hash, nq * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, c->ws[WS_CQ_KIDX].ensure(nq * 8));
     HIPCHK(c, c->ws[WS_CQ_NSEG].ensure(nq * 4));
-    static const bool lens_cache = [] { const char *e = getenv("FDGPU_LENS_CACHE"); return !(e && e[0] == '0'); }();
-    if (lens_cache && ix->n_hashes) {
-        // the index remembers the length of every list (4 bytes per hash, one pass over the value bytes on the first request)
-        {
-            std::lock_guard<std::mutex> lk(ix->lens_mu);
-            if (!ix->lens) {
-                uint32_t *l = nullptr;
-                HIPCHK(c, hipMalloc((void **)&l, ix->n_hashes * 4));
-                fd_launch_index_lens(ix->offsets, ix->value, ix->n_hashes, l, st);
-                hipError_t le = hipGetLastError();
-                if (le == hipSuccess) le = hipStreamSynchronize(st);      // other contexts read it from their own streams
-                if (le != hipSuccess) { (void)hipFree(l); c->err = std::string("posting lengths of the index: ") + hipGetErrorString(le); return FDGPU_EHIP; }
-                ix->lens = l;
-            }
-        }
-        fd_launch_posting_lookup(ix->hashes, ix->offsets, ix->lens, ix->n_hashes, c->ws[WS_MISC0].as<uint32_t>(), nq, c->ws[WS_MISC1].as<uint64_t>(),
-                                 c->ws[WS_CQ_NSEG].as<uint32_t>(), c->ws[WS_CQ_KIDX].as<long long>(), st);
-        HIPCHK(c, hipGetLastError());
+    if (!ix->n_hashes) {      // an empty index: every hash is absent (length 0, no segments, list position -1)
+        HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC1].p, 0, nq * 8, st));
+        HIPCHK(c, hipMemsetAsync(c->ws[WS_CQ_NSEG].p, 0, nq * 4, st));
+        HIPCHK(c, hipMemsetAsync(c->ws[WS_CQ_KIDX].p, 0xff, nq * 8, st));
         return FDGPU_OK;
     }
-    HIPCHK(c, c->ws[WS_CQ_WSTART].ensure((nq + 2) * 8));
-    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(nq) * 8 + 64));
-    HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-    fd_launch_posting_lengths(ix->hashes, ix->offsets, ix->value, ix->n_hashes, c->ws[WS_MISC0].as<uint32_t>(), nq, c->ws[WS_MISC1].as<uint64_t>(),
-                              c->ws[WS_CQ_KIDX].as<long long>(), c->ws[WS_CQ_NSEG].as<uint32_t>(), c->ws[WS_CQ_WSTART].as<uint64_t>(),
-                              c->ws[WS_SCANTMP].as<uint64_t>(), c->ws[WS_TOTAL].as<uint64_t>(), st);
+    // the index remembers the length of every list (4 bytes per hash, one pass over the value bytes on the first request)
+    {
+        std::lock_guard<std::mutex> lk(ix->lens_mu);
+        if (!ix->lens) {
+            uint32_t *l = nullptr;
+            HIPCHK(c, hipMalloc((void **)&l, ix->n_hashes * 4));
+            fd_launch_index_lens(ix->offsets, ix->value, ix->n_hashes, l, st);
+            hipError_t le = hipGetLastError();
+            if (le == hipSuccess) le = hipStreamSynchronize(st);      // other contexts read it from their own streams
+            if (le != hipSuccess) { (void)hipFree(l); c->err = std::string("posting lengths of the index: ") + hipGetErrorString(le); return FDGPU_EHIP; }
+            ix->lens = l;
+        }
+    }
+    fd_launch_posting_lookup(ix->hashes, ix->offsets, ix->lens, ix->n_hashes, c->ws[WS_MISC0].as<uint32_t>(), nq, c->ws[WS_MISC1].as<uint64_t>(),
+                             c->ws[WS_CQ_NSEG].as<uint32_t>(), c->ws[WS_CQ_KIDX].as<long long>(), st);
     HIPCHK(c, hipGetLastError());
     return FDGPU_OK;
 }
@@ -69,7 +64,7 @@ int fd_posting_lengths_segs(fdgpu_ctx *c, const fdgpu_index *ix, const uint32_t 
     if (!land) {
         HIPCHK(c, hipMemcpyAsync(lengths, d, nq * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(segs, c->ws[WS_CQ_NSEG].p, nq * 4, hipMemcpyDeviceToHost, c->stream));
-        if (kidx) HIPCHK(c, hipMemcpyAsync(kidx, c->ws[WS_CQ_KIDX].p, nq * 8, hipMemcpyDeviceToHost, c->stream));     // both length paths leave the list positions there
+        if (kidx) HIPCHK(c, hipMemcpyAsync(kidx, c->ws[WS_CQ_KIDX].p, nq * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return FDGPU_OK;
     }
@@ -416,19 +411,17 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
     const bool keys_only = dense_topn && !sliced;
     const bool qtile_on = [] { const char *e = getenv("FDGPU_QTILE"); return !(e && e[0] == '0'); }();      // 0: occupancy rows (read per call: tests compare the two)
     // k_qscore32.hip (32-bit sums, planned slot stream; needs the rows' posting lengths for the stream's bound): FDGPU_QT32=0 keeps the 64-bit kernel
-    // (read per call: tests compare the two), FDGPU_QT32=15 takes tiles of 2^15 structures (one workgroup per CU) instead of 2^14 (two per CU)
-    const int qt32_env = [] { const char *e = getenv("FDGPU_QT32"); return e ? atoi(e) : 14; }();
+    // (read per call: tests compare the two)
+    const bool qt32_env = [] { const char *e = getenv("FDGPU_QT32"); return !(e && e[0] == '0'); }();
     // (queries of more than 128 rows keep the 64-bit kernel as well: their idf units reach 2^32 on any real index, and k_qt_rows' small tables are sized for 128)
-    bool qt32 = keys_only && qtile_on && qt32_env != 0 && sums_fit32 && known_len && max_rows <= 128;
-    const uint32_t qt_tl2 = qt32 ? (qt32_env == 15 ? 15u : qt32_env == 13 ? 13u : 14u)
-                                 : [] { const char *e = getenv("FDGPU_QT_TILE"); return e && atoi(e) == 13 ? 13u : 14u; }();      // structures per tile (measurement)
+    bool qt32 = keys_only && qtile_on && qt32_env && sums_fit32 && known_len && max_rows <= 128;
+    const uint32_t qt_tl2 = 14;      // structures per tile: 2^14 (two workgroups per CU)
     const uint32_t NT = (uint32_t)((S + (1u << qt_tl2) - 1) >> qt_tl2);
     bool tiled = keys_only && qtile_on && max_rows <= QT_MAX_ROWS && nq * (S >> QT_CELL_LOG2) < (1ull << 31) && fd_index_checkpoints(c, ix) == FDGPU_OK;
     qt32 = qt32 && tiled;
     const uint32_t qt_wpr = (1u << (qt_tl2 - 8)) + 2u;      // windows a row can need in a tile: < 2 bytes per posting of a tile, windows at least half full, + its pieces' tails
     // one query of thousands of rows (a whole structure as the query) with a selection: the same tiles, the rows cut into slices (k_qt_score<BIG>)
-    const uint32_t NT14 = (uint32_t)((S + (1u << 14) - 1) >> 14);
-    bool tiled_big = dense_topn && sliced && qtile_on && !tiled && nq < (1ull << 18) && nq * NT14 < (1ull << 31) && fd_index_checkpoints(c, ix) == FDGPU_OK;
+    bool tiled_big = dense_topn && sliced && qtile_on && !tiled && nq < (1ull << 18) && nq * NT < (1ull << 31) && fd_index_checkpoints(c, ix) == FDGPU_OK;
     const uint32_t big_slices = (uint32_t)std::min<uint64_t>(32, nq), big_wpr = (uint32_t)((nq + 31) / 32), big_cap = top_n + 1024;
     hipError_t e = hipSuccess;
     auto need = [&](int w, size_t bytes) { if (e == hipSuccess) e = c->ws[w].ensure(bytes); };
@@ -437,7 +430,7 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
     // n x (bytes of the largest id) bytes, a slot holds 16 of them, and every (row, cell) piece ends in one partly filled slot
     uint64_t stream_cap = 0;
     const bool qt_stream = [] { const char *e = getenv("FDGPU_QT_STREAM"); return !(e && e[0] == '0'); }();      // 0: pass B decodes the lists again (tests, measurement)
-    if (tiled && (qt32 || (qt_stream && known_len && max_rows * (1u << (qt_tl2 - QT_CELL_LOG2)) <= (uint64_t)QT_MAXB * (qt_tl2 == 14 ? 512 : 256)))) {
+    if (tiled && (qt32 || (qt_stream && known_len && max_rows * (1u << (qt_tl2 - QT_CELL_LOG2)) <= (uint64_t)QT_MAXB * 512))) {
         const uint64_t top_id = ix->first_id + S, vb = top_id < (1ull << 7) ? 1 : top_id < (1ull << 14) ? 2 : top_id < (1ull << 21) ? 3 : top_id < (1ull << 28) ? 4 : 5;
         const uint64_t NCc = (S + (1u << QT_CELL_LOG2) - 1) >> QT_CELL_LOG2;
         // a piece per (row, cell) where the list has an entry per cell; a list with entries 2^j cells apart is cut into pieces of < 96 bytes on
@@ -469,9 +462,9 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
         }
     } else if (tiled_big) {
         need(WS_CQ_KIDX, nq * 8); need(WS_CQ_NSEG, nq * 4);
-        need(WS_QT_RANGES, (size_t)nq * NT14 * 16); need(WS_QT_COMPACT, ((size_t)NT14 << 14) * 8); need(WS_QT_COUNT, (size_t)NT14 * 4); need(WS_QT_AUX, sizeof(qt_aux) + 256);
-        need(WS_QT_PARTIAL, ((size_t)big_slices * NT14 << 14) * 8);
-        need(WS_QT_SURV, ((size_t)NT14 * 512 * 2 + NT14 + big_cap + 2 * big_wpr) * 4 + (big_slices + 2) * 8 + 64);
+        need(WS_QT_RANGES, (size_t)nq * NT * 16); need(WS_QT_COMPACT, ((size_t)NT << qt_tl2) * 8); need(WS_QT_COUNT, (size_t)NT * 4); need(WS_QT_AUX, sizeof(qt_aux) + 256);
+        need(WS_QT_PARTIAL, ((size_t)big_slices * NT << qt_tl2) * 8);
+        need(WS_QT_SURV, ((size_t)NT * 512 * 2 + NT + big_cap + 2 * big_wpr) * 4 + (big_slices + 2) * 8 + 64);
         need(WS_QT_ROWBITS, (size_t)big_cap * big_wpr * 4);
     } else need_rows();
     if (e != hipSuccess && (tiled || tiled_big)) {      // the tiled path's scratch did not fit (ranges, first-touch lists, decoded stream): the occupancy-row path instead
@@ -537,15 +530,10 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
         }
         T.plan_log2 = QT_CELL_LOG2; T.slices = nullptr; T.n_slices = 0; T.partial = nullptr; T.g_bm = T.g_rank = T.g_tcount = T.g_nid = T.g_rowbits = nullptr;
         T.g_wpr = 0; T.g_eend = T.g_nend = nullptr;
-        T.dbg = nullptr;
         T.pieces = nullptr; T.piece_p = nullptr; T.win = nullptr; T.heads = nullptr; T.win_per_row = 0; T.top_n = top_n; T.max_rows = (uint32_t)max_rows;
         if (qt32) {
             T.pieces = c->ws[WS_QT_RANGES].as<uint4>(); T.piece_p = c->ws[WS_QT_PIECEP].as<uint32_t>(); T.win = c->ws[WS_QT_WIN].as<uint32_t>();
             T.heads = c->ws[WS_QT_HEAD].as<uint4>(); T.win_per_row = qt_wpr;
-        }
-        if (getenv("FDGPU_QT_DBG")) {       // phase durations of the tile kernels (measurement aid)
-            T.dbg = (unsigned long long *)(c->ws[WS_QT_AUX].as<uint8_t>() + n_queries * sizeof(qt_aux));
-            (void)hipMemsetAsync(T.dbg, 0, 256, st);
         }
     }
     std::vector<uint64_t> big_sl;        // row slices of the large-query path and the rows that end an edge / a node (outlive their asynchronous copies)
@@ -553,11 +541,11 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
     if (tiled_big) {
         T.value = ix->value; T.offsets = ix->offsets; T.ck_meta = ix->ck_meta; T.ck_ent = (const uint2 *)ix->ck_ent;
         T.kidx = d_kidx; T.row_meta = A.row_meta; T.q_rows = d_qoff; T.penalty = d_penalty;
-        T.nq = (uint32_t)nq; T.n_queries = 1; T.S = (uint32_t)S; T.first_id = (uint32_t)ix->first_id; T.NT = NT14; T.tile_log2 = 14; T.plan_log2 = 14;
+        T.nq = (uint32_t)nq; T.n_queries = 1; T.S = (uint32_t)S; T.first_id = (uint32_t)ix->first_id; T.NT = NT; T.tile_log2 = qt_tl2; T.plan_log2 = qt_tl2;
         T.NC = (uint32_t)((S + (1u << QT_CELL_LOG2) - 1) >> QT_CELL_LOG2);
-        T.ranges = c->ws[WS_QT_RANGES].as<uint4>(); T.c_nid = c->ws[WS_QT_COMPACT].as<uint32_t>(); T.c_key = T.c_nid + ((size_t)NT14 << 14);
+        T.ranges = c->ws[WS_QT_RANGES].as<uint4>(); T.c_nid = c->ws[WS_QT_COMPACT].as<uint32_t>(); T.c_key = T.c_nid + ((size_t)NT << qt_tl2);
         T.ccount = c->ws[WS_QT_COUNT].as<uint32_t>();
-        T.ghist = nullptr; T.state = nullptr; T.aux = c->ws[WS_QT_AUX].as<qt_aux>(); T.out = nullptr; T.cap = big_cap; T.dbg = nullptr;
+        T.ghist = nullptr; T.state = nullptr; T.aux = c->ws[WS_QT_AUX].as<qt_aux>(); T.out = nullptr; T.cap = big_cap;
         T.stream_ids = nullptr; T.stream_row = nullptr; T.stream_tab = nullptr; T.stream_used = nullptr; T.stream_cap = 0;
         T.pieces = nullptr; T.piece_p = nullptr; T.win = nullptr; T.heads = nullptr; T.win_per_row = 0; T.top_n = top_n; T.max_rows = (uint32_t)max_rows;
         // slices of roughly equal posting counts: a row's list holds ~ S / 2^idf ids (idf = log2(S / length), its fixed-point image is in the metadata)
@@ -585,7 +573,7 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
             if (rows_meta[r] & 2ull) big_ends[big_wpr + (r >> 5)] |= 1u << (r & 31u);
         }
         uint32_t *sv = c->ws[WS_QT_SURV].as<uint32_t>();
-        T.g_bm = sv; T.g_rank = sv + (size_t)NT14 * 512; T.g_tcount = T.g_rank + (size_t)NT14 * 512; T.g_nid = T.g_tcount + NT14;
+        T.g_bm = sv; T.g_rank = sv + (size_t)NT * 512; T.g_tcount = T.g_rank + (size_t)NT * 512; T.g_nid = T.g_tcount + NT;
         uint32_t *d_ends = T.g_nid + big_cap;
         T.g_eend = d_ends; T.g_nend = d_ends + big_wpr;
         uint64_t *d_sl = (uint64_t *)(((uintptr_t)(d_ends + 2 * big_wpr) + 63) & ~(uintptr_t)63);
@@ -645,28 +633,6 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
             }
             StageTimer t(c, "cq_topn", 0);
             fd_launch_qt_select(T, top_n, c->ws[WS_TILE_HO].p, st);
-            if (T.dbg && qt32) {
-                unsigned long long d[32];
-                if (hipMemcpyAsync(d, T.dbg, 256, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-                    const double wg = (double)NT * (double)n_queries * 100.0;      // ticks of 10 ns -> us per workgroup
-                    fprintf(stderr, "[qt32] set-up %.2f decode (first wavefront) %.2f wait %.2f keys %.2f cut %.2f emit %.2f us/WG, %.1f windows/WG (%u x %llu WGs)\n",
-                            d[0] / wg, d[1] / wg, d[2] / wg, d[3] / wg, d[4] / wg, d[5] / wg, d[17] / ((double)NT * (double)n_queries), NT, (unsigned long long)n_queries);
-                }
-            } else if (T.dbg) {
-                unsigned long long d[32];
-                if (hipMemcpyAsync(d, T.dbg, 256, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-                    const double wg = (double)NT * (double)n_queries * 100.0;      // ticks of 10 ns -> us per workgroup
-                    fprintf(stderr, "[qt] A: setup %.2f plan %.2f units %.2f decode %.2f wait %.2f final %.2f | B: setup %.2f plan %.2f units %.2f decode %.2f wait %.2f records %.2f us/WG (%u x %llu WGs)\n",
-                            d[0] / wg, d[1] / wg, d[2] / wg, d[3] / wg, d[4] / wg, d[5] / wg, d[8] / wg, d[9] / wg, d[10] / wg, d[11] / wg, d[12] / wg, d[13] / wg, NT,
-                            (unsigned long long)n_queries);
-                    for (int z = 0; z < 2; ++z) {
-                        const unsigned long long *e = d + 16 + 8 * z;
-                        const double nw = (double)NT * (double)n_queries;
-                        fprintf(stderr, "[qt] %c unit loop: units/WG %.1f steps/WG %.1f, wave time mean %.2f us, slowest wave mean %.2f us\n", z ? 'B' : 'A', e[0] / nw, e[1] / nw,
-                                e[3] / (nw * (qt_tl2 == 14 ? 16 : 8) * 100.0), e[2] / (nw * 100.0));
-                    }
-                }
-            }
         } else if (e2 == hipSuccess && tiled_big) {
             T.ghist = c->ws[WS_CQ_TOPN].as<uint32_t>(); T.state = c->ws[WS_MISC2].as<qt_state>(); T.out = c->ws[WS_KEYS_A].p;
             if (have_k && !k_up) (void)hipMemcpyAsync(d_kidx, rows_kidx.data(), nq * 8, hipMemcpyHostToDevice, st);

@@ -87,8 +87,7 @@ int fd_match_pairs_multi(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t *res
     // 1.32 + 1.19 at 64, 1.21 + 1.02 at 128, 1.24 + 1.00 at 256)
     uint64_t max_aad_q = 0;
     for (uint64_t t = 0; t < n_queries; ++t) max_aad_q = std::max<uint64_t>(max_aad_q, qs[t].n_aad);
-    uint32_t j_span = !n_tiles ? 0u : max_aad_q > 4096 ? 128u : n_tiles < 256 ? 64u : n_tiles < 1024 ? 128u : 256u;
-    if (const char *js = getenv("FDGPU_MP_JSPAN")) if (n_tiles && atoi(js) >= 32) j_span = (uint32_t)atoi(js) & ~63u ? (uint32_t)atoi(js) & ~31u : 32u;      // (measurement aid)
+    const uint32_t j_span = !n_tiles ? 0u : max_aad_q > 4096 ? 128u : n_tiles < 256 ? 64u : n_tiles < 1024 ? 128u : 256u;
     TB.j_span = j_span;
     std::vector<uint32_t> wc, wi, wq, wj;
     // a one-off block (a batch of motif queries: 18 k work items per 128 queries) gets its work items written on the DEVICE (k_mp_items): the host
@@ -364,11 +363,9 @@ int fd_match_pairs_multi(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t *res
         A.qset = c->ws[WS_MP_QSET].as<uint32_t>();
     }
     A.n_found = c->ws[WS_TOTAL].as<unsigned long long>(); A.n_cands = A.n_found + 1; A.found = nullptr; A.cands = nullptr;
-    const bool mp_dbg = getenv("FDGPU_MP_DBG") != nullptr;       // clocks and counts of the pair scan's work items and drains on stderr (measurement aid)
     HIPCHK(c, c->ws[WS_TOTAL].ensure(16384));
-    // ws[WS_TOTAL] (u64): [0] found triples, [1] candidate pairs, [2] chunks drained, [4, 12) FDGPU_MP_DBG, from [16]: the 64 sub-queues' claimed chunks, one per 128-byte line
+    // ws[WS_TOTAL] (u64): [0] found triples, [1] candidate pairs, [2] chunks drained, from [16]: the 64 sub-queues' claimed chunks, one per 128-byte line
     A.n_found = c->ws[WS_TOTAL].as<unsigned long long>(); A.n_cands = A.n_found + 1; A.q_cnt = A.n_found + 16;
-    A.dbg = mp_dbg ? A.n_found + 4 : nullptr;
     A.cinfo = d_cinfo; A.act = d_act;
     A.compact = !want_iv;
       // (want_iv: some query observes more than 1,024 distances)
@@ -421,14 +418,6 @@ int fd_match_pairs_multi(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t *res
         {
             StageTimer t(c, "match_pairs", 0);
             fd_launch_match_pairs(A, st);
-        }
-        if (mp_dbg) {
-            unsigned long long d[8];
-            if (hipMemcpyAsync(d, A.dbg, 64, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-                const double live = (double)std::max<unsigned long long>(d[0], 1), us = 0.01;      // 100 MHz ticks
-                fprintf(stderr, "[mp] %llu work items: %llu live (%.2f us each; %.1f partners visited, %.1f pairs queued per item), %llu early exits (%.2f us each); %llu chunks drained (%.2f us each)\n",
-                        (unsigned long long)nw, d[0], d[1] * us / live, d[6] / live, d[7] / live, d[2], d[2] ? d[3] * us / (double)d[2] : 0.0, d[4], d[4] ? d[5] * us / (double)d[4] : 0.0);
-            }
         }
         HIPCHK(c, hipGetLastError());
         if (attempt == 0 && while_scanning && *while_scanning) (*while_scanning)();      // before the copy: one into pageable memory waits for the stream

@@ -379,13 +379,7 @@ static int fd_rb_device_glue(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t 
     A.found = d_found; A.cands = d_cands; A.seg_f = d_seg; A.seg_c = d_seg + (n_cand + 1); A.perm_f = d_pf; A.perm_c = d_pc;
     A.cand = dblk + o_cd; A.slot_q = dblk + o_sq;
     A.slot_matches = (uint32_t *)(c->ws[WS_RS_CNT].as<unsigned long long>() + 2 * RS_CNT_STRIDE + 8);
-    const bool rs_dbg = getenv("FDGPU_RS_DBG") != nullptr;      // phase clocks of the slots on stderr (measurement aid)
-    A.dbg = rs_dbg ? c->ws[WS_RS_CNT].as<unsigned long long>() + 8 : nullptr;
-    uint4 *dbg_slot = nullptr;
-    if (rs_dbg && hipMalloc((void **)&dbg_slot, std::max<uint64_t>(n_cand, 1) * 16) == hipSuccess) (void)hipMemsetAsync(dbg_slot, 0, n_cand * 16, st);
-    struct DbgFree { uint4 *p; ~DbgFree() { if (p) (void)hipFree(p); } } dbg_free{dbg_slot};
-    A.dbg_slot = dbg_slot;
-    A.order = getenv("FDGPU_RS_ORDER") && getenv("FDGPU_RS_ORDER")[0] == '0' ? nullptr : d_cur;      // 0: slot order (measurement)
+    A.order = d_cur;      // slots launch heaviest first
     A.db_res_off = db->res_off; A.db_ca = db->ca_xyz; A.db_cb = db->cb_xyz; A.q_ca = qb->ca_xyz; A.q_cb = qb->cb_xyz;
     A.qt = (const rs_query_dev *)(dblk + o_qt); A.hashes = dblk + o_h; A.kfirst = dblk + o_kf; A.sym = (const uint8_t *)(dblk + o_sy);
     A.map_qi = dblk + o_qi; A.map_qj = dblk + o_qj; A.map_idf = (const float *)(dblk + o_idf); A.indices = dblk + o_idx;
@@ -398,7 +392,7 @@ static int fd_rb_device_glue(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t 
     A.koff = c->ws[WS_RS_KOFF].as<uint64_t>(); A.d0 = (float *)(A.koff + cap_prob + 1);
     A.cap_matches = cap_m; A.cap_res = cap_res; A.cap_prob = cap_prob; A.cap_pts = cap_pts;
     // the split form of the glue (k_rs_setup + a wavefront per component, k_retrieve.hip); FDGPU_RS_SPLIT=0: k_rs_slots alone (read per call: tests compare the two)
-    if (!(getenv("FDGPU_RS_SPLIT") && getenv("FDGPU_RS_SPLIT")[0] == '0') && !rs_dbg) {
+    if (!(getenv("FDGPU_RS_SPLIT") && getenv("FDGPU_RS_SPLIT")[0] == '0')) {
         auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
         const size_t o_big = 0, o_head = o_big + up16(n_cand * 4), o_nodes = o_head + n_cand * 32, o_comps = o_nodes + n_cand * FD_WAVE * 4,
                      o_work = o_comps + n_cand * 2 * FD_WAVE * 8, o_np = o_work + up16(cap_m * 8), o_gq = o_np + cap_m * 16, o_gr = o_gq + cap_m * 2 * FD_WAVE * 4,
@@ -408,7 +402,7 @@ static int fd_rb_device_glue(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t 
         A.sp_big = (uint32_t *)(sp + o_big); A.sp_head = (uint4 *)(sp + o_head); A.sp_nodes = (uint32_t *)(sp + o_nodes);
         A.sp_comps = (unsigned long long *)(sp + o_comps); A.sp_work = (uint2 *)(sp + o_work); A.sp_edges = (uint4 *)(sp + o_edges);
         A.sp_np = (uint4 *)(sp + o_np); A.sp_gq = (uint32_t *)(sp + o_gq); A.sp_gr = (uint32_t *)(sp + o_gr);
-        A.sp_big_n = (uint32_t *)(c->ws[WS_RS_CNT].as<unsigned long long>() + 6);      // zeroed with the counters above (flags at + 4, clocks from + 8)
+        A.sp_big_n = (uint32_t *)(c->ws[WS_RS_CNT].as<unsigned long long>() + 6);      // zeroed with the counters above (flags at + 4)
     }
     {
         StageTimer tm(c, "retrieve_slots", 0);
@@ -423,155 +417,48 @@ static int fd_rb_device_glue(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t 
         memcpy(cnt_h, cv.data(), 32 * 8);
         cnt_h[1] = cv[RS_CNT_STRIDE]; cnt_h[2] = cv[2 * RS_CNT_STRIDE];
     }
-    if (rs_dbg && dbg_slot) {      // the slots by duration: is the launch its longest slot?
-        std::vector<uint4> ds(n_cand);
-        if (hipMemcpy(ds.data(), dbg_slot, n_cand * 16, hipMemcpyDeviceToHost) == hipSuccess) {
-            std::vector<uint32_t> idx(n_cand);
-            for (uint64_t k = 0; k < n_cand; ++k) idx[k] = (uint32_t)k;
-            std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ds[a].w > ds[b].w; });
-            double sum = 0; uint64_t live = 0, big = 0;
-            for (uint64_t k = 0; k < n_cand; ++k) { sum += ds[k].w; live += ds[k].w ? 1 : 0; big += ds[k].y > 512 ? 1 : 0; }
-            fprintf(stderr, "[rs_slots] %llu slots, %llu with found triples (%llu with more candidate pairs than LDS holds), mean %.1f us; longest (us: found, cands, components):", (unsigned long long)n_cand,
-                    (unsigned long long)live, (unsigned long long)big, live ? sum / live / 100.0 : 0.0);
-            for (uint64_t k = 0; k < std::min<uint64_t>(n_cand, 24); ++k) fprintf(stderr, " %.0f:%u,%u,%u", ds[idx[k]].w / 100.0, ds[idx[k]].x, ds[idx[k]].y, ds[idx[k]].z);
-            fprintf(stderr, "; percentiles 50/90/99: %.0f / %.0f / %.0f us\n", ds[idx[n_cand / 2]].w / 100.0, ds[idx[n_cand / 10]].w / 100.0, ds[idx[n_cand / 100]].w / 100.0);
-        }
-    }
-    if (rs_dbg) {
-        const unsigned long long *d = cnt_h + 8;
-        const double ns = std::max<double>((double)n_cand, 1.0) * 100.0, nc2 = std::max<double>((double)d[7], 1.0) * 100.0;
-        fprintf(stderr, "[rs_slots] per slot (%llu slots): edges + rank %.2f, lookup %.2f, nodes %.2f, components %.2f us; per slot WITH components (%llu): order %.2f, "
-                        "components' loop %.2f us = votes %.2f + best / greedy %.2f + rescue votes %.2f + assignment %.2f + output %.2f\n", (unsigned long long)n_cand, d[0] / ns, d[1] / ns,
-                d[2] / ns, d[3] / ns, d[7], d[4] / nc2, (d[5] + d[8] + d[9] + d[10] + d[11] + d[12]) / nc2, d[8] / nc2, d[9] / nc2, d[10] / nc2, d[11] / nc2, d[12] / nc2);
-    }
     const uint32_t dflags = (uint32_t)cnt_h[4];
     auto D2 = t_now();
     if (dflags == 0) {
         const uint64_t nm = cnt_h[0], nprob = cnt_h[1] >> 40, npts = cnt_h[1] & ((1ull << 40) - 1ull);
-        // the 32-byte match headers come back for the ordering; the records themselves (fd_match_rec: 39 words from the solution arrays)
-        // and the residue lists are gathered on the device in their final order (k_rs_records) and copied straight into the caller's
-        // page-locked arrays — the host loop over 23 k records of a 512-query batch (8 scattered reads + 232 bytes written each) was
-        // 1.6-2.3 ms of the call
         float *d_rmsd0 = c->ws[WS_RS_SOL].as<float>();
-        const char *ho_env = getenv("FDGPU_RS_HOST_ORDER");       // 1: the records are ordered on the host from their headers (tests compare the two)
-        if (!(ho_env && ho_env[0] == '1')) {
-            // the records' final places are computed on the device (k_rs_offsets: bases of the slots from their record counts; a record's
-            // place inside its slot was fixed when it was written) — no header copy, no host sort, no gather plan: after the counters above
-            // nothing but the finished arrays crosses the bus, with one wait
-            const uint64_t tot_res = cnt_h[2];
-            if (tot_res >= (1ull << 32)) { c->err = "retrieve_batch: residue lists beyond 2^32 entries; split the batch"; return FDGPU_ERANGE; }
-            float *d_rot0 = d_rmsd0 + nprob, *d_tran0 = d_rot0 + 9 * nprob, *d_met0 = d_tran0 + 3 * nprob;
-            uint64_t *omo = (uint64_t *)malloc((n_queries + 1) * 8), *oro = (uint64_t *)malloc((n_queries + 1) * 8);
-            // dev_out: the ordered records stay in the workspaces for the caller (sharded retrieval: gathered device to device); only the offsets return
-            fd_match_rec *om = dev_out ? nullptr : (fd_match_rec *)fd_out_alloc(std::max<size_t>(nm, 1) * sizeof(fd_match_rec), true);
-            int32_t *orr = dev_out ? nullptr : (int32_t *)fd_out_alloc(std::max<size_t>(tot_res, 1) * sizeof(int32_t), true);
-            if (!omo || !oro || (!dev_out && (!om || !orr))) { fdgpu_free(om); fdgpu_free(orr); free(omo); free(oro); return FDGPU_ENOMEM; }
-            hipError_t e = c->ws[WS_RS_REC].ensure(std::max<uint64_t>(nm, 1) * sizeof(fd_match_rec));
-            if (e == hipSuccess) e = c->ws[WS_RS_RECRES].ensure(std::max<uint64_t>(tot_res, 1) * 4);
-            if (e == hipSuccess && nprob) {
-                fd_launch_rs_points(A, nprob, npts, st);
-                fd_launch_kabsch(A.kx, A.ky, A.koff, nprob, d_rmsd0, d_rot0, d_tran0, st, npts);
-                fd_launch_metrics(A.ky, A.kx, A.koff, nprob, d_rot0, d_tran0, A.d0, d_met0, st, npts);
-            }
-            uint64_t *d_mo = (uint64_t *)(d_ord + o_mo), *d_ro = (uint64_t *)(d_ord + o_ro);
-            if (e == hipSuccess) {
-                fd_launch_rs_records_dev(A.matches, nm, A.slot_matches, (uint32_t)n_cand, (const uint64_t *)(dblk + o_co), A.slot_q, A.qt, (uint32_t)n_queries, d_ord + o_scr,
-                                         d_mo, d_ro, d_rmsd0, d_rot0, d_tran0, d_met0, A.residues, c->ws[WS_RS_REC].p, c->ws[WS_RS_RECRES].as<int32_t>(), st);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess && nm && !dev_out) e = hipMemcpyAsync(om, c->ws[WS_RS_REC].p, nm * sizeof(fd_match_rec), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && tot_res && !dev_out) e = hipMemcpyAsync(orr, c->ws[WS_RS_RECRES].p, tot_res * 4, hipMemcpyDeviceToHost, st);
-            if (dev_out) { dev_out->got = true; dev_out->recs = c->ws[WS_RS_REC].p; dev_out->residues = c->ws[WS_RS_RECRES].as<int32_t>(); dev_out->n_recs = nm; dev_out->n_res = tot_res; }
-            // the two offset arrays lie side by side on the device: one copy into the context's page-locked block, parted on the host
-            uint64_t *off_land = d_ro == d_mo + (n_queries + 1) ? (uint64_t *)c->host_pinned(1, 2 * (n_queries + 1) * 8) : nullptr;
-            if (e == hipSuccess && off_land) e = hipMemcpyAsync(off_land, d_mo, 2 * (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && !off_land) e = hipMemcpyAsync(omo, d_mo, (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && !off_land) e = hipMemcpyAsync(oro, d_ro, (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e == hipSuccess && off_land) { memcpy(omo, off_land, (n_queries + 1) * 8); memcpy(oro, off_land + (n_queries + 1), (n_queries + 1) * 8); }
-            if (e != hipSuccess) { fdgpu_free(om); fdgpu_free(orr); free(omo); free(oro); c->err = std::string("retrieve_batch records: ") + hipGetErrorString(e); return FDGPU_EHIP; }
-            if (trace) fprintf(stderr, "[fdgpu_retrieve] device glue: scan %.3f ms (found %llu, cands %llu), group+slots %.3f, superpose + records ordered on the device + copy (%llu records, %llu problems) %.3f\n",
-                               t_ms(T0, D1), (unsigned long long)nf_d, (unsigned long long)nc_d, t_ms(D1, D2), (unsigned long long)nm, (unsigned long long)nprob, t_ms(D2, t_now()));
-            *matches = om; *match_off = omo; *residues = orr; *res_off = oro;
-            *done = true;
-            return FDGPU_OK;
-        }
-        std::vector<uint8_t> land_v;
-        const size_t b_hm = std::max<uint64_t>(nm, 1) * sizeof(rs_match_dev);
-        uint8_t *land = (uint8_t *)c->host_pinned(1, b_hm);
-        if (!land) { land_v.resize(b_hm); land = land_v.data(); }
-        rs_match_dev *hm = (rs_match_dev *)land;
-        float *d_rmsd = c->ws[WS_RS_SOL].as<float>(), *d_rot = d_rmsd + nprob, *d_tran = d_rot + 9 * nprob, *d_met = d_tran + 3 * nprob;
-        if (nprob) {
-            fd_launch_rs_points(A, nprob, npts, st);
-            fd_launch_kabsch(A.kx, A.ky, A.koff, nprob, d_rmsd, d_rot, d_tran, st, npts);
-            fd_launch_metrics(A.ky, A.kx, A.koff, nprob, d_rot, d_tran, A.d0, d_met, st, npts);
-            HIPCHK(c, hipGetLastError());
-        }
-        if (nm) {
-            HIPCHK(c, hipMemcpyAsync(hm, A.matches, nm * sizeof(rs_match_dev), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-        }
-        const auto E1 = t_now();
-        // the records arrive in append order: into (slot, component) order by a counting sort over the slots and a sort of every slot's few
-        // records (a comparison sort of all 45 k records of a 512-query batch was 3 of the stage's 3.7 ms)
-        std::vector<uint32_t> order(nm);
-        {
-            std::vector<uint32_t> at(n_cand + 2, 0);
-            bool in_range = true;
-            for (uint64_t k = 0; k < nm; ++k) { if (hm[k].slot < n_cand) ++at[hm[k].slot + 1]; else in_range = false; }
-            if (in_range) {
-                for (uint64_t z = 0; z < n_cand; ++z) at[z + 1] += at[z];
-                std::vector<uint32_t> cur(at.begin(), at.end() - 1);
-                for (uint64_t k = 0; k < nm; ++k) order[cur[hm[k].slot]++] = (uint32_t)k;
-                for (uint64_t z = 0; z < n_cand; ++z)
-                    if (at[z + 1] - at[z] > 1)
-                        std::sort(order.begin() + at[z], order.begin() + at[z + 1], [&](uint32_t a, uint32_t b) { return hm[a].ci < hm[b].ci; });
-            } else {
-                for (uint64_t k = 0; k < nm; ++k) order[k] = (uint32_t)k;
-                std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hm[a].slot != hm[b].slot ? hm[a].slot < hm[b].slot : hm[a].ci < hm[b].ci; });
-            }
-        }
-        const auto E2 = t_now();
-        // the gather plan per output record and the per-query offsets
+        // the records' final places are computed on the device (k_rs_offsets: bases of the slots from their record counts; a record's
+        // place inside its slot was fixed when it was written) — no header copy, no host sort, no gather plan: after the counters above
+        // nothing but the finished arrays crosses the bus, with one wait
+        const uint64_t tot_res = cnt_h[2];
+        if (tot_res >= (1ull << 32)) { c->err = "retrieve_batch: residue lists beyond 2^32 entries; split the batch"; return FDGPU_ERANGE; }
+        float *d_rot0 = d_rmsd0 + nprob, *d_tran0 = d_rot0 + 9 * nprob, *d_met0 = d_tran0 + 3 * nprob;
         uint64_t *omo = (uint64_t *)malloc((n_queries + 1) * 8), *oro = (uint64_t *)malloc((n_queries + 1) * 8);
-        if (!omo || !oro) { free(omo); free(oro); return FDGPU_ENOMEM; }
-        std::vector<uint32_t> plan_v;
-        uint32_t *plan = (uint32_t *)c->host_pinned(0, std::max<uint64_t>(nm, 1) * 16);
-        if (!plan) { plan_v.resize(std::max<uint64_t>(nm, 1) * 4); plan = plan_v.data(); }
-        uint64_t tq = 0, rpos = 0;
-        omo[0] = 0; oro[0] = 0;
-        for (uint64_t k = 0; k < nm; ++k) {
-            const rs_match_dev &m = hm[order[k]];
-            while (m.slot >= cand_off[tq + 1]) { ++tq; omo[tq] = k; oro[tq] = rpos; }
-            const uint64_t nq2 = 2 * qms[tq]->n_indices;
-            plan[4 * k] = order[k]; plan[4 * k + 1] = (uint32_t)(m.slot - cand_off[tq]); plan[4 * k + 2] = (uint32_t)rpos; plan[4 * k + 3] = (uint32_t)nq2;
-            rpos += nq2;
+        // dev_out: the ordered records stay in the workspaces for the caller (sharded retrieval: gathered device to device); only the offsets return
+        fd_match_rec *om = dev_out ? nullptr : (fd_match_rec *)fd_out_alloc(std::max<size_t>(nm, 1) * sizeof(fd_match_rec), true);
+        int32_t *orr = dev_out ? nullptr : (int32_t *)fd_out_alloc(std::max<size_t>(tot_res, 1) * sizeof(int32_t), true);
+        if (!omo || !oro || (!dev_out && (!om || !orr))) { fdgpu_free(om); fdgpu_free(orr); free(omo); free(oro); return FDGPU_ENOMEM; }
+        hipError_t e = c->ws[WS_RS_REC].ensure(std::max<uint64_t>(nm, 1) * sizeof(fd_match_rec));
+        if (e == hipSuccess) e = c->ws[WS_RS_RECRES].ensure(std::max<uint64_t>(tot_res, 1) * 4);
+        if (e == hipSuccess && nprob) {
+            fd_launch_rs_points(A, nprob, npts, st);
+            fd_launch_kabsch(A.kx, A.ky, A.koff, nprob, d_rmsd0, d_rot0, d_tran0, st, npts);
+            fd_launch_metrics(A.ky, A.kx, A.koff, nprob, d_rot0, d_tran0, A.d0, d_met0, st, npts);
         }
-        while (tq < n_queries) { ++tq; omo[tq] = nm; oro[tq] = rpos; }
-        const uint64_t tot_res = rpos;
-        if (tot_res >= (1ull << 32)) { free(omo); free(oro); c->err = "retrieve_batch: residue lists beyond 2^32 entries; split the batch"; return FDGPU_ERANGE; }
-        fd_match_rec *om = (fd_match_rec *)fd_out_alloc(std::max<size_t>(nm, 1) * sizeof(fd_match_rec), true);
-        int32_t *orr = (int32_t *)fd_out_alloc(std::max<size_t>(tot_res, 1) * sizeof(int32_t), true);
-        if (!om || !orr) { fdgpu_free(om); fdgpu_free(orr); free(omo); free(oro); return FDGPU_ENOMEM; }
-        const auto E3 = t_now();
-        if (nm) {
-            hipError_t e = c->ws[WS_RS_PLAN].ensure(nm * 16);
-            if (e == hipSuccess) e = c->ws[WS_RS_REC].ensure(nm * sizeof(fd_match_rec));
-            if (e == hipSuccess) e = c->ws[WS_RS_RECRES].ensure(std::max<uint64_t>(tot_res, 1) * 4);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->ws[WS_RS_PLAN].p, plan, nm * 16, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                fd_launch_rs_records(A.matches, c->ws[WS_RS_PLAN].p, nm, d_rmsd, d_rot, d_tran, d_met, A.residues, c->ws[WS_RS_REC].p, c->ws[WS_RS_RECRES].as<int32_t>(), st);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(om, c->ws[WS_RS_REC].p, nm * sizeof(fd_match_rec), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && tot_res) e = hipMemcpyAsync(orr, c->ws[WS_RS_RECRES].p, tot_res * 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) { fdgpu_free(om); fdgpu_free(orr); free(omo); free(oro); c->err = std::string("retrieve_batch records: ") + hipGetErrorString(e); return FDGPU_EHIP; }
+        uint64_t *d_mo = (uint64_t *)(d_ord + o_mo), *d_ro = (uint64_t *)(d_ord + o_ro);
+        if (e == hipSuccess) {
+            fd_launch_rs_records_dev(A.matches, nm, A.slot_matches, (uint32_t)n_cand, (const uint64_t *)(dblk + o_co), A.slot_q, A.qt, (uint32_t)n_queries, d_ord + o_scr,
+                                     d_mo, d_ro, d_rmsd0, d_rot0, d_tran0, d_met0, A.residues, c->ws[WS_RS_REC].p, c->ws[WS_RS_RECRES].as<int32_t>(), st);
+            e = hipGetLastError();
         }
-        if (trace) fprintf(stderr, "[fdgpu_retrieve] device glue: scan %.3f ms (found %llu, cands %llu), group+slots %.3f, superpose+copy+assemble(%llu) %.3f (superpose + headers %.3f, order %.3f, plan %.3f, records %.3f)\n",
-                           t_ms(T0, D1), (unsigned long long)nf_d, (unsigned long long)nc_d, t_ms(D1, D2), (unsigned long long)nprob, t_ms(D2, t_now()), t_ms(D2, E1), t_ms(E1, E2),
-                           t_ms(E2, E3), t_ms(E3, t_now()));
+        if (e == hipSuccess && nm && !dev_out) e = hipMemcpyAsync(om, c->ws[WS_RS_REC].p, nm * sizeof(fd_match_rec), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && tot_res && !dev_out) e = hipMemcpyAsync(orr, c->ws[WS_RS_RECRES].p, tot_res * 4, hipMemcpyDeviceToHost, st);
+        if (dev_out) { dev_out->got = true; dev_out->recs = c->ws[WS_RS_REC].p; dev_out->residues = c->ws[WS_RS_RECRES].as<int32_t>(); dev_out->n_recs = nm; dev_out->n_res = tot_res; }
+        // the two offset arrays lie side by side on the device: one copy into the context's page-locked block, parted on the host
+        uint64_t *off_land = d_ro == d_mo + (n_queries + 1) ? (uint64_t *)c->host_pinned(1, 2 * (n_queries + 1) * 8) : nullptr;
+        if (e == hipSuccess && off_land) e = hipMemcpyAsync(off_land, d_mo, 2 * (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !off_land) e = hipMemcpyAsync(omo, d_mo, (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !off_land) e = hipMemcpyAsync(oro, d_ro, (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess && off_land) { memcpy(omo, off_land, (n_queries + 1) * 8); memcpy(oro, off_land + (n_queries + 1), (n_queries + 1) * 8); }
+        if (e != hipSuccess) { fdgpu_free(om); fdgpu_free(orr); free(omo); free(oro); c->err = std::string("retrieve_batch records: ") + hipGetErrorString(e); return FDGPU_EHIP; }
+        if (trace) fprintf(stderr, "[fdgpu_retrieve] device glue: scan %.3f ms (found %llu, cands %llu), group+slots %.3f, superpose + records ordered on the device + copy (%llu records, %llu problems) %.3f\n",
+                           t_ms(T0, D1), (unsigned long long)nf_d, (unsigned long long)nc_d, t_ms(D1, D2), (unsigned long long)nm, (unsigned long long)nprob, t_ms(D2, t_now()));
         *matches = om; *match_off = omo; *residues = orr; *res_off = oro;
         *done = true;
         return FDGPU_OK;

@@ -534,9 +534,8 @@ extern "C" int fdgpu_make_query_map_batch(fdgpu_ctx *c, const fdgpu_batch *qb, u
             // preconditions: hashes only, the rest on the host as before.
             uint64_t max_ins = 0;
             for (uint64_t t = 0; t < n_queries; ++t) max_ins = std::max(max_ins, cand_off[t + 1] - cand_off[t]);
-            static const bool lens_cache = [] { const char *e = getenv("FDGPU_LENS_CACHE"); return !(e && e[0] == '0'); }();
             dev_chain = max_ins <= QM_DD_MAX && !(qd_env_chain && qd_env_chain[0] == '2');
-            const bool chain_len = dev_chain && index && lens_cache && index->lens && index->n_hashes && index->n_structures;
+            const bool chain_len = dev_chain && index && index->lens && index->n_hashes && index->n_structures;
             const size_t up_words = nv + 2 * (n_queries + 1) + 2;
             uint32_t *up = (uint32_t *)c->host_pinned(3, up_words * 4);
             std::vector<uint32_t> up_v;

@@ -491,21 +491,9 @@ static int ensure_sort_ws(fdgpu_ctx *c, uint64_t P, size_t id_bytes = 4) {
     return FDGPU_OK;
 }
 
-// stable sort of (keys, vals) by the low key_bits of keys; FDGPU_SORT=classic selects the 3-kernel LSD variant
-static int sort_mode();
+// stable sort of (keys, vals) by the low key_bits of keys
 int sort_pairs(fdgpu_ctx *c, uint32_t *ka, uint32_t *va, uint32_t *kb, uint32_t *vb, uint64_t n, int key_bits) {
-    (void)sort_mode();
     return fd_radix_sort_pairs(ka, va, kb, vb, n, key_bits, c->ws[WS_GHIST].as<uint32_t>(), c->ws[WS_TOT].as<uint64_t>(), c->stream, c);
-}
-static int sort_mode() {
-    // FDGPU_SORT = classic18 (default: 512x16-key tiles) | classic19 | classic20 | classic21 | classic30, see k_sort.hip
-    static const int mode = [] {
-        const char *e = getenv("FDGPU_SORT");
-        if (e && !strncmp(e, "classic", 7) && e[7] >= '0' && e[7] <= '9') return atoi(e + 7);
-        return 18;
-    }();
-    fd_rs_set_variant(mode);
-    return mode;
 }
 
 // ---- S1 ---------------------------------------------------------------------------------------------------------------
@@ -681,17 +669,7 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
     HIPCHK(c, c->ws[WS_MISC3].ensure(512));     // words 0-2: encode totals, 3: wide flag, 4: sort overflow flag, 8-48: the MSD stream's bucket starts for the encoder
     HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC3].p, 0, 64, st));
     C.wide_flag = c->ws[WS_MISC3].as<unsigned long long>() + 3;
-    const bool msd_perm = [] { const char *e = getenv("FDGPU_MSD_PERM"); return !(e && e[0] == '0'); }();      // 0: buckets without the amino-acid order (measurement)
-    if (msd && !msd_perm) {
-        {
-            StageTimer t(c, "frames", b->n_res * (37 + sizeof(fd_frame)));
-            fd_launch_frames(b->view(), b->n_res, c->ws[WS_FRAMES].p, st);
-            fd_launch_aa_check(V, b->n_res, C.wide_flag, st);
-        }
-        uint64_t odd = 0;      // the bucket tables hold residue types 0..19 only: decided BEFORE the pair kernels index them
-        if (int r = d2h_u64(c, (const uint64_t *)C.wide_flag, &odd)) return r;
-        if (odd) return FDGPU_RETRY_WIDE;
-    } else if (msd) {
+    if (msd) {
         HIPCHK(c, c->ws[WS_CA_PERM].ensure(std::max<uint64_t>(b->n_res, 1) * 12));
         HIPCHK(c, c->ws[WS_OK_PERM].ensure(std::max<uint64_t>(b->n_res, 1)));
         HIPCHK(c, c->ws[WS_AA_PERM].ensure(std::max<uint64_t>(b->n_res, 1)));
@@ -768,7 +746,6 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
         }
     }
     int cur;
-    (void)sort_mode();
     if (msd) {      // every bucket by hash bits [0, 24) = key bits [8, 32): three passes; the bucket holds the other six
         HIPCHK(c, c->ws[WS_GHIST].ensure((size_t)256 * fd_rs_seg_num_tiles(P, NB) * 4));
         HIPCHK(c, c->ws[WS_TOT].ensure(fd_rs_seg_tot_words(P, NB) * 8));

@@ -285,7 +285,6 @@ void fd_launch_pair_emit2(const fd_batch_view &B, const void *frames, const fd_h
                           uint32_t *keys, void *ids, bool ids16, uint32_t first_id, hipStream_t st);
 int fd_radix_sort_pairs16(uint32_t *keys_a, uint16_t *vals_a, uint32_t *keys_b, uint16_t *vals_b, uint64_t n, int key_bits, uint32_t *ghist,
                           uint64_t *tot, hipStream_t st, fdgpu_ctx *timing_ctx = nullptr);
-void fd_launch_aa_check(const fd_batch_view &B, uint64_t n_res, unsigned long long *wide_flag, hipStream_t st);
 void fd_launch_frames_perm(const fd_batch_view &B, void *frames, float *ca_perm, uint8_t *ok_perm, uint8_t *aa_perm, unsigned long long *wide_flag, hipStream_t st);
 void fd_launch_pair_count_msd(const fd_batch_view &B, const fd_hash_consts &C, uint32_t *counts, hipStream_t st);
 void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const fd_hash_consts &C, const uint64_t *seg_off, uint32_t *cursor, uint32_t *keys,
@@ -303,7 +302,6 @@ template <typename TIn>
 void fd_exclusive_scan(const TIn *in, uint64_t n, uint64_t *out, uint64_t *chunk_tmp, uint64_t *total_dev, hipStream_t st);
 uint64_t fd_scan_tmp_elems(uint64_t n);
 uint32_t fd_rs_num_tiles(uint64_t n);
-void fd_rs_set_variant(int v);
 int fd_radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, uint32_t *vals_b, uint64_t n, int key_bits, uint32_t *ghist,
                         uint64_t *tot, hipStream_t st, fdgpu_ctx *timing_ctx = nullptr);
 uint32_t fd_enc_num_tiles(uint64_t n);
@@ -330,7 +328,7 @@ struct cq_args {
 
 // k_qtile.hip: tiled scoring of motif batches (posting lists entered per tile of structures, scores in LDS)
 #define QT_CELL_LOG2 11                    /* checkpoint granule: 2,048 structure ids — the piece of a list one (row, tile) work unit is cut into */
-/* structures per workgroup (tile): 2^13 (64 KB of LDS accumulators, two workgroups per CU) or 2^14; qt_args.tile_log2 */
+/* structures per workgroup (tile): 2^14; qt_args.tile_log2 */
 #define QT_BINS 2048
 #define QT_MAX_ROWS 1024                   /* rows per query the survivors' row bits are laid out for */
 #define QT_MAXB 16                         /* row batches of a (query, tile) the decoded stream keeps a record of */
@@ -356,7 +354,6 @@ struct qt_args {
     void *stream_ids; uint16_t *stream_row;        // [stream_cap][16] u16 (0xffff: none), [stream_cap]
     uint2 *stream_tab;                     // [n_queries][NT][QT_MAXB] first record and records of a (query, tile, row batch)
     uint32_t *stream_used; uint32_t stream_cap;    // records claimed so far (zero on entry), records the buffers hold
-    unsigned long long *dbg;               // optional (FDGPU_QT_DBG): [16] phase durations summed over the workgroups
     // the 32-bit path (k_qscore32.hip): k_qt_layout leaves, per (query, tile), its non-empty pieces laid out as a stream of 16-byte slots in
     // 64-slot WINDOWS (a piece of <= 64 slots never straddles a window), k_qt_score32 gives every wavefront whole windows
     uint4 *pieces;                         // [nq x NC] region of (query, tile): {first byte lo, first byte hi (16 bits) | row << 16, bytes, id before}
@@ -384,9 +381,6 @@ void fd_launch_qt_select(const qt_args &A, uint32_t top_n, void *sorted, hipStre
 void fd_launch_qt_layout(const qt_args &A, hipStream_t st);
 void fd_launch_qt_score32(const qt_args &A, hipStream_t st);
 
-void fd_launch_posting_lengths(const uint32_t *hashes, const uint64_t *offsets, const uint8_t *value, uint64_t H, const uint32_t *q_hash,
-                               uint64_t nq, uint64_t *lengths, long long *kidx, uint32_t *nseg, uint64_t *wstart, uint64_t *scan_tmp, uint64_t *total,
-                               hipStream_t st);
 void fd_launch_index_lens(const uint64_t *offsets, const uint8_t *value, uint64_t H, uint32_t *lens, hipStream_t st);
 void fd_launch_posting_lookup(const uint32_t *hashes, const uint64_t *offsets, const uint32_t *lens, uint64_t H, const uint32_t *q_hash, uint64_t nq, uint64_t *lengths,
                               uint32_t *nseg, long long *kidx, hipStream_t st);
@@ -430,7 +424,6 @@ struct mp_args {
     float ca_window;
     unsigned long long *n_found, *n_cands;
     const uint4 *cinfo; const uint32_t *act;      // optional (items written on the device): per candidate {first residue, end, active residues | full << 31, first list entry}, the lists
-    unsigned long long *dbg;       // FDGPU_MP_DBG: [8] live items, their ticks, early exits, their ticks, chunks drained, their ticks, partners visited, pairs queued; else null
     // the queue between k_mp_scan and k_mp_drain: chunks of up to 64 packed pairs in 64 sub-queues of cap_subq chunks (sub-queue s: chunks
     // [s * cap_subq, ...), q_cnt[s] claimed — beyond cap_subq: counted only), their headers {slot, pairs | query << 8, first residue, end}.  In chunk
     // order v (sub-queue by sub-queue): the drain's results per pair, the chunk's {candidate-pair records, found triples}, their first positions
@@ -514,8 +507,6 @@ struct rs_args {
     const uint32_t *cand, *slot_q;                       // slot -> structure of the database batch, slot -> query
     const uint32_t *order;                               // launch order of the slots, heaviest first (k_rs_order; null: slot order)
     uint32_t *slot_matches;                              // records every slot wrote (zeroed before the launch; null: not kept)
-    unsigned long long *dbg;                             // FDGPU_RS_DBG: phase clocks summed over the slots (8 counters), else null
-    uint4 *dbg_slot;                                     // FDGPU_RS_DBG: per slot {found triples, candidate pairs, components, 100 MHz ticks}, else null
     const uint32_t *db_res_off; const float *db_ca, *db_cb, *q_ca, *q_cb;
     const rs_query_dev *qt;
     const uint32_t *hashes, *kfirst; const uint8_t *sym;
@@ -546,10 +537,8 @@ void fd_launch_rs_group(const fd_pair_rec *found, uint64_t nf, const fd_cand_rec
                         uint32_t *perm_f, uint32_t *perm_c, hipStream_t st);
 void fd_launch_rs_slots(const rs_args &A, uint32_t n_cand, hipStream_t st);
 void fd_launch_rs_points(const rs_args &A, uint64_t n_prob, uint64_t n_points, hipStream_t st);      // the [CA, CB] point lists of the problems k_rs_slots described and koff[n_prob] (before k_superpose / k_metrics)
-void fd_launch_rs_records(const void *matches, const void *plan, uint64_t n, const float *rmsd, const float *rot, const float *tran, const float *met,
-                          const int32_t *residues, void *out, int32_t *out_res, hipStream_t st);
-// the same with the order made on the device: slot_matches -> per-slot bases, per-query offsets (match_off / res_off, n_queries + 1 each) -> every
-// source record gathered into its final place.  scratch: (2 * n_cand + 2) words
+// the caller's match records (fd_match_rec, 39 words) and residue lists in their final order, made on the device: slot_matches -> per-slot bases,
+// per-query offsets (match_off / res_off, n_queries + 1 each) -> every source record gathered into its final place.  scratch: (2 * n_cand + 2) words
 void fd_launch_rs_records_dev(const void *matches, uint64_t n, const uint32_t *slot_matches, uint32_t n_cand, const uint64_t *cand_off, const uint32_t *slot_q,
                               const rs_query_dev *qt, uint32_t n_queries, uint32_t *scratch, uint64_t *match_off, uint64_t *res_off, const float *rmsd,
                               const float *rot, const float *tran, const float *met, const int32_t *residues, void *out, int32_t *out_res, hipStream_t st);

@@ -559,16 +559,6 @@ __global__ void k_selfcheck(fd_quant q, uint32_t *__restrict__ out /*[24]*/) {
 // ------------------------------------------------------------------ launchers (called from fdgpu_api.hip)
 extern "C++" {
 void fd_launch_selfcheck(const fd_quant &q, uint32_t *out, hipStream_t st) { hipLaunchKernelGGL(k_selfcheck, dim3(1), dim3(64), 0, st, q, out); }
-// FDGPU_MSD_PERM=0 (buckets over the caller's residue order): the check k_frames_perm makes while it permutes
-__global__ void k_aa_check(const uint8_t *__restrict__ aa, const uint8_t *__restrict__ ok, uint64_t n, unsigned long long *__restrict__ wide_flag) {
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n && ok[k] && aa[k] >= 20u) atomicOr(wide_flag, 1ull);
-}
-void fd_launch_aa_check(const fd_batch_view &B, uint64_t n_res, unsigned long long *wide_flag, hipStream_t st) {
-    if (!n_res) return;
-    hipLaunchKernelGGL(k_aa_check, dim3((unsigned)((n_res + 255) / 256)), dim3(256), 0, st, B.aa, B.hash_ok, n_res, wide_flag);
-}
-
 void fd_launch_hash_ok(const uint8_t *aa, const uint8_t *cb_valid, uint8_t *ok, uint64_t n, hipStream_t st) {
     if (!n) return;
     hipLaunchKernelGGL(k_hash_ok, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, aa, cb_valid, ok, n);

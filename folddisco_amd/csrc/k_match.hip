@@ -198,8 +198,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_mp_scan(mp_args A_in) {
     __shared__ __attribute__((aligned(8))) float s_d_buf[COMPACT ? 1024 : 2048];
     __shared__ start_t s_start[1026];
     __shared__ uint32_t s_sel[FD_WAVE];
-    const unsigned long long tk0 = A.dbg ? wall_clock64() : 0ull;
-    unsigned long long n_vis = 0, n_q = 0;
     const uint32_t slot = A.wi_cand[w];
     const uint32_t lane = threadIdx.x;
     const bool tert = A.C.q.type == FD_HASH_TERTIARY;     // TertiaryInteraction needs no CB (feature.rs:113-160)
@@ -282,10 +280,7 @@ __global__ __launch_bounds__(FD_WAVE) void k_mp_scan(mp_args A_in) {
     }
     fd_wave_lds_fence();      // the masks' buffer is the distance buffer
     }
-    if (n_act <= 64u * t_sel) {             // (wave-uniform) nothing left for this tile: before any table is staged
-        if (A.dbg && threadIdx.x == 0) { atomicAdd(&A.dbg[2], 1ull); atomicAdd(&A.dbg[3], wall_clock64() - tk0); }
-        return;
-    }
+    if (n_act <= 64u * t_sel) return;       // (wave-uniform) nothing left for this tile: before any table is staged
     const uint32_t n_here = n_act - 64u * t_sel < FD_WAVE ? n_act - 64u * t_sel : FD_WAVE;
     // the query's observed (aa_i, aa_j) -> CA distance lists (aa_dist_map, controller/query.rs), grouped by residue-type pair:
     // aad_start[aa_i * 32 + aa_j] .. [+1] indexes the distance / query-residue arrays (host-sorted, stable).  Start table and,
@@ -352,7 +347,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_mp_scan(mp_args A_in) {
             if (lane < n) A.chunk_ij[cidx * FD_WAVE + lane] = src[lane];
             if (lane == 0) A.chunk_hdr[cidx] = make_uint4(slot, n | (tq << 8), r0, r1);
         }
-        n_q += n;
     };
     uint32_t qn = 0;   // wave-uniform
     // per block: the partners that can pass at all (their own filters: ~1 in 5 for a motif query's residue types) are walked, wave-uniform broadcasts (v_readlane)
@@ -368,7 +362,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_mp_scan(mp_args A_in) {
         if (!full) okj = okj && aaj_l < 20u && ((Sx.aa2_mask >> aaj_l) & 1u);
         const uint64_t okm = __ballot(okj);
         uint64_t todo = okm;
-        if (A.dbg) n_vis += (unsigned long long)__popcll(okm);
         while (todo) {
             const uint32_t k = (uint32_t)__builtin_ctzll(todo);
             todo &= todo - 1ull;
@@ -423,9 +416,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_mp_scan(mp_args A_in) {
     }
 #undef MP_LOAD_GROUP
     if (qn) { fd_wave_lds_fence(); push(q, qn); }
-    if (A.dbg && threadIdx.x == 0) {
-        atomicAdd(&A.dbg[0], 1ull); atomicAdd(&A.dbg[1], wall_clock64() - tk0); atomicAdd(&A.dbg[6], n_vis); atomicAdd(&A.dbg[7], n_q);
-    }
 }
 
 // the chunks of the 64 sub-queues in one order: v in [0, total) -> the chunk's slot.  Every lane loads one sub-queue's count; returns the total
@@ -454,7 +444,6 @@ __global__ __launch_bounds__(FD_WAVE) __attribute__((amdgpu_waves_per_eu(3, 3)))
     if (blockIdx.x >= nc) return;
     tab[lane] = A.bintab[lane];
     for (uint32_t v = blockIdx.x; v < nc; v += gridDim.x) {
-        const unsigned long long td = A.dbg ? wall_clock64() : 0ull;
         const uint64_t c = mp_chunk_slot(A, incl, v);
         const uint4 hd = A.chunk_hdr[c];
         const uint32_t slot = hd.x, n = hd.y & 255u, tq = hd.y >> 8, r0 = hd.z, r1 = hd.w;
@@ -468,7 +457,6 @@ __global__ __launch_bounds__(FD_WAVE) __attribute__((amdgpu_waves_per_eu(3, 3)))
         if (staged) for (uint32_t e = lane; e < Sx.n_aad; e += FD_WAVE) s_d[e] = Sx.aad_dist[e];
         __syncthreads();
         match_drain(A, Sx, A.chunk_ij + c * FD_WAVE, n, slot, r0, r1, Sx.aad_start, staged ? s_d : Sx.aad_dist, tab, staged_h ? s_qh : nullptr, v);
-        if (A.dbg && lane == 0) { atomicAdd(&A.dbg[4], 1ull); atomicAdd(&A.dbg[5], wall_clock64() - td); }
     }
 }
 

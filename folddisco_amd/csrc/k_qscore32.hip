@@ -174,10 +174,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
     __shared__ uint32_t s_cnt;                     // (structure, key) pairs listed so far
     const uint32_t wg = blockIdx.x;
     const uint32_t t = wg % A.NT, q = wg / A.NT, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    unsigned long long tstamp = A.dbg ? wall_clock64() : 0ull;
-    auto stamp = [&](int k) {      // FDGPU_QT_DBG: phase durations of the workgroup's first thread, summed over the launch (100 MHz ticks)
-        if (A.dbg && tid == 0) { const unsigned long long now = wall_clock64(); atomicAdd(&A.dbg[k], now - tstamp); tstamp = now; }
-    };
     const uint4 hd = A.heads[(uint64_t)q * A.NT + t];
     const uint32_t n_pieces = hd.x, n_win = hd.w ? 0u : hd.y, sbase = hd.z;
     const uint64_t r0 = A.q_rows[q];
@@ -195,10 +191,8 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
     for (uint32_t k = tid; k < QT_BINS / 2; k += NTHR) s_hist[k] = 0u;
     if (tid == 0) s_cnt = 0u;
     q32_barrier_lds();
-    stamp(0);
     // ---- decode: three stages in flight per wavefront — the piece descriptors of the window after next are requested while the posting bytes of
     // the next window travel and the current window is decoded (a window costs two dependent global round trips; a wavefront has ~2 windows)
-    uint32_t my_steps = 0;
     uint32_t i0 = 0, it = 0xffffffffu;       // chunk of 64 of the wavefront's windows, position inside it
     auto next_win = [&](const q32_win &X) -> q32_win {
         q32_win Y;
@@ -258,7 +252,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
     };
     uint32_t carry = 0, prev_last = 0;
     auto decode = [&](const q32_win &X, const q32_slot &S) {
-        ++my_steps;
         const uint32_t w0 = X.w << 6;
         // ---- lane-local decode: the varints that END in these 16 bytes; the leading bytes of the first are the tail of the slot before —
         // the lane below's last four bytes (lane 0 of a continued piece: lane 63 of the window before)
@@ -329,7 +322,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
             }
         }
     }
-    stamp(1);
     // ---- finalize.  A wavefront owns BLK = 2,048 neighbouring structures (lane: 8 groups of four).  Their penalties travel while the slower
     // wavefronts finish; the barrier waits for LDS only (__syncthreads would drain the stream's stores and these loads first)
     constexpr uint32_t BLK = TILE / NW, J = BLK / 256u;
@@ -343,8 +335,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
         for (int u = 0; u < 4; ++u) pen[j][u] = k + u < tile_lim ? A.penalty[tile_lo + k + u] : 0.0f;
     }
     q32_barrier_lds();
-    stamp(2);
-    if (A.dbg && lane == 0) atomicAdd(&A.dbg[16 + 1], (unsigned long long)my_steps);
     // the sums leave LDS for registers (the wavefront's block is then free), idf * penalty for every one of them (three instructions; the dozen
     // that follow — order key, bin, histogram — only for the touched structures, a quarter of the tile: compacted first)
     uint32_t kf[J][4];
@@ -386,7 +376,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
             }
     }
     q32_barrier_lds();
-    stamp(3);
     // ---- the tile's own cut: the highest bin b with (keys in the bins above b) + hist[b] >= top_n (bin 0 when the tile holds fewer) — every
     // wavefront works it out for itself, no hand-over through LDS: lane l sums bins 32 l .. 32 l + 31, the lane where the count from the top
     // crosses top_n is split over the lanes once more
@@ -414,7 +403,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
             bloc = 32u * (uint32_t)L + (uint32_t)(63 - __clzll((long long)mk2));
         }
     }
-    stamp(4);
     // ---- (structure, key) of the keys from that bin up, a wavefront's picks side by side (slots claimed from the workgroup's counter, any order);
     // those bins into the query's histogram
     const uint32_t thr = qt_edge(bloc);
@@ -456,7 +444,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
     }
     q32_barrier_lds();
     if (tid == 0) A.ccount[(uint64_t)q * A.NT + t] = s_cnt;
-    stamp(5);
 }
 
 void fd_launch_qt_layout(const qt_args &A, hipStream_t st) {
@@ -467,7 +454,5 @@ void fd_launch_qt_layout(const qt_args &A, hipStream_t st) {
 void fd_launch_qt_score32(const qt_args &A, hipStream_t st) {
     if (!A.n_queries || !A.S) return;
     const dim3 g(A.NT * A.n_queries);
-    if (A.tile_log2 == 15) hipLaunchKernelGGL((k_qt_score32<15, 1024>), g, dim3(1024), 0, st, A);
-    else if (A.tile_log2 == 13) hipLaunchKernelGGL((k_qt_score32<13, 256>), g, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((k_qt_score32<14, 512>), g, dim3(512), 0, st, A);
+    hipLaunchKernelGGL((k_qt_score32<14, 512>), g, dim3(512), 0, st, A);
 }

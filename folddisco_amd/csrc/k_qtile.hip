@@ -170,17 +170,11 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
     __shared__ uint32_t s_w[NTHR / 64];
     __shared__ uint32_t s_mark[NTHR / 4];         // 64 bytes per wavefront: first lanes of the rows that begin inside a step
     __shared__ uint32_t s_nheavy, s_nlight, s_ucur, s_n, s_cnt, s_base;
-    __shared__ uint32_t s_dbg[8];
     // (query, tile) of the workgroup, tiles of a query on consecutive workgroups = spread over the XCDs (all tiles of a query on ONE XCD
     // measured 25 % slower: the queries' weights differ and the XCDs finish apart)
     const uint32_t wg = blockIdx.x;
     if (wg >= A.NT * (BIG ? A.n_slices : A.n_queries)) return;
     const uint32_t t = wg % A.NT, q = BIG ? 0u : wg / A.NT, slice = BIG ? wg / A.NT : 0u, tid = threadIdx.x, lane = tid & 63u;
-    unsigned long long tstamp = A.dbg ? wall_clock64() : 0ull;
-    auto stamp = [&](int k) {      // FDGPU_QT_DBG: phase durations of the workgroup's first thread, summed over the launch (100 MHz ticks)
-        if (A.dbg && tid == 0) { const unsigned long long now = wall_clock64(); atomicAdd(&A.dbg[(RICH ? 8 : 0) + k], now - tstamp); tstamp = now; }
-    };
-    if (A.dbg && tid < 8) s_dbg[tid] = 0;
     const uint64_t r0 = BIG ? A.slices[slice] : A.q_rows[q];
     const uint32_t nrows = (uint32_t)((BIG ? A.slices[slice + 1] : A.q_rows[q + 1]) - r0);
     const uint32_t tile_lo = t << TL2;
@@ -244,7 +238,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
         if (tid == 0) out_base = atomicAdd(&A.state[q].count, n_surv);       // the answer is needed when the records are written
     }
     __syncthreads();
-    stamp(0);
     for (uint32_t round = 0; round < n_rounds; ++round) {
         const uint32_t s_lo = round * per_round;
         if (RICH && !BIG) {
@@ -281,7 +274,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
                 }
             }
             __syncthreads();
-            stamp(1);
             const uint32_t n = s_n;
             // ---- units: the rows that START in one 64-slot window, processed by one wavefront (a row longer than the window stays whole);
             // units that open with a multi-step row are handed out first (from the front of s_units, the others from its back)
@@ -290,16 +282,12 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
                 else s_units[RB - 1u - atomicAdd(&s_nlight, 1u)] = (uint16_t)tid;
             }
             __syncthreads();
-            stamp(2);
             const uint32_t n_heavy = s_nheavy, n_units = n_heavy + s_nlight;
-            const unsigned long long t_loop = A.dbg ? wall_clock64() : 0ull;
-            uint32_t my_units = 0, my_steps = 0;
             for (;;) {
                 uint32_t ui = 0;
                 if (lane == 0) ui = atomicAdd(&s_ucur, 1u);
                 ui = (uint32_t)__builtin_amdgcn_readfirstlane((int)ui);
                 if (ui >= n_units) break;
-                ++my_units;
                 const uint32_t c0 = s_units[ui < n_heavy ? ui : RB - 1u - (ui - n_heavy)], u = s_P[c0] >> 6;
                 const uint32_t pc = c0 + 1u + lane;
                 const uint64_t outm = __ballot(pc >= n || (s_P[pc < n ? pc : n] >> 6) != u);
@@ -332,7 +320,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
                 uint32_t carry = 0, prev_last = 0;
                 for (uint32_t base = s_beg; base < s_end; base += FD_WAVE) {
                     const bool more = base + FD_WAVE < s_end;
-                    ++my_steps;
                     if (AHEAD && more) prep(base + FD_WAVE, nxt);
                     // ---- lane-local decode: the varints that END in these 16 bytes; the leading bytes of the first are the tail of the
                     // slot before — the lane below's last four bytes (lane 0: lane 63 of the step before)
@@ -459,20 +446,7 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
                     if (more) { if (AHEAD) cur = nxt; else prep(base + FD_WAVE, cur); }
                 }
             }
-            if (A.dbg && lane == 0) {       // per wavefront: units, steps, time in the loop (LDS; the workgroup's first thread reports)
-                const uint32_t dt = (uint32_t)(wall_clock64() - t_loop);
-                atomicAdd(&s_dbg[0], my_units); atomicAdd(&s_dbg[1], my_steps); atomicMax(&s_dbg[2], dt); atomicAdd(&s_dbg[3], dt);
-                if (dt == 0xffffffffu) s_dbg[4] = 0;
-            }
-            stamp(3);
             __syncthreads();
-            stamp(4);
-            if (A.dbg && tid == 0) {
-                unsigned long long *d = A.dbg + (RICH ? 24 : 16);
-                atomicAdd(&d[0], (unsigned long long)s_dbg[0]); atomicAdd(&d[1], (unsigned long long)s_dbg[1]); atomicAdd(&d[2], (unsigned long long)s_dbg[2]);
-                atomicAdd(&d[3], (unsigned long long)s_dbg[3]);
-                s_dbg[0] = 0; s_dbg[1] = 0; s_dbg[2] = 0; s_dbg[3] = 0;
-            }
         }
         if (RICH && !BIG) {
             // ---- the survivors' records, one survivor per thread: match count = set rows, edge / node counts = row groups with a set
@@ -507,7 +481,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
                 }
             }
             __syncthreads();
-            stamp(5);
         }
     }
     if (RICH) return;
@@ -542,7 +515,6 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
         if (cn) atomicAdd(&A.ghist[(uint64_t)q * QT_BINS + k], cn);
     }
     if (tid == 0) A.ccount[(uint64_t)q * A.NT + t] = n_t;
-    stamp(5);
 }
 
 // ------------------------------------------------------------------ pass B from the decoded stream
@@ -942,8 +914,7 @@ void fd_launch_qt_big_select(const qt_args &A, uint32_t top_n, void *sorted, hip
 void fd_launch_qt_score(const qt_args &A, hipStream_t st) {
     if (!A.n_queries || !A.S) return;
     const dim3 g(A.NT * A.n_queries);
-    if (A.tile_log2 == 14) hipLaunchKernelGGL((k_qt_score<false, 14, 1024, 512, 1>), g, dim3(1024), 0, st, A);
-    else hipLaunchKernelGGL((k_qt_score<false, 13, 512, 256, 1>), g, dim3(512), 0, st, A);
+    hipLaunchKernelGGL((k_qt_score<false, 14, 1024, 512, 1>), g, dim3(1024), 0, st, A);
 }
 // threshold -> pass B: survivors' records in A.out[query][cap] (any order; A.state[query].count of them, > cap: overflow) -> ranked
 // top_n records per query in sorted[query][top_n]
@@ -951,14 +922,10 @@ void fd_launch_qt_select(const qt_args &A, uint32_t top_n, void *sorted, hipStre
     if (!A.n_queries || !A.S) return;
     const dim3 g(A.NT * A.n_queries);
     hipLaunchKernelGGL(k_qt_thr, dim3(A.n_queries), dim3(1024), 0, st, A, top_n);
-    if (A.stream_ids && A.tile_log2 == 15) hipLaunchKernelGGL((k_qt_rows<15, 512, 6144, 512>), g, dim3(512), 0, st, A);
-    else if (A.stream_ids && A.tile_log2 == 14 && A.max_rows && A.max_rows <= 128u) {
+    if (A.stream_ids && A.max_rows && A.max_rows <= 128u) {
         hipLaunchKernelGGL((k_qt_rows<14, 512, 1024, 512, 128>), g, dim3(512), 0, st, A);       // (256 / 128 threads per workgroup: 75 / 97 us against 75)
     }
-    else if (A.stream_ids && A.tile_log2 == 14) hipLaunchKernelGGL((k_qt_rows<14, 512, 6144, 512>), g, dim3(512), 0, st, A);
-    else if (A.stream_ids && A.heads && A.max_rows && A.max_rows <= 128u) hipLaunchKernelGGL((k_qt_rows<13, 256, 1024, 256, 128>), g, dim3(256), 0, st, A);
-    else if (A.stream_ids) hipLaunchKernelGGL((k_qt_rows<13, 512, 6144, 256>), g, dim3(512), 0, st, A);
-    else if (A.tile_log2 == 14) hipLaunchKernelGGL((k_qt_score<true, 14, 1024, 512, 6144>), g, dim3(1024), 0, st, A);
-    else hipLaunchKernelGGL((k_qt_score<true, 13, 512, 256, 6144>), g, dim3(512), 0, st, A);
+    else if (A.stream_ids) hipLaunchKernelGGL((k_qt_rows<14, 512, 6144, 512>), g, dim3(512), 0, st, A);
+    else hipLaunchKernelGGL((k_qt_score<true, 14, 1024, 512, 6144>), g, dim3(1024), 0, st, A);
     hipLaunchKernelGGL(k_qt_sort, dim3(A.n_queries), dim3(QT_SORT_T), 0, st, (const qt_rec *)A.out, A.cap, A.state, top_n, (qt_rec *)sorted);
 }

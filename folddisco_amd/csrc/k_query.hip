@@ -133,32 +133,6 @@ __global__ void k_cq_plan(const uint32_t *__restrict__ hashes, const uint64_t *_
     nseg[q] = k < 0 ? 0u : (uint32_t)((offsets[k + 1] - offsets[k] + CQ_SEG - 1) / CQ_SEG);
 }
 
-// number of ids in each query hash's posting list (= bytes without the continuation bit), over the same segments: a list of 100 k
-// ids is ~75 independent 2 KB pieces instead of one wavefront's 2,300 dependent steps; 16 bytes per lane and step
-__global__ __launch_bounds__(FD_WAVE) void k_pl_count(const uint64_t *__restrict__ offsets, const uint8_t *__restrict__ value, const long long *__restrict__ kidx,
-                                                      const uint64_t *__restrict__ wstart, uint64_t nq, unsigned long long *__restrict__ lengths) {
-    const uint32_t lane = threadIdx.x;
-    const uint64_t W = wstart[nq];
-    for (uint64_t w = blockIdx.x; w < W; w += gridDim.x) {
-        uint64_t lo = 0, hi = nq;
-        while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (wstart[mid] <= w) lo = mid; else hi = mid; }
-        const uint64_t q = lo;
-        const long long k = kidx[q];
-        const uint64_t b0 = offsets[k], b1 = offsets[k + 1];
-        const uint64_t s0 = b0 + (w - wstart[q]) * CQ_SEG, s1 = s0 + CQ_SEG < b1 ? s0 + CQ_SEG : b1;
-        uint32_t cnt = 0;
-        for (uint64_t p = s0 + (uint64_t)lane * 16; p < s1; p += 64 * 16) {
-            if (p + 16 <= s1) {
-                unsigned long long w0, w1;
-                __builtin_memcpy(&w0, value + p, 8); __builtin_memcpy(&w1, value + p + 8, 8);
-                cnt += 16u - (uint32_t)__popcll(w0 & 0x8080808080808080ull) - (uint32_t)__popcll(w1 & 0x8080808080808080ull);
-            } else for (uint64_t z = p; z < s1; ++z) cnt += (value[z] & 0x80u) ? 0u : 1u;
-        }
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, FD_WAVE);
-        if (lane == 0 && cnt) atomicAdd(&lengths[q], (unsigned long long)cnt);
-    }
-}
-
 // row word of a structure id, monotone in the id (ids outside the index's range clamp to the row's ends and set no bit)
 __device__ __forceinline__ uint32_t cq_word_of(uint32_t id, uint32_t first_id, uint32_t S) {
     if (id < first_id) return 0u;
@@ -829,11 +803,10 @@ void fd_launch_cq_rows_finalize(const cq_args &A, const uint64_t *q_rows, uint32
         if (!A.packed) (void)hipMemsetAsync(A.match, 0, n * 4, st);
     }
     const dim3 grid((A.words + CQ_FIN_T - 1) / CQ_FIN_T, n_queries, add ? n_slices : 1);
-    static const bool fin_alias = [] { const char *e = getenv("FDGPU_FIN_ALIAS"); return !(e && e[0] == '0'); }();      // 0: the separate count tile (A/B)
     if (max_rows_per_query < 256)
         hipLaunchKernelGGL(k_cq_rows_finalize<8>, grid, dim3(CQ_FIN_T), 0, st, A.hash_bits, A.row_meta, q_rows, A.nq, add ? slices : nullptr, A.words, A.S, A.packed,
                            A.match, A.idf, node_cnt, edge_cnt, flags);
-    else if (add && A.packed && fin_alias)
+    else if (add && A.packed)
         hipLaunchKernelGGL((k_cq_rows_finalize<20, true>), grid, dim3(CQ_FIN_T), 0, st, A.hash_bits, A.row_meta, q_rows, A.nq, add ? slices : nullptr, A.words, A.S, A.packed,
                            A.match, A.idf, node_cnt, edge_cnt, flags);
     else
@@ -883,16 +856,6 @@ void fd_launch_posting_lookup(const uint32_t *hashes, const uint64_t *offsets, c
     if (nq) hipLaunchKernelGGL(k_pl_lookup, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, hashes, offsets, lens, H, q_hash, nq, (unsigned long long *)lengths, nseg, kidx);
 }
 
-// kidx / nseg / wstart / scan_tmp / total: plan workspaces for nq hashes (k_cq_plan + exclusive scan)
-void fd_launch_posting_lengths(const uint32_t *hashes, const uint64_t *offsets, const uint8_t *value, uint64_t H, const uint32_t *q_hash,
-                               uint64_t nq, uint64_t *lengths, long long *kidx, uint32_t *nseg, uint64_t *wstart, uint64_t *scan_tmp, uint64_t *total,
-                               hipStream_t st) {
-    if (!nq) return;
-    (void)hipMemsetAsync(lengths, 0, nq * 8, st);
-    hipLaunchKernelGGL(k_cq_plan, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, hashes, offsets, H, q_hash, nq, kidx, nseg);
-    fd_exclusive_scan<uint32_t>(nseg, nq, wstart, scan_tmp, total, st);
-    hipLaunchKernelGGL(k_pl_count, dim3(8192), dim3(FD_WAVE), 0, st, offsets, value, kidx, wstart, nq, (unsigned long long *)lengths);
-}
 void fd_launch_cq_compact(const uint32_t *match, const unsigned long long *idf, const uint32_t *node_cnt, const uint32_t *edge_cnt,
                           const uint8_t *flags, const uint64_t *pos, const float *penalty, uint32_t S, uint32_t first_id, void *out,
                           hipStream_t st) {

@@ -175,11 +175,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
     const uint32_t r0 = A.db_res_off[st], Rt = A.db_res_off[st + 1] - r0;
     const uint32_t c0 = A.seg_c[slot], c1 = A.seg_c[slot + 1];
     const bool cands_lds = c1 - c0 <= RS_CAND_LDS;
-    unsigned long long tstamp = A.dbg ? wall_clock64() : 0ull;
-    const unsigned long long t_slot0 = tstamp;
-    auto stamp = [&](int k) {      // FDGPU_RS_DBG: phase durations summed over the slots (100 MHz ticks)
-        if (A.dbg && lane == 0) { const unsigned long long now = wall_clock64(); atomicAdd(&A.dbg[k], now - tstamp); tstamp = now; }
-    };
     // ---- edges in the reference's scan order: (i, j) row-major, several bin pairs of one (i, j) in emission order
     for (uint32_t x = lane; x < F; x += FD_WAVE) {
         const uint32_t o = A.perm_f[f0 + x];
@@ -198,7 +193,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
     }
     RS_SYNC();
     // query-map entry (first one holding the hash, like the reference's hash map) and symmetry flag of every edge
-    stamp(0);
     // (the query's sorted hashes through s_a, free between the ranking above and the votes below: the bisection's six dependent loads stay in LDS)
     const bool hs_lds = Q.n_hashes <= RS_LIST_CAP;
     if (hs_lds) { for (uint32_t x = lane; x < Q.n_hashes; x += FD_WAVE) s_a[x] = A.hashes[Q.qh_off + x]; RS_SYNC(); }
@@ -212,7 +206,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
         s_k[x] = ok ? (int32_t)A.kfirst[Q.qh_off + lo] : -1;
         s_sym[x] = ok ? A.sym[Q.qh_off + lo] : (uint8_t)0;
     }
-    stamp(1);
     // ---- nodes in first-appearance order, adjacency rows
     uint32_t node_res = 0xffffffffu, n_nodes = 0;
     uint64_t adj = 0;
@@ -231,7 +224,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
         if (lane == 0) { s_es[e] = (uint8_t)ids[0]; s_et[e] = (uint8_t)ids[1]; }
     }
     RS_SYNC();
-    stamp(2);
     // the edges' query-map fields (query residues of the pair, idf) take the place of i / j / hash, which nothing reads any more
     for (uint32_t x = lane; x < F; x += FD_WAVE) {
         const int32_t k = s_k[x];
@@ -254,18 +246,13 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
     const bool wcc_rep = lane < n_nodes && (uint32_t)__builtin_ctzll(wcc) == lane && (uint32_t)__popcll(wcc) >= A.node_count && wcc != scc;
     const uint64_t ms = __ballot(scc_rep), mw = __ballot(wcc_rep);
     const uint32_t n_scc = (uint32_t)__popcll(ms), n_comp = n_scc + (uint32_t)__popcll(mw);
-    stamp(3);
-    if (n_comp == 0) {
-        if (A.dbg_slot && lane == 0) A.dbg_slot[slot] = make_uint4(F, c1 - c0, 0u, (uint32_t)(wall_clock64() - t_slot0));
-        return;
-    }
+    if (n_comp == 0) return;
     if (lane < NQ) s_idx[lane] = A.indices[Q.idx_off + lane];
     if (cands_lds)
         for (uint32_t x = lane; x < c1 - c0; x += FD_WAVE) {
             const fd_cand_rec cr = A.cands[A.perm_c[c0 + x]];
             s_cq[x] = cr.qi; s_ci[x] = cr.i; s_cj[x] = cr.j;
         }
-    if (A.dbg && lane == 0) atomicAdd(&A.dbg[7], 1ull);
     if (scc_rep) s_cm[fd_mbcnt(ms)] = scc;
     if (wcc_rep) s_cm[n_scc + fd_mbcnt(mw)] = wcc;
     RS_SYNC();
@@ -276,7 +263,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
         s_cs[rank] = a;
     }
     RS_SYNC();
-    stamp(4);
     // every component writes exactly one record: the slot claims its records and residue ints with ONE returning atomic each, here, long before
     // their values are needed (the per-record claims of 10^4 records on one cache line were two thirds of the output phase)
     unsigned long long mi0 = 0, rp0 = 0;
@@ -316,7 +302,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
                 RS_SYNC();
             }
         }
-        stamp(8);
         // ---- per query residue: highest count, smallest target residue holding it
         uint32_t bq = 0, bc = 0, br = 0, nb = 0;
         for (uint32_t v = 0; v < nv; ++v) {
@@ -345,7 +330,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
         RS_SYNC();           // the vote arrays are free from here on
         if (lane < n_asg) { s_aq[lane] = my_aq; s_ar[lane] = my_ar; }
         RS_SYNC();
-        stamp(9);
         // ---- rescue votes (retrieve.rs:498-511): for a query residue without a target, the candidate pairs (query residue, i, j)
         // whose partner j some assignment mapped vote for i; the unique maximum (>= 2) joins
         for (uint32_t pos = 0; pos < NQ; ++pos) {
@@ -396,7 +380,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
             if (lane == 0) { s_rmx[pos] = mx; s_rnm[pos] = nmx; s_rarg[pos] = arg; }
         }
         RS_SYNC();
-        stamp(10);
         // ---- residue assignment + rescue, sequential as in the reference (retrieve.rs:430-516)
         if (lane < NQ) { s_fh[lane] = -1; s_pr[lane] = -1; }
         RS_SYNC();
@@ -430,7 +413,6 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
         RS_SYNC();
         const uint32_t n_sc = s_misc[0];
         const bool same = s_misc[1] != 0;
-        stamp(11);
         // ---- outputs: one record, 2 NQ residues, one or two superposition problems of [CA, CB] points (retrieve.rs:761-767)
         const uint32_t nprob = same ? 1u : 2u, npts = 2u * n_asg + (same ? 0u : 2u * n_sc);
         unsigned long long mi = 0, rp = 0, pk = 0;
@@ -467,11 +449,7 @@ __global__ __launch_bounds__(FD_WAVE) void k_rs_slots(rs_args A) {
         }
         ++n_emit;
         RS_SYNC();
-        stamp(12);
     }
-    stamp(5);
-    if (A.dbg_slot && lane == 0) A.dbg_slot[slot] = make_uint4(F, c1 - c0, n_comp, (uint32_t)(wall_clock64() - t_slot0));
-    if (A.dbg && lane == 0) atomicAdd(&A.dbg[6], 1ull);
     if (lane == 0 && A.slot_matches) A.slot_matches[slot] = n_emit;
 }
 
@@ -961,32 +939,6 @@ void fd_launch_rs_slots(const rs_args &A, uint32_t n_cand, hipStream_t st) {
     hipLaunchKernelGGL(k_rs_slots, dim3(n_cand), dim3(FD_WAVE), 0, st, B);
 }
 
-// The caller's match records (fd_match_rec, 39 words) and residue lists in their final order, gathered on the device: one wavefront per
-// record; plan[k] = {source record, candidate slot inside its query, first output residue, residue ints}.  The host only orders the
-// records (a counting sort over 32-byte headers); the 8 scattered reads per record it did in the solution arrays are lanes here.
-__global__ __launch_bounds__(FD_WAVE) void k_rs_records(const rs_match_dev *__restrict__ m, const uint4 *__restrict__ plan, const float *__restrict__ rmsd,
-                                                        const float *__restrict__ rot, const float *__restrict__ tran, const float *__restrict__ met,
-                                                        const int32_t *__restrict__ residues, uint32_t *__restrict__ out, int32_t *__restrict__ out_res) {
-    const uint64_t k = blockIdx.x;
-    const uint32_t lane = threadIdx.x;
-    const uint4 pl = plan[k];
-    const rs_match_dev r = m[pl.x];
-    const uint32_t pf = r.prob0, po = r.same ? r.prob0 : r.prob1;
-    uint32_t v = 0;
-    if (lane == 0) v = pl.y;
-    else if (lane == 1) v = r.same;
-    else if (lane == 2) v = __float_as_uint(r.idf);
-    else if (lane == 3) v = __float_as_uint(rmsd[po]);
-    else if (lane == 4) v = __float_as_uint(rmsd[pf]);
-    else if (lane < 14) v = __float_as_uint(rot[9ull * po + (lane - 5)]);
-    else if (lane < 17) v = __float_as_uint(tran[3ull * po + (lane - 14)]);
-    else if (lane < 22) v = __float_as_uint(met[5ull * po + (lane - 17)]);
-    else if (lane < 31) v = __float_as_uint(rot[9ull * pf + (lane - 22)]);
-    else if (lane < 34) v = __float_as_uint(tran[3ull * pf + (lane - 31)]);
-    else if (lane < 39) v = __float_as_uint(met[5ull * pf + (lane - 34)]);
-    if (lane < 39) out[39ull * k + lane] = v;
-    for (uint32_t z = lane; z < pl.w; z += FD_WAVE) out_res[(uint64_t)pl.z + z] = residues[(uint64_t)r.res_pos + z];
-}
 // Final places of the records without the host: exclusive scan of the slots' record counts (base of every slot), the per-query offsets the
 // caller gets (match_off[t] = base of query t's first slot, res_off = running 2 * n_idx * records) and every slot's first output residue.
 __global__ __launch_bounds__(1024) void k_rs_offsets(const uint32_t *__restrict__ slot_matches, uint32_t n_cand, const uint64_t *__restrict__ cand_off,
@@ -1057,9 +1009,4 @@ void fd_launch_rs_records_dev(const void *matches, uint64_t n, const uint32_t *s
     hipLaunchKernelGGL(k_rs_offsets, dim3(1), dim3(1024), 0, st, slot_matches, n_cand, cand_off, slot_q, qt, n_queries, mbase, rbase, match_off, res_off);
     if (n) hipLaunchKernelGGL(k_rs_records_dev, dim3((unsigned)n), dim3(FD_WAVE), 0, st, (const rs_match_dev *)matches, mbase, rbase, cand_off, slot_q, qt, rmsd, rot, tran, met,
                               residues, (uint32_t *)out, out_res);
-}
-void fd_launch_rs_records(const void *matches, const void *plan, uint64_t n, const float *rmsd, const float *rot, const float *tran, const float *met,
-                          const int32_t *residues, void *out, int32_t *out_res, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_rs_records, dim3((unsigned)n), dim3(FD_WAVE), 0, st, (const rs_match_dev *)matches, (const uint4 *)plan, rmsd, rot, tran, met, residues,
-                              (uint32_t *)out, out_res);
 }

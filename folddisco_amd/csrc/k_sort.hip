@@ -203,8 +203,8 @@ __global__ __launch_bounds__(RS_BINS) void k_rs_scan_tot(uint64_t *__restrict__ 
 //   3. keys / payloads are placed digit-contiguously in LDS and leave as runs (neighbouring tiles of one XCD complete each
 //      other's partial lines in L2: PMC traffic 1.03x algorithmic).
 // Full tiles run without any bounds predicate.  The kernel sits at 5.9 ms per pass against 4.8 ms for its own memory
-// skeleton (k_rs_copy_floor).
-template <int THREADS, int ITEMS, typename V, bool FULL, bool PACK = false>
+// skeleton (a load / LDS / store copy of the tile without ranking, measured once: HISTORY.md).
+template <int THREADS, int ITEMS, typename V, bool FULL>
 __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ keys_in, const V *__restrict__ vals_in,
                                                  uint32_t *__restrict__ keys_out, V *__restrict__ vals_out, uint64_t n, uint32_t shift,
                                                  uint32_t mask, const uint32_t *__restrict__ ghist_row, const uint64_t *__restrict__ dbase,
@@ -279,8 +279,8 @@ __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ ke
     for (int c = 0; c < ITEMS; ++c) {
         if (FULL || (uint32_t)(c * 64) + lane < n_wave) {
             uint32_t pos = cnt[(key[c] >> shift) & mask] + rnk[c];
-            if (PACK) reinterpret_cast<uint2 *>(s_keys)[pos] = make_uint2(key[c], (uint32_t)val[c]);
-            else { s_keys[pos] = key[c]; s_vals[pos] = val[c]; }
+            s_keys[pos] = key[c];
+            s_vals[pos] = val[c];
         }
     }
     __syncthreads();
@@ -288,18 +288,14 @@ __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ ke
 #pragma unroll
         for (int c = 0; c < ITEMS; ++c) {
             uint32_t k = c * THREADS + tid;
-            uint32_t kk, vv;
-            if (PACK) { uint2 e = reinterpret_cast<const uint2 *>(s_keys)[k]; kk = e.x; vv = e.y; }
-            else { kk = s_keys[k]; vv = (uint32_t)s_vals[k]; }
+            const uint32_t kk = s_keys[k], vv = (uint32_t)s_vals[k];
             long long g = (long long)k + s_gofs[(kk >> shift) & mask];
             keys_out[g] = kk;
             vals_out[g] = (V)vv;
         }
     } else {
         for (uint32_t k = tid; k < n_tile; k += THREADS) {
-            uint32_t kk, vv;
-            if (PACK) { uint2 e = reinterpret_cast<const uint2 *>(s_keys)[k]; kk = e.x; vv = e.y; }
-            else { kk = s_keys[k]; vv = (uint32_t)s_vals[k]; }
+            const uint32_t kk = s_keys[k], vv = (uint32_t)s_vals[k];
             long long g = (long long)k + s_gofs[(kk >> shift) & mask];
             keys_out[g] = kk;
             vals_out[g] = (V)vv;
@@ -307,45 +303,15 @@ __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ ke
     }
 }
 
-// measurement aid (FDGPU_SORT=classic30): the scatter's memory skeleton without ranking — load the tile like k_rs_scatter4, stage
-// through LDS, store the tile back in place order.  NOT a sort; used only to read off the kernel's memory floor.
 template <int THREADS, int ITEMS, typename V>
-__global__ __launch_bounds__(THREADS) void k_rs_copy_floor(const uint32_t *__restrict__ keys_in, const V *__restrict__ vals_in,
-                                                           uint32_t *__restrict__ keys_out, V *__restrict__ vals_out, uint64_t n, uint32_t nb) {
-    constexpr int TILE = THREADS * ITEMS;
-    __shared__ uint32_t s_keys[TILE];
-    __shared__ V s_vals[TILE];
-    const uint32_t tile = fd_xcd_remap(blockIdx.x, nb);
-    if (tile >= nb || (uint64_t)(tile + 1) * TILE > n) return;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const uint64_t tile_base = (uint64_t)tile * TILE;
-    const uint32_t *kp = keys_in + tile_base + (uint64_t)wid * (64 * ITEMS) + lane;
-    const V *vp = vals_in + tile_base + (uint64_t)wid * (64 * ITEMS) + lane;
-    uint32_t key[ITEMS];
-    V val[ITEMS];
-#pragma unroll
-    for (int c = 0; c < ITEMS; ++c) { key[c] = kp[c * 64]; val[c] = vp[c * 64]; }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < ITEMS; ++c) { uint32_t pos = wid * 64 * ITEMS + c * 64 + lane; s_keys[pos] = key[c]; s_vals[pos] = val[c]; }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < ITEMS; ++c) {
-        uint32_t k = c * THREADS + tid;
-        keys_out[tile_base + k] = s_keys[k];
-        vals_out[tile_base + k] = s_vals[k];
-    }
-}
-
-template <int THREADS, int ITEMS, typename V, bool PACK = false>
 __global__ __launch_bounds__(THREADS) void k_rs_scatter4(const uint32_t *__restrict__ keys_in, const V *__restrict__ vals_in,
                                                          uint32_t *__restrict__ keys_out, V *__restrict__ vals_out, uint64_t n,
                                                          uint32_t shift, uint32_t mask, const uint32_t *__restrict__ ghist, uint32_t nb,
                                                          const uint64_t *__restrict__ dbase) {
     constexpr int TILE = THREADS * ITEMS;
     constexpr int WAVES = THREADS / 64;
-    __shared__ __attribute__((aligned(8))) uint32_t s_keys[PACK ? 2 * TILE : TILE];
-    __shared__ V s_vals[PACK ? 1 : TILE];
+    __shared__ __attribute__((aligned(8))) uint32_t s_keys[TILE];
+    __shared__ V s_vals[TILE];
     __shared__ uint32_t s_cnt[WAVES][RS_BINS];
     __shared__ long long s_gofs[RS_BINS];
     __shared__ uint64_t sm[17];
@@ -353,11 +319,11 @@ __global__ __launch_bounds__(THREADS) void k_rs_scatter4(const uint32_t *__restr
     if (tile >= nb) return;
     const uint64_t tile_base = (uint64_t)tile * TILE;
     if (tile_base + TILE <= n)
-        rs_scatter4_body<THREADS, ITEMS, V, true, PACK>(keys_in, vals_in, keys_out, vals_out, n, shift, mask, ghist + (uint64_t)tile * RS_BINS, dbase, tile_base, TILE, s_keys,
-                                                        s_vals, s_cnt, s_gofs, sm);
+        rs_scatter4_body<THREADS, ITEMS, V, true>(keys_in, vals_in, keys_out, vals_out, n, shift, mask, ghist + (uint64_t)tile * RS_BINS, dbase, tile_base, TILE, s_keys,
+                                                  s_vals, s_cnt, s_gofs, sm);
     else
-        rs_scatter4_body<THREADS, ITEMS, V, false, PACK>(keys_in, vals_in, keys_out, vals_out, n, shift, mask, ghist + (uint64_t)tile * RS_BINS, dbase, tile_base,
-                                                         (uint32_t)(n - tile_base), s_keys, s_vals, s_cnt, s_gofs, sm);
+        rs_scatter4_body<THREADS, ITEMS, V, false>(keys_in, vals_in, keys_out, vals_out, n, shift, mask, ghist + (uint64_t)tile * RS_BINS, dbase, tile_base,
+                                                   (uint32_t)(n - tile_base), s_keys, s_vals, s_cnt, s_gofs, sm);
 }
 
 // ------------------------------------------------------------------------ segmented form (MSD index build)
@@ -478,24 +444,22 @@ __global__ __launch_bounds__(THREADS) void k_rs_scatter4_seg(const uint32_t *__r
     rs_seg_lookup(D, v, &seg, &base, &cnt);
     if (!cnt) return;
     if (cnt == TILE)
-        rs_scatter4_body<THREADS, ITEMS, V, true, false>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
-                                                         TILE, s_keys, s_vals, s_cnt, s_gofs, sm);
+        rs_scatter4_body<THREADS, ITEMS, V, true>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
+                                                  TILE, s_keys, s_vals, s_cnt, s_gofs, sm);
     else
-        rs_scatter4_body<THREADS, ITEMS, V, false, false>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
-                                                          cnt, s_keys, s_vals, s_cnt, s_gofs, sm);
+        rs_scatter4_body<THREADS, ITEMS, V, false>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
+                                                   cnt, s_keys, s_vals, s_cnt, s_gofs, sm);
 }
 
-// LSD radix sort, 8-bit digits.  FDGPU_SORT=classicN selects measured alternatives: 18 = 512x16-key tiles (default, fastest),
-// 19 = 256x16, 20 = 512x8, 21 = 512x16 with packed 8-byte LDS staging, 30 = memory skeleton only (NOT a sort, see
-// k_rs_copy_floor).  Earlier generations (LDS-atomic ranking, persistent software-pipelined scatter, 16-bit counters for a third
-// workgroup per CU, decoupled-look-back onesweep, 3 x 10-bit digits) were slower and are documented in DESIGN.md §4 / §9.
-static int g_rs_variant = 18;
-void fd_rs_set_variant(int v) { g_rs_variant = v; }
-uint32_t fd_rs_num_tiles(uint64_t n) { return (uint32_t)((n + 2048 - 1) / 2048); }  // upper bound over variants (workspace sizing)
+// LSD radix sort, 8-bit digits, 512x16-key tiles.  The measured alternatives (256x16, 512x8, packed 8-byte LDS staging) and
+// earlier generations (LDS-atomic ranking, persistent software-pipelined scatter, 16-bit counters for a third workgroup per CU,
+// decoupled-look-back onesweep, 3 x 10-bit digits) were slower and are documented in DESIGN.md §4 / §9 and HISTORY.md.
+uint32_t fd_rs_num_tiles(uint64_t n) { return (uint32_t)((n + 2048 - 1) / 2048); }  // workspace sizing (a bound on the tile count)
 
-template <int THREADS, int ITEMS, typename V, bool PACK = false>
+template <typename V>
 static void rs_pass4(uint32_t *ki, V *vi, uint32_t *ko, V *vo, uint64_t n, uint32_t shift, uint32_t mask, uint32_t *ghist, uint64_t *tot,
                      hipStream_t st, fdgpu_ctx *tc) {
+    constexpr int THREADS = 512, ITEMS = 16;
     uint32_t nb = (uint32_t)((n + THREADS * ITEMS - 1) / (THREADS * ITEMS));
     uint32_t grid = ((nb + 7u) / 8u) * 8u;
     {
@@ -513,7 +477,7 @@ static void rs_pass4(uint32_t *ki, V *vi, uint32_t *ko, V *vo, uint64_t n, uint3
     }
     {
         StageTimer t(tc, "rs_scatter", n * (8 + 2 * sizeof(V)));
-        hipLaunchKernelGGL((k_rs_scatter4<THREADS, ITEMS, V, PACK>), dim3(grid), dim3(THREADS), 0, st, ki, vi, ko, vo, n, shift, mask, ghist, nb, tot);
+        hipLaunchKernelGGL((k_rs_scatter4<THREADS, ITEMS, V>), dim3(grid), dim3(THREADS), 0, st, ki, vi, ko, vo, n, shift, mask, ghist, nb, tot);
     }
 }
 
@@ -527,18 +491,7 @@ static int radix_sort_pairs_t(uint32_t *keys_a, V *vals_a, uint32_t *keys_b, V *
         uint32_t mask = (uint32_t)((1ull << bits) - 1ull);
         uint32_t *ki = cur ? keys_b : keys_a, *ko = cur ? keys_a : keys_b;
         V *vi = cur ? vals_b : vals_a, *vo = cur ? vals_a : vals_b;
-        switch (g_rs_variant) {
-            case 19: rs_pass4<256, 16, V>(ki, vi, ko, vo, n, (uint32_t)shift, mask, ghist, tot, st, tc); break;
-            case 20: rs_pass4<512, 8, V>(ki, vi, ko, vo, n, (uint32_t)shift, mask, ghist, tot, st, tc); break;
-            case 21: rs_pass4<512, 16, V, true>(ki, vi, ko, vo, n, (uint32_t)shift, mask, ghist, tot, st, tc); break;
-            case 30: {   // memory floor of the scatter (see k_rs_copy_floor); the result is NOT sorted
-                uint32_t nb = (uint32_t)((n + 8191) / 8192), grid = ((nb + 7u) / 8u) * 8u;
-                StageTimer t(tc, "rs_scatter", n * (8 + 2 * sizeof(V)));
-                hipLaunchKernelGGL((k_rs_copy_floor<512, 16, V>), dim3(grid), dim3(512), 0, st, ki, vi, ko, vo, n, nb);
-                break;
-            }
-            default: rs_pass4<512, 16, V>(ki, vi, ko, vo, n, (uint32_t)shift, mask, ghist, tot, st, tc); break;
-        }
+        rs_pass4<V>(ki, vi, ko, vo, n, (uint32_t)shift, mask, ghist, tot, st, tc);
         cur ^= 1;
     }
     return cur;

@@ -365,19 +365,18 @@ def test_tiled_scoring_equals_occupancy_rows(human, monkeypatch):
     queries.insert(2, (np.zeros(0, np.uint32),) * 3)
     queries.append((np.array([0x3fffffff], np.uint32), np.zeros(1, np.uint32), np.ones(1, np.uint32)))      # absent hash only
 
-    def run(index, penalty, total, top_n, tiled, tile="13"):
+    def run(index, penalty, total, top_n, tiled):
         monkeypatch.setenv("FDGPU_QTILE", "1" if tiled else "0")
-        monkeypatch.setenv("FDGPU_QT_TILE", tile)
         return fd.count_query_batch(ctx, index, queries, penalty, total_structures=total, top_n=top_n)
 
     full = run(ix, pen, HUMAN, 0, False)
     assert max(len(f) for f in full) > 15000          # most of the tiles touched
     for N in (1, 20, 1000, 3000):
-        a, a14, b = run(ix, pen, HUMAN, N, True), run(ix, pen, HUMAN, N, True, "14"), run(ix, pen, HUMAN, N, False)
-        for f, x, x14, y in zip(full, a, a14, b):
-            assert x.tobytes() == x14.tobytes() == y.tobytes() == rank_hits(f, N).tobytes(), N
+        a, b = run(ix, pen, HUMAN, N, True), run(ix, pen, HUMAN, N, False)
+        for f, x, y in zip(full, a, b):
+            assert x.tobytes() == y.tobytes() == rank_hits(f, N).tobytes(), N
     # query maps made against the index carry their lists' positions and lengths: pass B then reads the decoded stream pass A left
-    # (k_qt_rows) instead of decoding the lists again — both forms, both tile sizes, against the ranked full list
+    # (k_qt_rows) instead of decoding the lists again — both forms, against the ranked full list
     from folddisco_amd import query as fq
     Qs = human["queries"]
     qall = ctx.upload(fd.PackedStructures.concat([Q["q"].as_item() for Q in Qs]))
@@ -387,24 +386,21 @@ def test_tiled_scoring_equals_occupancy_rows(human, monkeypatch):
     monkeypatch.setenv("FDGPU_QTILE", "1")
     monkeypatch.setenv("FDGPU_QT32", "0")
     for N in (5, 1000):
-        for tile in ("13", "14"):
-            for stream in ("1", "0"):
-                monkeypatch.setenv("FDGPU_QT_TILE", tile); monkeypatch.setenv("FDGPU_QT_STREAM", stream)
-                got = fd.count_query_maps(ctx, ix, qms, pen, total_structures=HUMAN, top_n=N)
-                for f, x in zip(full_m, got):
-                    assert x.tobytes() == rank_hits(f, N).tobytes(), (N, tile, stream)
-    monkeypatch.delenv("FDGPU_QT_STREAM")
-    # ... and the default since round 6: 32-bit sums over a planned slot stream (k_qscore32.hip; tiles of 2^14 or 2^15 structures), every cut
-    # incl. the ones that take the whole tile's keys (more than the tile holds), ties around the cut, a shard's sub-range of the ids
-    for mode in ("13", "14", "15"):
-        monkeypatch.setenv("FDGPU_QT32", mode)
-        for N in (1, 5, 1000, 3000):
+        for stream in ("1", "0"):
+            monkeypatch.setenv("FDGPU_QT_STREAM", stream)
             got = fd.count_query_maps(ctx, ix, qms, pen, total_structures=HUMAN, top_n=N)
             for f, x in zip(full_m, got):
-                assert x.tobytes() == rank_hits(f, N).tobytes(), (N, mode)
+                assert x.tobytes() == rank_hits(f, N).tobytes(), (N, stream)
+    monkeypatch.delenv("FDGPU_QT_STREAM")
+    # ... and the default since round 6: 32-bit sums over a planned slot stream (k_qscore32.hip), every cut incl. the ones that take the
+    # whole tile's keys (more than the tile holds), ties around the cut, a shard's sub-range of the ids
+    monkeypatch.delenv("FDGPU_QT32")
+    for N in (1, 5, 1000, 3000):
+        got = fd.count_query_maps(ctx, ix, qms, pen, total_structures=HUMAN, top_n=N)
+        for f, x in zip(full_m, got):
+            assert x.tobytes() == rank_hits(f, N).tobytes(), N
     # a decoded stream too small for the batch (FDGPU_QT_STREAM_CAP: the bound the host sizes it by, cut down): the tiles that do not fit are not scored,
     # their queries raise the selection's overflow flag and the call is ranked by the compacting path — same records
-    monkeypatch.setenv("FDGPU_QT32", "14")
     for cap_recs in ("64", "20000"):
         monkeypatch.setenv("FDGPU_QT_STREAM_CAP", cap_recs)
         got = fd.count_query_maps(ctx, ix, qms, pen, total_structures=HUMAN, top_n=1000)
@@ -419,16 +415,13 @@ def test_tiled_scoring_equals_occupancy_rows(human, monkeypatch):
     full_sm = fd.count_query_maps(ctx, sub_m, qms_s, pen[3000:20000].copy(), total_structures=HUMAN, top_n=0)
     assert all((f["nid"] >= 3000).all() and (f["nid"] < 20000).all() for f in full_sm if len(f))
     monkeypatch.setenv("FDGPU_QTILE", "1")
-    for mode in ("13", "14", "15"):
-        monkeypatch.setenv("FDGPU_QT32", mode)
-        for N in (50, 1000):
-            got = fd.count_query_maps(ctx, ix, qms, ones, total_structures=HUMAN, top_n=N)
-            for f, x in zip(full_1, got):
-                assert x.tobytes() == rank_hits(f, N).tobytes(), (N, mode, "ties")
-            got = fd.count_query_maps(ctx, sub_m, qms_s, pen[3000:20000].copy(), total_structures=HUMAN, top_n=N)
-            for f, x in zip(full_sm, got):
-                assert x.tobytes() == rank_hits(f, N).tobytes(), (N, mode, "shard")
-    monkeypatch.delenv("FDGPU_QT32")
+    for N in (50, 1000):
+        got = fd.count_query_maps(ctx, ix, qms, ones, total_structures=HUMAN, top_n=N)
+        for f, x in zip(full_1, got):
+            assert x.tobytes() == rank_hits(f, N).tobytes(), (N, "ties")
+        got = fd.count_query_maps(ctx, sub_m, qms_s, pen[3000:20000].copy(), total_structures=HUMAN, top_n=N)
+        for f, x in zip(full_sm, got):
+            assert x.tobytes() == rank_hits(f, N).tobytes(), (N, "shard")
     # ties: a penalty of 1 makes the key a function of the matched rows alone — thousands of equal keys around the cut
     one = np.ones_like(pen)
     full1 = run(ix, one, HUMAN, 0, False)

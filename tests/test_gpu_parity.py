@@ -813,10 +813,9 @@ def test_count_query_against_recount_packed_and_wide(ctx):
 
 def test_msd_build_equals_structure_major_build(ctx):
     """The default index build of the default encoding (keys bucketed by the top six hash bits at emit time, residues visited in
-    amino-acid order, three segmented 8-bit sort passes) against the structure-major stream + four passes (FDGPU_MSD=0) and against the
-    buckets without the amino-acid order (FDGPU_MSD_PERM=0): byte-identical indices, for shapes that stress the bucket bookkeeping — one
-    residue type only, unknown residues and missing CB mixed in, a structure longer than one tile row, empty structures, a shard that
-    starts at a late id."""
+    amino-acid order, three segmented 8-bit sort passes) against the structure-major stream + four passes (FDGPU_MSD=0): byte-identical
+    indices, for shapes that stress the bucket bookkeeping — one residue type only, unknown residues and missing CB mixed in, a structure
+    longer than one tile row, empty structures, a shard that starts at a late id."""
     import os
     import folddisco_amd as fd
     from folddisco_amd import synth
@@ -833,9 +832,8 @@ def test_msd_build_equals_structure_major_build(ctx):
     ps_odd = fd.PackedStructures(ps.res_off, ps.n_xyz, ps.ca_xyz, ps.cb_xyz, np.where(np.arange(len(aa)) % 97 == 5, 25, aa).astype(np.uint8), cbv)
     outs = {}
     try:
-        for tag, env in (("msd", {}), ("plain", {"FDGPU_MSD": "0"}), ("noperm", {"FDGPU_MSD_PERM": "0"})):
-            for k in ("FDGPU_MSD", "FDGPU_MSD_PERM"):
-                os.environ.pop(k, None)
+        for tag, env in (("msd", {}), ("plain", {"FDGPU_MSD": "0"})):
+            os.environ.pop("FDGPU_MSD", None)
             os.environ.update(env)
             ix = fd.FolddiscoIndex.build(ctx, ctx.upload(ps), first_id=70000)
             outs[tag] = ix.export()
@@ -843,13 +841,11 @@ def test_msd_build_equals_structure_major_build(ctx):
             # structure-major path and equals what the plain build gives for the same input
             outs[tag + "_odd"] = fd.FolddiscoIndex.build(ctx, ctx.upload(ps_odd), first_id=70000).export()
     finally:
-        for k in ("FDGPU_MSD", "FDGPU_MSD_PERM"):
-            os.environ.pop(k, None)
-    for tag in ("plain", "noperm"):
-        for a, b in zip(outs["msd"], outs[tag]):
-            assert np.array_equal(a, b), tag
-        for a, b in zip(outs["msd_odd"], outs[tag + "_odd"]):
-            assert np.array_equal(a, b), tag
+        os.environ.pop("FDGPU_MSD", None)
+    for a, b in zip(outs["msd"], outs["plain"]):
+        assert np.array_equal(a, b), "plain"
+    for a, b in zip(outs["msd_odd"], outs["plain_odd"]):
+        assert np.array_equal(a, b), "plain_odd"
     assert not np.array_equal(outs["msd"][1], outs["msd_odd"][1])
     assert len(outs["msd"][1]) > 10 ** 6
 
