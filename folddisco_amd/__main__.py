@@ -1,4 +1,4 @@
-"""`python -m folddisco_amd index|query …` — the reference's two hot-path subcommands with its flag names and defaults
+"""`python -m folddisco_amd index|query|update …` — the reference's two hot-path subcommands (and `update`, which it lacks) with its flag names and defaults
 (src/cli/main.rs:26-110, src/cli/workflows/build_index.rs:64-241, src/cli/workflows/query_pdb.rs:144-519), driving the
 GPU path through the C ABI.  Structure order = lexicographic path order (the reference uses readdir order, which is
 filesystem dependent; SURVEY §7 hard part 3).  Only the default PDBTrRosetta encoding is supported; input is PDB or mmCIF, optionally gzip."""
@@ -232,6 +232,97 @@ def _cmd_index_sharded(a, fd, indexio, structure, paths, prefix, rank, world):
     dist.destroy_process_group()
 
 
+INDEX_FILES = ("", ".offset", ".lookup", ".type")
+
+
+def _update_plan(a):
+    """everything `update` decides before it touches a device: the index's rows and settings, the keep mask, the files to append.
+    Refusals exit with status 1 and change nothing."""
+    from folddisco_amd import indexio
+    if not a.index:
+        sys.exit("[FAIL] -i/--index is required")
+    if not a.pdbs and not a.remove:
+        sys.exit("[FAIL] update: give structures to append (-p) and / or a file of tids to remove (--remove)")
+    for ext in INDEX_FILES:
+        if not os.path.exists(a.index + ext):
+            sys.exit(f"[FAIL] {a.index}{ext} not found")
+    rows = indexio.read_lookup_rows(a.index + ".lookup")
+    tids = [r.rstrip("\n").split("\t")[1] for r in rows]
+    cfg = indexio.load_type(a.index + ".type")
+    with open(a.index + ".type") as f:
+        type_text = f.read()
+    fczdb = cfg.get("input_format") == "FCZDB"
+    keep = np.ones(len(rows), dtype=bool)
+    if a.remove:
+        with open(a.remove) as f:
+            gone = [line.strip() for line in f if line.strip()]
+        known = set(tids)
+        unknown = [t for t in dict.fromkeys(gone) if t not in known]
+        if unknown:
+            sys.exit(f"[FAIL] update: {len(unknown)} tid(s) of {a.remove} are not in {a.index}.lookup: " + ", ".join(unknown[:10]) +
+                     (" ..." if len(unknown) > 10 else ""))
+        gone = set(gone)
+        keep = np.array([t not in gone for t in tids], dtype=bool)
+        if not keep.any():
+            sys.exit("[FAIL] update: removing every structure is refused (build a new index with `index`)")
+    add_paths = []
+    if a.pdbs:
+        if fczdb:
+            sys.exit("[FAIL] update: appending to an index built from a Foldcomp database is not supported (-p); --remove is")
+        add_paths = _load_paths(a.pdbs, a.recursive)
+        if not add_paths:
+            sys.exit(f"[FAIL] no structures under {a.pdbs}")
+    return dict(rows=rows, keep=keep, cfg=cfg, type_text=type_text, fczdb=fczdb, add_paths=add_paths)
+
+
+def cmd_update(a):
+    """`update`: remove structures from an index and / or append new ones without a rebuild.  The result is byte for byte the index `index`
+    builds over (kept structures in their old order) + (added structures in walk order): the resident index is pruned on the device
+    (fdgpu_index_remove), the added structures are built at the next ids with the hash parameters of PREFIX.type and merged on the device
+    (fdgpu_index_merge).  The four files are written under temporary names beside the output prefix and then renamed over it."""
+    plan = _update_plan(a)
+    import folddisco_amd as fd
+    from folddisco_amd import indexio, structure
+    cfg, keep, add_paths = plan["cfg"], plan["keep"], plan["add_paths"]
+    # hash parameters of the existing index, never the command line's defaults
+    a.distance, a.angle, a.grid = int(cfg.get("num_bin_dist", 0)), int(cfg.get("num_bin_angle", 0)), float(cfg.get("grid_width", 20.0))
+    a.hash_type, a.multi = hash_type_index(cfg.get("hash_type", "PDBTrRosetta")), cfg.get("multiple_bin")
+    a.fc = None
+    n_kept = int(keep.sum())
+    ctx = fd.Context(a.device)
+    v, h, o = indexio.read_index_files(a.index)
+    ix = fd.FolddiscoIndex.load(ctx, h, o, v, len(keep))
+    del v, h, o
+    if n_kept < len(keep):
+        pruned = ix.remove(keep)
+        del ix                                   # the loaded index is released once the pruned one exists
+        ix = pruned
+    rows = indexio.update_lookup_rows(plan["rows"], keep, keep_db_keys=plan["fczdb"])
+    if add_paths:
+        a.timings = {}
+        parts, nres, plddt = _build_chunks(a, fd, structure, ctx, add_paths, n_kept, resident=True)
+        ix = _merge_resident(fd, [ix] + parts)
+        del parts
+        rows += indexio.lookup_rows(n_kept, [indexio.parse_path_by_id_type(x, a.id) for x in add_paths], nres, plddt)
+    out = a.output or a.index
+    tmp = f"{out}.update-tmp{os.getpid()}"
+    try:
+        ix.save(tmp)
+        with open(tmp + ".lookup", "w", newline="") as f:
+            f.writelines(rows)
+        with open(tmp + ".type", "w") as f:
+            f.write(indexio.update_type_text(plan["type_text"], len(rows)))
+        for ext in INDEX_FILES:
+            os.replace(tmp + ext, out + ext)
+    finally:
+        for ext in INDEX_FILES:
+            if os.path.exists(tmp + ext):
+                os.remove(tmp + ext)
+    if a.verbose:
+        print(f"[DONE] {len(keep) - n_kept} removed, {len(add_paths)} added: {len(rows)} structures, {ix.num_hashes} hashes, {ix.value_len} value bytes -> {out}",
+              file=sys.stderr)
+
+
 def cmd_query(a):
     import folddisco_amd as fd
     from folddisco_amd import indexio, query, structure
@@ -398,6 +489,17 @@ def main(argv=None):
     pq.add_argument("-o", "--output", default="")
     pq.add_argument("-v", "--verbose", action="store_true")
     pq.add_argument("--device", type=int, default=0)
+    pu = sub.add_parser("update")                                    # index update without a rebuild (no counterpart in the reference)
+    pu.add_argument("-i", "--index", required=True)
+    pu.add_argument("-p", "--pdbs", default="", help="structures to append: a directory or a file, walked and ordered as `index` does")
+    pu.add_argument("--remove", default="", help="text file with one tid per line (column 2 of PREFIX.lookup); every row with that tid is removed")
+    pu.add_argument("-o", "--output", default="", help="output prefix (default: rewrite PREFIX in place)")
+    pu.add_argument("--id", default="relpath", help="--id of the added structures' tids: the one the index was built with")
+    pu.add_argument("-r", "--recursive", action="store_true")
+    pu.add_argument("-t", "--threads", type=int, default=1)
+    pu.add_argument("--chunk", type=int, default=16384)
+    pu.add_argument("--device", type=int, default=0)
+    pu.add_argument("-v", "--verbose", action="store_true")
     pa = sub.add_parser("analyze")                                   # src/cli/workflows/analyze.rs:19-40 (summary branch)
     pa.add_argument("-i", "--index", required=True)
     pa.add_argument("-p", "--pdbs", default=None)
@@ -424,6 +526,9 @@ def main(argv=None):
             return
         out = a.output or f"{a.index}_summary"                       # analyze.rs:71-84
         analyze.save_summary(analyze.summarize(a.index), out, a.top)
+        return
+    if a.cmd == "update":
+        cmd_update(a)
         return
     if a.cmd == "index":
         if a.mmap_on_disk and a.verbose:

@@ -186,6 +186,7 @@ SYMBOLS = [
     ("fdgpu_merge_subindices", C.c_int, [C.c_uint64, C.POINTER(u8p), C.POINTER(u32p), C.POINTER(u64p), u64p, C.POINTER(u8p), u64p,
                                          C.POINTER(u32p), C.POINTER(u64p), u64p]),
     ("fdgpu_index_merge", C.c_int, [VP, C.POINTER(VP), C.c_uint64, C.POINTER(VP)]),
+    ("fdgpu_index_remove", C.c_int, [VP, VP, u8p, C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_posting_bytes", C.c_int, [VP, VP, u32p, C.c_uint64, u64p]),
     ("fdgpu_index_set_first_id", C.c_int, [VP, C.c_uint64]),
     ("fdgpu_host_libm_matches", C.c_int, [VP]),

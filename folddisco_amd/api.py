@@ -233,6 +233,23 @@ class FolddiscoIndex:
     def save(self, prefix: str):
         self.ctx.check(self.ctx.L.fdgpu_index_save(self.ctx.h, self.h, prefix.encode()))
 
+    # ---- index update: byte-identical to a fresh build over (kept structures in their order) + (added structures)
+    def remove(self, keep) -> "FolddiscoIndex":
+        """a new resident index without the structures whose keep[s] is false (fdgpu_index_remove): the kept ones are renumbered
+        densely from first_id in their old order; this index stays valid"""
+        k = np.ascontiguousarray(np.asarray(keep).astype(bool).astype(np.uint8))
+        if k.ndim != 1 or len(k) != self.n_structures:
+            raise ValueError(f"keep: {self.n_structures} entries expected, got {k.shape}")
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.fdgpu_index_remove(self.ctx.h, self.h, _ptr(k, u8p), len(k), C.byref(h)))
+        return FolddiscoIndex(self.ctx, h, int(k.sum()), self.first_id)
+
+    def append(self, ctx: Context, batch: Batch, **hash_params) -> "FolddiscoIndex":
+        """a new resident index over this one's structures followed by the batch's (built at first_id + n_structures with the given
+        hash parameters, those of FolddiscoIndex.build, and merged on the device); this index stays valid"""
+        part = FolddiscoIndex.build(ctx, batch, first_id=self.first_id + self.n_structures, **hash_params)
+        return FolddiscoIndexSet([self, part]).merge()
+
     # ---- one on-disk index from N ranks (fd_shard_index.hip; SURVEY §8e row 2, Option A)
     def range_bounds(self, n_ranges: int) -> np.ndarray:
         """n_ranges - 1 ascending hash values cutting this index into ranges of about equal posting bytes"""

@@ -99,6 +99,47 @@ def load_lookup(path: str):
     return tids, np.array(nres, np.uint64), np.array(plddt, np.float32), np.array(keys, np.uint64)
 
 
+def read_lookup_rows(path: str):
+    """PREFIX.lookup as its raw lines (newline kept), for the index update's verbatim rewrite"""
+    with open(path, newline="") as f:
+        return f.readlines()
+
+
+def update_lookup_rows(rows, keep, keep_db_keys: bool):
+    """the kept rows of PREFIX.lookup after an index update: tid, nres and plddt verbatim, the id renumbered densely in the old order; the
+    db_key column renumbered too for a file-built index (there it equals the id) and left as it was for a Foldcomp-built one (its database key)"""
+    keep = np.asarray(keep, dtype=bool)
+    if len(keep) != len(rows):
+        raise ValueError(f"keep: {len(rows)} entries expected, got {len(keep)}")
+    out, i = [], 0
+    for row, k in zip(rows, keep):
+        if not k:
+            continue
+        p = row.rstrip("\n").split("\t")
+        p[0] = str(i)
+        if len(p) > 4 and not keep_db_keys:
+            p[4] = str(i)
+        out.append("\t".join(p) + "\n")
+        i += 1
+    return out
+
+
+def lookup_rows(first: int, tids, nres, plddt, db_keys=None):
+    """PREFIX.lookup lines of structures first, first + 1, ... (the format of save_lookup)"""
+    return [f"{first + i}\t{tid}\t{int(nres[i])}\t{format_f32_display(plddt[i])}\t{first + i if db_keys is None else int(db_keys[i])}\n"
+            for i, tid in enumerate(tids)]
+
+
+def update_type_text(text: str, n_structures: int) -> str:
+    """PREFIX.type after an index update: chunk_size = the new number of structures, every other line as it was"""
+    lines = text.splitlines(keepends=True)
+    hit = [k for k, line in enumerate(lines) if line.split("=", 1)[0].strip() == "chunk_size"]
+    if len(hit) != 1:
+        raise ValueError("index type file: no chunk_size line")
+    lines[hit[0]] = f"chunk_size = {int(n_structures)}\n"
+    return "".join(lines)
+
+
 def save_type(path: str, n_structures: int, grid_width: float = 20.0, max_residue: int = 50000, nbin_angle: int = 0, nbin_dist: int = 0,
               input_format: str = "PDB", hash_type: str = "PDBTrRosetta", multiple_bins=None, foldcomp_db=None):
     """IndexConfig::to_toml (cli/config.rs:66-87): keys in alphabetical order (toml's table is a BTreeMap)"""

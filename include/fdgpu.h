@@ -504,6 +504,13 @@ int fdgpu_merge_subindices(uint64_t n_parts, const uint8_t *const *values, const
  * (indextable.rs:171-202 appends ids in ascending order).  At most 64 parts per call; the parts stay valid. */
 int fdgpu_index_merge(fdgpu_ctx *ctx, const fdgpu_index *const *parts, uint64_t n_parts, fdgpu_index **out);
 
+/* Drop structures from a resident index.  keep[s] != 0 keeps structure first_id + s (n_keep == fdgpu_index_num_structures(ix)).
+ * Kept structures are renumbered densely from first_id in their old order; lists that lose every id are dropped with their hash.
+ * The result is byte-identical to fdgpu_index_build over the kept structures with the same first_id, carries per-list last ids
+ * (so fdgpu_index_merge needs no extra decode pass), and leaves `ix` valid.  FDGPU_EINVAL if nothing is kept or n_keep mismatches.
+ * Appending is fdgpu_index_build of the new structures at first_id + (kept count) and fdgpu_index_merge of the two. */
+int fdgpu_index_remove(fdgpu_ctx *ctx, const fdgpu_index *ix, const uint8_t *keep, uint64_t n_keep, fdgpu_index **out);
+
 /* `analyze -p`: right-tail hypergeometric test of every encoding (src/controller/summary.rs:543-628, get_enriched_hashes /
  * hypergeometric_test with the reference's log-factorial): p_value[k] = P(X >= query_count[k]) for a sample of total_query draws from a
  * population of total_bg + total_query holding bg_count[k] + query_count[k] successes.  Host threads; no device needed. */
