@@ -641,16 +641,9 @@ extern "C" int fdgpu_comm_single_index(fdgpu_ctx *c, fdgpu_comm *m, const fdgpu_
     // 4. the pieces this rank receives: piece r = rank r's slice of this rank's hash range, with rank r's id range
     for (int r = 0; r < W; ++r) {
         const uint64_t *mr = &all_meta[mw * r + 4 * me];
-        fdgpu_index *g = new (std::nothrow) fdgpu_index();
-        if (!g) { drop(); return comm_broken(c, m, "single index: out of memory"); }
-        got[r] = g;
-        g->ctx = c; g->n_hashes = mr[0]; g->value_len = mr[1]; g->n_postings = mr[2]; g->first_id = all_meta[mw * r + 4 * W]; g->n_structures = all_meta[mw * r + 4 * W + 1];
-        hipError_t e;
-        g->hashes = (uint32_t *)c->pool_alloc(std::max<uint64_t>(g->n_hashes, 1) * 4, &e); g->cap_hashes = c->last_cap;
-        if (e == hipSuccess) { g->offsets = (uint64_t *)c->pool_alloc((g->n_hashes + 1) * 8, &e); g->cap_offsets = c->last_cap; }
-        if (e == hipSuccess) { g->value = (uint8_t *)c->pool_alloc(g->value_len + 16, &e); g->cap_value = c->last_cap; }
-        if (e == hipSuccess && mr[3]) { g->last_ids = (uint32_t *)c->pool_alloc(std::max<uint64_t>(g->n_hashes, 1) * 4, &e); g->cap_last = c->last_cap; }
-        if (e != hipSuccess) { drop(); return comm_broken(c, m, std::string("single index: ") + hipGetErrorString(e)); }
+        if (fd_index_new(c, true, mr[0], mr[1], mr[3] != 0, &got[r])) { drop(); return comm_broken(c, m, "single index: " + c->err); }
+        fdgpu_index *g = got[r];
+        g->n_postings = mr[2]; g->first_id = all_meta[mw * r + 4 * W]; g->n_structures = all_meta[mw * r + 4 * W + 1];
     }
     ncclResult_t nr = rccl().GroupStart();
     for (int r = 0; r < W && nr == ncclSuccess; ++r) {

@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 #include "fdgpu_internal.h"
+#include "fd_postings.h"
 #include <chrono>
 
 #define HIPCHK(ctx, expr)                                                                                   \
@@ -1199,11 +1200,6 @@ static inline uint64_t fd_decode_last(const uint8_t *b, uint64_t n, uint64_t *fi
         prev = cur; acc = 0; shift = 0;
     }
     return cur;
-}
-static inline unsigned fd_put_varint(uint64_t v, uint8_t *out) {
-    unsigned n = 0;
-    do { uint8_t byte = v & 0x7f; v >>= 7; out[n++] = byte | (v ? 0x80 : 0); } while (v);
-    return n;
 }
 
 extern "C" int fdgpu_merge_subindices(uint64_t n_parts, const uint8_t *const *values, const uint32_t *const *hashes,

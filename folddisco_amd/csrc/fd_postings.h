@@ -1,0 +1,62 @@
+// fd_postings.h — the posting-list byte format, stated once for the encoder (k_index.hip), the device merge (k_merge.hip), the removal
+// (k_prune.hip) and the host merge (fdgpu_merge_subindices).
+//
+// A posting list is the ascending ids of the structures that hold one hash, as LEB128 varints (7-bit groups, least significant first; bit 7
+// set = another byte follows; 0 is one 0x00 byte; a u32 takes at most five bytes; codec of indextable.rs:93-99, 397-418).  The first varint
+// of a list is the absolute id, every later one the delta from the id before it.  An index stores its lists back to back in one value array
+// (offsets[k] = first byte of list k) followed by FD_VALUE_SLACK readable bytes, so that the 8-byte window of fd_first_varint at the start of
+// any list, the last one included, stays inside the allocation.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define FD_VALUE_SLACK 16      // bytes behind an index's value array: fd_first_varint reads 8 bytes at the start of a list of any length
+
+// bytes of the varint of v: 1 + ilog2(v) / 7, 1 for 0
+__host__ __device__ __forceinline__ uint32_t fd_varint_len(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return v == 0 ? 1u : 1u + (31u - (uint32_t)__clz(v)) / 7u;      // __clz, not __builtin_clz: the encoder's code is smaller with it
+#else
+    return v == 0 ? 1u : 1u + (31u - (uint32_t)__builtin_clz(v)) / 7u;
+#endif
+}
+
+// value and byte length of the varint at the low end of an 8-byte window
+__device__ __forceinline__ uint32_t fd_varint_at(unsigned long long w, uint32_t *nf) {
+    const unsigned long long stop = ~w & 0x8080808080ull;            // terminator bits of the first five bytes
+    const uint32_t n = (uint32_t)__ffsll((long long)stop) >> 3;      // 1-based byte index of the first terminator
+    *nf = n;
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 5; ++k) if (k < n) v |= (uint32_t)((w >> (8 * k)) & 0x7full) << (7 * k);
+    return v;
+}
+// first varint of a list: value and byte length (reads 8 bytes at p: FD_VALUE_SLACK)
+__device__ __forceinline__ uint32_t fd_first_varint(const uint8_t *__restrict__ p, uint32_t *nf) {
+    unsigned long long w;
+    __builtin_memcpy(&w, p, 8);
+    return fd_varint_at(w, nf);
+}
+
+// A list moved to a new place with a new head: lane sub (0..7) of the eight lanes that copy it writes byte sub of the dl-byte varint of head
+// (dl = 0: the head moves with the bytes), then the n bytes at sp follow behind the head, 16 bytes per lane and step (unaligned 16-byte global
+// accesses are native on gfx950); the lane that reaches the ragged tail (< 16 bytes) copies it byte by byte.
+typedef unsigned int fd_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void fd_list_copy(uint8_t *__restrict__ d, uint32_t head, uint32_t dl, const uint8_t *__restrict__ sp, uint64_t n, uint32_t sub) {
+    if (sub < dl) d[sub] = (uint8_t)(((head >> (7u * sub)) & 0x7fu) | (sub + 1u < dl ? 0x80u : 0u));
+    d += dl;
+    uint64_t o = (uint64_t)sub * 16u;
+    for (; o + 16 <= n; o += 128) {
+        fd_u32x4 v;
+        __builtin_memcpy(&v, sp + o, 16);
+        __builtin_memcpy(d + o, &v, 16);
+    }
+    if (o < n) for (uint64_t z = o; z < n; ++z) d[z] = sp[z];
+}
+
+// host writer: the varint of v at out, returns its byte length
+static inline unsigned fd_put_varint(uint64_t v, uint8_t *out) {
+    unsigned n = 0;
+    do { uint8_t byte = v & 0x7f; v >>= 7; out[n++] = byte | (v ? 0x80 : 0); } while (v);
+    return n;
+}

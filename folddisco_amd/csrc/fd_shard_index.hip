@@ -46,14 +46,6 @@ __global__ void k_si_rebase(const uint64_t *__restrict__ src, uint64_t n, uint64
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) dst[k] = src[k] - base;
 }
-__global__ __launch_bounds__(256) void k_si_count_postings(const uint8_t *__restrict__ value, uint64_t n, unsigned long long *__restrict__ out) {
-    unsigned long long acc = 0;
-    for (uint64_t p = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16; p < n; p += (uint64_t)gridDim.x * 256 * 16)
-        for (uint64_t k = p; k < n && k < p + 16; ++k) acc += !(value[k] & 0x80u);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out, acc);
-}
-
 extern "C" int fdgpu_index_range_bounds(fdgpu_ctx *c, const fdgpu_index *ix, uint32_t n_ranges, uint32_t *bounds) { FD_LOCK(c);
     if (!c || !ix || !n_ranges || (n_ranges > 1 && !bounds)) return FDGPU_EINVAL;
     if (n_ranges == 1) return FDGPU_OK;
@@ -80,15 +72,11 @@ extern "C" int fdgpu_index_slice(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t h
         HIPCHK(c, hipStreamSynchronize(st));
     }
     const uint64_t i0 = f[0], i1 = f[1], b0 = f[2], b1 = f[3], H = i1 - i0, V = b1 - b0;
-    fdgpu_index *s = new (std::nothrow) fdgpu_index();
-    if (!s) return FDGPU_ENOMEM;
-    s->ctx = c; s->n_hashes = H; s->value_len = V; s->n_structures = ix->n_structures; s->first_id = ix->first_id;
-    hipError_t e;
-    s->hashes = (uint32_t *)c->pool_alloc(std::max<uint64_t>(H, 1) * 4, &e); s->cap_hashes = c->last_cap;
-    if (e == hipSuccess) { s->offsets = (uint64_t *)c->pool_alloc((H + 1) * 8, &e); s->cap_offsets = c->last_cap; }
-    if (e == hipSuccess) { s->value = (uint8_t *)c->pool_alloc(V + 16, &e); s->cap_value = c->last_cap; }
-    if (e == hipSuccess && ix->last_ids) { s->last_ids = (uint32_t *)c->pool_alloc(std::max<uint64_t>(H, 1) * 4, &e); s->cap_last = c->last_cap; }
-    if (e == hipSuccess && H) e = hipMemcpyAsync(s->hashes, ix->hashes + i0, H * 4, hipMemcpyDeviceToDevice, st);
+    fdgpu_index *s = nullptr;
+    if (int rc = fd_index_new(c, true, H, V, ix->last_ids != nullptr, &s)) return rc;
+    s->n_structures = ix->n_structures; s->first_id = ix->first_id;
+    hipError_t e = hipSuccess;
+    if (H) e = hipMemcpyAsync(s->hashes, ix->hashes + i0, H * 4, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && H && s->last_ids) e = hipMemcpyAsync(s->last_ids, ix->last_ids + i0, H * 4, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && V) e = hipMemcpyAsync(s->value, ix->value + b0, V, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) {
@@ -96,15 +84,8 @@ extern "C" int fdgpu_index_slice(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t h
         else e = hipMemsetAsync(s->offsets, 0, 8, st);
         if (e == hipSuccess) e = hipGetLastError();
     }
-    unsigned long long np = 0;
-    if (e == hipSuccess && V) {
-        e = hipMemsetAsync(c->ws[WS_TOTAL].p, 0, 8, st);
-        if (e == hipSuccess) { hipLaunchKernelGGL(k_si_count_postings, dim3(2048), dim3(256), 0, st, s->value, V, c->ws[WS_TOTAL].as<unsigned long long>()); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipMemcpyAsync(&np, c->ws[WS_TOTAL].p, 8, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = fd_count_postings(c, s->value, V, &s->n_postings);
     if (e != hipSuccess) { c->err = std::string("index slice: ") + hipGetErrorString(e); fdgpu_index_destroy(s); return FDGPU_EHIP; }
-    s->n_postings = np;
     *out = s;
     return FDGPU_OK;
 }

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "fd_api_common.h"
+#include "fd_postings.h"
 
 // ---- small kernels used only here ------------------------------------------------------------------
 __global__ void k_uniq_flags(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ ids, uint64_t n, uint8_t *__restrict__ flags) {
@@ -50,7 +51,19 @@ __global__ __launch_bounds__(256) void k_count_postings(const uint8_t *__restric
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
     if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out, acc);
 }
-
+hipError_t fd_count_postings(fdgpu_ctx *c, const uint8_t *value, uint64_t n, uint64_t *out) {
+    unsigned long long np = 0;
+    hipError_t e = hipSuccess;
+    if (n) {
+        e = c->ws[WS_TOTAL].ensure(64);
+        if (e == hipSuccess) e = hipMemsetAsync(c->ws[WS_TOTAL].p, 0, 8, c->stream);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_count_postings, dim3(2048), dim3(256), 0, c->stream, value, n, c->ws[WS_TOTAL].as<unsigned long long>()); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipMemcpyAsync(&np, c->ws[WS_TOTAL].p, 8, hipMemcpyDeviceToHost, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    *out = np;
+    return e;
+}
 
 // ---- context ------------------------------------------------------------------------------------------------
 extern "C" const char *fdgpu_version(void) { return "folddisco_amd 0.1 (gfx950)"; }
@@ -616,13 +629,37 @@ extern "C" int fdgpu_hash_batch_rows(fdgpu_ctx *c, const fdgpu_batch *b, const f
 }
 
 // ---- S2 ---------------------------------------------------------------------------------------------------------------
+// An index's blocks come from the pool of the context that owns it (steady-state builds then call neither hipMalloc nor hipFree, which would
+// serialise the stream), or from hipMalloc for an index without one (fdgpu_index_load); fdgpu_index_destroy releases them the same way.
+hipError_t fd_index_block(fdgpu_ctx *pool, size_t bytes, void **p, size_t *cap) {
+    if (!pool) return hipMalloc(p, bytes);
+    hipError_t e;
+    *p = pool->pool_alloc(bytes, &e);
+    *cap = pool->last_cap;
+    return e;
+}
+int fd_index_new(fdgpu_ctx *c, bool pooled, uint64_t H, uint64_t value_len, bool with_last, fdgpu_index **out) {
+    *out = nullptr;
+    fdgpu_index *ix = new (std::nothrow) fdgpu_index();
+    if (!ix) FAIL(c, FDGPU_ENOMEM, "index alloc: out of memory");
+    ix->ctx = pooled ? c : nullptr; ix->n_hashes = H;
+    hipError_t e = hipSuccess;
+    if (value_len != FD_VALUE_LATER) { ix->value_len = value_len; e = fd_index_block(ix->ctx, value_len + FD_VALUE_SLACK, (void **)&ix->value, &ix->cap_value); }
+    if (e == hipSuccess) e = fd_index_block(ix->ctx, std::max<uint64_t>(H, 1) * 4, (void **)&ix->hashes, &ix->cap_hashes);
+    if (e == hipSuccess) e = fd_index_block(ix->ctx, (H + 1) * 8, (void **)&ix->offsets, &ix->cap_offsets);
+    if (e == hipSuccess && with_last) e = fd_index_block(ix->ctx, std::max<uint64_t>(H, 1) * 4, (void **)&ix->last_ids, &ix->cap_last);
+    if (e != hipSuccess) { c->err = std::string("index alloc: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
+    *out = ix;
+    return FDGPU_OK;
+}
 extern "C" void fdgpu_index_destroy(fdgpu_index *ix) {
     if (!ix) return;
     FD_LOCK(ix->ctx);     // the blocks go back to the context's pool
     if (ix->ctx) {
         ix->ctx->pool_free(ix->hashes, ix->cap_hashes); ix->ctx->pool_free(ix->offsets, ix->cap_offsets); ix->ctx->pool_free(ix->value, ix->cap_value);
-        ix->ctx->pool_free(ix->last_ids, ix->cap_last);
-    } else { (void)hipFree(ix->hashes); (void)hipFree(ix->offsets); (void)hipFree(ix->value); (void)hipFree(ix->last_ids); }
+    } else { (void)hipFree(ix->hashes); (void)hipFree(ix->offsets); (void)hipFree(ix->value); }
+    if (ix->ctx && ix->cap_last) ix->ctx->pool_free(ix->last_ids, ix->cap_last);
+    else (void)hipFree(ix->last_ids);      // no context, or derived later by fd_index_last_ids
     if (ix->penalty) (void)hipFree(ix->penalty);
     if (ix->lens) (void)hipFree(ix->lens);
     if (ix->ck_meta) (void)hipFree(ix->ck_meta);
@@ -783,25 +820,15 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
     HIPCHK(c, hipStreamSynchronize(st));
     if (tot[4]) FAIL(c, FDGPU_ERANGE, "index build: one (residue-pair bucket, key digit) group holds 2^32 keys or more; build the shard in several calls and merge");
     if (el6 && tot[3]) return FDGPU_RETRY_WIDE;
-    fdgpu_index *ix = new (std::nothrow) fdgpu_index();
-    if (!ix) return FDGPU_ENOMEM;
-    ix->ctx = c; ix->value_len = tot[0]; ix->n_hashes = tot[1]; ix->n_postings = tot[2]; ix->n_structures = S; ix->first_id = first_id;
-    hipError_t e;
-    ix->value = (uint8_t *)c->pool_alloc(ix->value_len + 16, &e); ix->cap_value = c->last_cap;      // + 16: the merge reads 8 bytes at a list's start (mg_first_varint)
-    if (e == hipSuccess) { ix->hashes = (uint32_t *)c->pool_alloc(std::max<uint64_t>(ix->n_hashes, 1) * 4, &e); ix->cap_hashes = c->last_cap; }
-    if (e == hipSuccess) { ix->offsets = (uint64_t *)c->pool_alloc((ix->n_hashes + 1) * 8, &e); ix->cap_offsets = c->last_cap; }
-    if (e == hipSuccess) { ix->last_ids = (uint32_t *)c->pool_alloc(std::max<uint64_t>(ix->n_hashes, 1) * 4, &e); ix->cap_last = c->last_cap; }
-    if (e != hipSuccess) {
-        c->err = std::string("index alloc: ") + hipGetErrorString(e);
-        fdgpu_index_destroy(ix);
-        return FDGPU_EHIP;
-    }
+    fdgpu_index *ix = nullptr;
+    if ((rc = fd_index_new(c, true, tot[1], tot[0], true, &ix))) return rc;
+    ix->n_postings = tot[2]; ix->n_structures = S; ix->first_id = first_id;
     {
         StageTimer t(c, "encode_write", P * (el6 ? 6 : 8) + ix->value_len + ix->n_hashes * 12);
         fd_launch_enc_write(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_TILE_HO].as<uint64_t>(), ix->value, ix->hashes, ix->offsets,
                             ix->last_ids, c->ws[WS_MISC3].as<uint64_t>(), ix->n_hashes, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
     }
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { c->err = std::string("encode launch: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
     *out = ix;
     return FDGPU_OK;
@@ -871,15 +898,13 @@ extern "C" int fdgpu_index_load(fdgpu_ctx *c, const uint32_t *hashes, const uint
                                 uint64_t vlen, uint64_t n_structures, fdgpu_index **out) { FD_LOCK(c);
     if (!c || !out || (H && (!hashes || !offsets)) || (vlen && !value)) return FDGPU_EINVAL;
     *out = nullptr;
-    fdgpu_index *ix = new (std::nothrow) fdgpu_index();
-    if (!ix) return FDGPU_ENOMEM;
-    ix->ctx = nullptr; ix->n_hashes = H; ix->value_len = vlen; ix->n_structures = n_structures;
-    hipError_t e;
+    fdgpu_index *ix = nullptr;
+    int rc = fd_index_new(c, false, H, vlen, false, &ix);
+    if (rc) return rc;
+    ix->n_structures = n_structures;
+    hipError_t e = hipSuccess;
     uint64_t zero = 0;
-    if ((e = hipMalloc((void **)&ix->value, std::max<uint64_t>(vlen, 4) + 16)) != hipSuccess ||
-        (e = hipMalloc((void **)&ix->hashes, std::max<uint64_t>(H, 1) * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&ix->offsets, (H + 1) * 8)) != hipSuccess ||
-        (vlen && (e = hipMemcpyAsync(ix->value, value, vlen, hipMemcpyHostToDevice, c->stream)) != hipSuccess) ||
+    if ((vlen && (e = hipMemcpyAsync(ix->value, value, vlen, hipMemcpyHostToDevice, c->stream)) != hipSuccess) ||
         (H && (e = hipMemcpyAsync(ix->hashes, hashes, H * 4, hipMemcpyHostToDevice, c->stream)) != hipSuccess) ||
         (e = hipMemcpyAsync(ix->offsets, H ? offsets : &zero, (H + 1) * 8, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
@@ -887,133 +912,12 @@ extern "C" int fdgpu_index_load(fdgpu_ctx *c, const uint32_t *hashes, const uint
         fdgpu_index_destroy(ix);
         return FDGPU_EHIP;
     }
-    // postings = bytes without the continuation bit
-    ix->n_postings = 0;
-    if (vlen) {
-        unsigned long long np = 0;
-        bool counted = false;
-        if (c->ws[WS_TOTAL].ensure(64) == hipSuccess && hipMemsetAsync(c->ws[WS_TOTAL].p, 0, 8, c->stream) == hipSuccess) {
-            hipLaunchKernelGGL(k_count_postings, dim3(2048), dim3(256), 0, c->stream, ix->value, vlen, c->ws[WS_TOTAL].as<unsigned long long>());
-            if (hipGetLastError() == hipSuccess && hipMemcpyAsync(&np, c->ws[WS_TOTAL].p, 8, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
-                hipStreamSynchronize(c->stream) == hipSuccess) { ix->n_postings = np; counted = true; }
-        }
-        if (!counted) {       // nothing stays latched for the next call; the index would report 0 postings: refuse it
-            (void)hipGetLastError();
-            c->err = "index load: counting the postings failed";
-            fdgpu_index_destroy(ix);
-            return FDGPU_EHIP;
-        }
+    if ((e = fd_count_postings(c, ix->value, vlen, &ix->n_postings)) != hipSuccess) {      // an index that would report 0 postings: refuse it
+        (void)hipGetLastError();
+        c->err = std::string("index load: counting the postings: ") + hipGetErrorString(e);
+        fdgpu_index_destroy(ix);
+        return FDGPU_EHIP;
     }
-    *out = ix;
-    return FDGPU_OK;
-}
-
-// ---- device merge of sub-indices (k_merge.hip) ---------------------------------------------------------------------
-struct mg_part_h { const uint32_t *hashes; const uint64_t *offsets; const uint8_t *value; const uint32_t *last_ids; uint64_t H; };
-void fd_mg_last_ids(const uint64_t *offsets, const uint8_t *value, uint64_t H, uint32_t *last_ids, hipStream_t st);
-void fd_mg_bitmap_set(const uint32_t *hashes, uint64_t n, uint32_t *bitmap, hipStream_t st);
-void fd_mg_popc(const uint32_t *bitmap, uint64_t n_words, uint32_t *cnt, hipStream_t st);
-void fd_mg_expand(const uint32_t *bitmap, const uint64_t *prefix, uint64_t n_words, uint32_t *out, hipStream_t st);
-void fd_mg_pos_fill(const uint32_t *hashes, uint64_t n, const uint32_t *bitmap, const uint64_t *prefix, uint32_t *pos, uint32_t part, uint32_t n_parts,
-                    hipStream_t st);
-void fd_mg_sizes(const void *parts, uint32_t n_parts, const uint32_t *pos, uint64_t n_slots, uint32_t *sizes, uint32_t *out_last, void *plan, uint32_t *plan_dst,
-                 uint32_t *err_flag, hipStream_t st);
-void fd_mg_copy(const void *parts, uint32_t n_parts, const void *plan, const uint32_t *plan_dst, uint64_t n_slots, const uint64_t *out_off, uint8_t *out_value,
-                hipStream_t st);
-
-extern "C" int fdgpu_index_merge(fdgpu_ctx *c, const fdgpu_index *const *parts, uint64_t n_parts, fdgpu_index **out) { FD_LOCK(c);
-    if (!c || !out || !n_parts || !parts) return FDGPU_EINVAL;
-    *out = nullptr;
-    if (n_parts > 64) FAIL(c, FDGPU_ERANGE, "index merge: at most 64 parts per call (merge in rounds)");
-    reset_timings(c);
-    hipStream_t st = c->stream;
-    uint64_t n_struct = 0, n_post = 0, sum_h = 0, sum_v = 0;
-    std::vector<mg_part_h> ph(n_parts);
-    for (uint64_t k = 0; k < n_parts; ++k) {
-        const fdgpu_index *p = parts[k];
-        if (!p) return FDGPU_EINVAL;
-        if (k && p->first_id != parts[k - 1]->first_id + parts[k - 1]->n_structures)
-            FAIL(c, FDGPU_EINVAL, "index merge: parts must cover consecutive structure-id ranges in the order given");
-        if (!p->last_ids && p->n_hashes) {     // a loaded index: last id of every list by one decode pass, kept with the index
-            fdgpu_index *mp = const_cast<fdgpu_index *>(p);
-            hipError_t le = hipSuccess;      // the block is released the way fdgpu_index_destroy releases the part's other blocks: pool for a built index, hipFree for a loaded one
-            if (mp->ctx) { mp->last_ids = (uint32_t *)mp->ctx->pool_alloc(p->n_hashes * 4, &le); mp->cap_last = mp->ctx->last_cap; }
-            else le = hipMalloc((void **)&mp->last_ids, p->n_hashes * 4);
-            if (le != hipSuccess) { mp->last_ids = nullptr; c->err = std::string("index merge: ") + hipGetErrorString(le); return FDGPU_EHIP; }
-            fd_mg_last_ids(p->offsets, p->value, p->n_hashes, mp->last_ids, st);
-        }
-        ph[k] = {p->hashes, p->offsets, p->value, p->last_ids, p->n_hashes};
-        n_struct += p->n_structures; n_post += p->n_postings; sum_h += p->n_hashes; sum_v += p->value_len;
-    }
-    // hash space: 2^30 unless a part holds an overflowed hash (unmasked OR of the fields)
-    uint32_t max_hash = 0;
-    for (uint64_t k = 0; k < n_parts; ++k)
-        if (parts[k]->n_hashes) {
-            uint32_t h = 0;
-            HIPCHK(c, hipMemcpyAsync(&h, parts[k]->hashes + parts[k]->n_hashes - 1, 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            max_hash = std::max(max_hash, h);
-        }
-    const uint64_t n_words = max_hash < (1u << 30) ? (1ull << 25) : (1ull << 27);
-    HIPCHK(c, c->ws[WS_KEYS_A].ensure(n_words * 4));
-    HIPCHK(c, c->ws[WS_KEYS_B].ensure(n_words * 4));
-    HIPCHK(c, c->ws[WS_IDS_A].ensure((n_words + 2) * 8));
-    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(n_words, sum_h)) * 8 + 64));
-    HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-    HIPCHK(c, c->ws[WS_MISC4].ensure(n_parts * sizeof(mg_part_h)));
-    uint32_t *bitmap = c->ws[WS_KEYS_A].as<uint32_t>(), *cnt = c->ws[WS_KEYS_B].as<uint32_t>();
-    uint64_t *prefix = c->ws[WS_IDS_A].as<uint64_t>();
-    uint64_t Ht = 0;
-    {
-        StageTimer t(c, "merge_union", sum_h * 4 + n_words * 24);
-        HIPCHK(c, hipMemsetAsync(bitmap, 0, n_words * 4, st));
-        HIPCHK(c, hipMemcpyAsync(c->ws[WS_MISC4].p, ph.data(), n_parts * sizeof(mg_part_h), hipMemcpyHostToDevice, st));
-        for (uint64_t k = 0; k < n_parts; ++k) fd_mg_bitmap_set(ph[k].hashes, ph[k].H, bitmap, st);
-        fd_mg_popc(bitmap, n_words, cnt, st);
-        fd_exclusive_scan<uint32_t>(cnt, n_words, prefix, c->ws[WS_SCANTMP].as<uint64_t>(), c->ws[WS_TOTAL].as<uint64_t>(), st);
-    }
-    HIPCHK(c, hipGetLastError());
-    int rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &Ht);
-    if (rc) return rc;
-    fdgpu_index *ix = new (std::nothrow) fdgpu_index();
-    if (!ix) return FDGPU_ENOMEM;
-    ix->ctx = c; ix->n_hashes = Ht; ix->n_postings = n_post; ix->n_structures = n_struct; ix->first_id = parts[0]->first_id;
-    hipError_t e;
-    ix->hashes = (uint32_t *)c->pool_alloc(std::max<uint64_t>(Ht, 1) * 4, &e); ix->cap_hashes = c->last_cap;
-    if (e == hipSuccess) { ix->offsets = (uint64_t *)c->pool_alloc((Ht + 1) * 8, &e); ix->cap_offsets = c->last_cap; }
-    if (e == hipSuccess) { ix->last_ids = (uint32_t *)c->pool_alloc(std::max<uint64_t>(Ht, 1) * 4, &e); ix->cap_last = c->last_cap; }
-    if (e == hipSuccess) e = c->ws[WS_IDS_B].ensure(std::max<uint64_t>(Ht, 1) * n_parts * 4);
-    if (e == hipSuccess) e = c->ws[WS_MISC0].ensure(std::max<uint64_t>(Ht, 1) * 4);
-    if (e == hipSuccess) e = c->ws[WS_FRAMES].ensure(std::max<uint64_t>(Ht, 1) * n_parts * 16);     // copy plan: 16 + 4 bytes per (slot, part)
-    if (e == hipSuccess) e = c->ws[WS_MISC1].ensure(std::max<uint64_t>(Ht, 1) * n_parts * 4);
-    if (e != hipSuccess) { c->err = std::string("index merge alloc: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
-    uint32_t *pos = c->ws[WS_IDS_B].as<uint32_t>(), *sizes = c->ws[WS_MISC0].as<uint32_t>();
-    {
-        StageTimer t(c, "merge_sizes", sum_v + sum_h * 20 + Ht * n_parts * 8 + Ht * 16);
-        fd_mg_expand(bitmap, prefix, n_words, ix->hashes, st);
-        (void)hipMemsetAsync(pos, 0xff, std::max<uint64_t>(Ht, 1) * n_parts * 4, st);
-        for (uint64_t k = 0; k < n_parts; ++k) fd_mg_pos_fill(ph[k].hashes, ph[k].H, bitmap, prefix, pos, (uint32_t)k, (uint32_t)n_parts, st);
-        (void)hipMemsetAsync(c->ws[WS_TOTAL].as<uint32_t>() + 4, 0, 4, st);      // "a merged list does not fit 32 bits" flag, behind the scan total
-        fd_mg_sizes(c->ws[WS_MISC4].p, (uint32_t)n_parts, pos, Ht, sizes, ix->last_ids, c->ws[WS_FRAMES].p, c->ws[WS_MISC1].as<uint32_t>(),
-                    c->ws[WS_TOTAL].as<uint32_t>() + 4, st);
-        fd_exclusive_scan<uint32_t>(sizes, Ht, ix->offsets, c->ws[WS_SCANTMP].as<uint64_t>(), c->ws[WS_TOTAL].as<uint64_t>(), st);
-    }
-    e = hipGetLastError();
-    uint64_t vlen = 0;
-    if (e == hipSuccess) { rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &vlen); if (rc) { fdgpu_index_destroy(ix); return rc; } }
-    if (e == hipSuccess) {
-        uint32_t too_long = 0;
-        e = hipMemcpy(&too_long, c->ws[WS_TOTAL].as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && too_long) { fdgpu_index_destroy(ix); FAIL(c, FDGPU_ERANGE, "index merge: a merged posting list reaches 4 GiB"); }
-    }
-    if (e == hipSuccess) { ix->value_len = vlen; ix->value = (uint8_t *)c->pool_alloc(vlen + 16, &e); ix->cap_value = c->last_cap; }
-    if (e != hipSuccess) { c->err = std::string("index merge: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
-    {
-        StageTimer t(c, "merge_copy", sum_v + vlen + Ht * n_parts * 4);
-        fd_mg_copy(c->ws[WS_MISC4].p, (uint32_t)n_parts, c->ws[WS_FRAMES].p, c->ws[WS_MISC1].as<uint32_t>(), Ht, ix->offsets, ix->value, st);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) { c->err = std::string("index merge copy: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
     *out = ix;
     return FDGPU_OK;
 }

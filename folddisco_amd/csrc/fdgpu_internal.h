@@ -222,8 +222,10 @@ struct fdgpu_index {
     uint32_t *hashes = nullptr;   // device [H]
     uint64_t *offsets = nullptr;  // device [H+1]
     uint8_t *value = nullptr;     // device [value_len]
-    uint32_t *last_ids = nullptr; // device [H] last structure id of every list (written by the encoder; the device merge re-bases the next
-                                  // part's first delta against it); null for an index that was loaded — computed on demand
+    // device [H] last structure id of every list: the device merge re-bases the next part's first delta against it, the removal tells from it
+    // which lists lose ids.  Written by the encoder, the merge and the removal; an index that was loaded gets it as a derived table on the first
+    // merge or removal (fd_index_last_ids: hipMalloc, lens_mu, cap_last = 0)
+    mutable uint32_t *last_ids = nullptr;
     size_t cap_hashes = 0, cap_offsets = 0, cap_value = 0, cap_last = 0;
     mutable uint32_t *lens = nullptr;   // device [H] posting length of every list, made on the first length request (fd_posting_lengths_dev)
     mutable std::mutex lens_mu;         // several contexts (streams) may share one index: the first one fills lens, complete before it is published
@@ -237,6 +239,16 @@ struct fdgpu_index {
     mutable bool ck_failed = false;                  // the table did not fit for the id range (ck_first, ck_S): the tiled path is off until the range changes or a retry succeeds
     mutable uint32_t ck_fail_skips = 0;
 };
+
+// making an index (fdgpu_api.hip): the object and its hashes / offsets blocks, last_ids if with_last, value_len value bytes + FD_VALUE_SLACK
+// (fd_postings.h) unless value_len is FD_VALUE_LATER (the merge sizes its lists first, then takes the value block with fd_index_block).
+// pooled: the index belongs to c and its blocks come from c's pool; otherwise from hipMalloc (a loaded index).  Nothing is left on failure.
+#define FD_VALUE_LATER (~0ull)
+int fd_index_new(fdgpu_ctx *c, bool pooled, uint64_t H, uint64_t value_len, bool with_last, fdgpu_index **out);
+hipError_t fd_index_block(fdgpu_ctx *pool, size_t bytes, void **p, size_t *cap);      // pool = the index's ctx (null: hipMalloc)
+int fd_index_last_ids(fdgpu_ctx *c, const fdgpu_index *ix);      // k_merge.hip: ix->last_ids, derived once for a loaded index
+hipError_t fd_count_postings(fdgpu_ctx *c, const uint8_t *value, uint64_t n, uint64_t *out);      // terminators of n value bytes; synchronises
+static inline unsigned fd_grid(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
 
 // batched scoring with the ranked selection left on the device (fdgpu_api.hip; consumed by the sharded query, fd_comm.hip)
 struct fd_cq_dev_out {

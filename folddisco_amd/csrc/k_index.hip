@@ -4,21 +4,16 @@
 // wrapup_offset_and_save_entries / prune_to_sparse of the reference
 // (src/index/indextable.rs:88-105, 204-237, 171-202, 239-295, codec :397-418):
 //   * duplicates (same hash, same id — the reference's per-structure dedup, mod.rs:343-345) drop out,
-//   * first id of a list is absolute, the rest are deltas, each LEB128 (7-bit groups, MSB = continue,
-//     value 0 -> one 0x00 byte),
+//   * first id of a list is absolute, the rest are deltas, each LEB128 (the format of fd_postings.h),
 //   * lists are laid out in ascending hash order; only non-empty hashes are kept (sparse form):
 //     hashes[H], offsets[H+1] with offsets[k] = first byte of list k, offsets[H] = total bytes.
 // Two streaming passes over the sorted pairs (sizes, then write), HBM-bound.
 #include "fd_device.h"
+#include "fd_postings.h"
 
 #define ENC_THREADS 256
 #define ENC_ITEMS 8
 #define ENC_TILE (ENC_THREADS * ENC_ITEMS)
-
-__device__ __forceinline__ uint32_t varint_len(uint32_t v) {
-    // 1 + ilog2(v)/7 for v > 0, 1 for v == 0 (indextable.rs:93-99)
-    return v == 0 ? 1u : 1u + (31u - (uint32_t)__clz(v)) / 7u;
-}
 
 struct enc_item { uint32_t len; uint32_t head; uint32_t delta; uint32_t hash; };
 
@@ -124,7 +119,7 @@ __device__ __forceinline__ void enc_load_classify(const uint32_t *__restrict__ k
         it[j].hash = h;
         it[j].head = (in && head) ? 1u : 0u;
         it[j].delta = head ? id : id - pid;
-        it[j].len = (!in || dup) ? 0u : varint_len(it[j].delta);
+        it[j].len = (!in || dup) ? 0u : fd_varint_len(it[j].delta);
         ph = h; pid = id; have_prev = true;
     }
 }

@@ -15,6 +15,8 @@
 //   copy                             one wavefront per merged slot, eight lanes per part, 16 bytes per lane and step
 // HBM-bound byte work: one read + one write of the value bytes.
 #include "fdgpu_internal.h"
+#include "fd_api_common.h"
+#include "fd_postings.h"
 
 #define MG_NONE 0xffffffffu
 #define MG_MAX_PARTS 64
@@ -55,7 +57,6 @@ __device__ __forceinline__ uint32_t mg_wave_sum(uint32_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, FD_WAVE);
     return v;
 }
-__device__ __forceinline__ uint32_t mg_varint_len(uint32_t v) { return v == 0 ? 1u : 1u + (31u - (uint32_t)__clz(v)) / 7u; }
 
 // last structure id of every list of an index that carries no last_ids (fdgpu_index_load): one wavefront per list, the last id is
 // the sum over the list's bytes of (byte & 0x7f) << 7 * (position inside its varint)
@@ -77,19 +78,6 @@ __global__ __launch_bounds__(256) void k_mg_last_ids(const uint64_t *__restrict_
     }
     acc = mg_wave_sum(acc);
     if (lane == 0) last_ids[t] = acc;
-}
-
-// first varint of a byte string: value and length (<= 5 bytes; the 8 bytes behind p are readable: the value buffers carry slack)
-__device__ __forceinline__ uint32_t mg_first_varint(const uint8_t *__restrict__ p, uint32_t *nf) {
-    unsigned long long w;
-    __builtin_memcpy(&w, p, 8);
-    const unsigned long long stop = ~w & 0x8080808080ull;            // terminator bits of the first five bytes
-    const uint32_t n = ((uint32_t)__ffsll((long long)stop) >> 3);     // 1-based byte index of the first terminator
-    *nf = n;
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 5; ++k) if (k < n) v |= (uint32_t)((w >> (8 * k)) & 0x7full) << (7 * k);
-    return v;
 }
 
 // sizes: thread = merged slot.  size = sum over the parts holding the hash of (bytes of the part's list), the first varint of every
@@ -115,9 +103,9 @@ __global__ __launch_bounds__(256) void k_mg_sizes(const mg_part *__restrict__ pa
             uint32_t len = (uint32_t)(b1 - b0), nf = 0, dl = 0, delta = 0;
             if (b1 - b0 > 0xffffffffull - total) *err_flag = 1u;      // a merged list of 4 GiB or more does not fit the u32 plan: the call fails (FDGPU_ERANGE)
             if (have_prev) {
-                const uint32_t first = mg_first_varint(P.value + b0, &nf);
+                const uint32_t first = fd_first_varint(P.value + b0, &nf);
                 delta = first - prev_last;
-                dl = mg_varint_len(delta);
+                dl = fd_varint_len(delta);
                 len = len - nf + dl;
             }
             const uint64_t src = b0 + nf;
@@ -133,9 +121,8 @@ __global__ __launch_bounds__(256) void k_mg_sizes(const mg_part *__restrict__ pa
     out_last[g] = prev_last;
 }
 
-// copy: eight lanes per (slot, part) piece, 16 bytes per lane and step (unaligned 16-byte global accesses are native on gfx950); the pieces
-// of one slot are adjacent work items, so a merged list still leaves through neighbouring lanes
-typedef unsigned int mg_u32x4 __attribute__((ext_vector_type(4)));
+// copy: eight lanes per (slot, part) piece (fd_list_copy); the pieces of one slot are adjacent work items, so a merged list still leaves through
+// neighbouring lanes
 __global__ __launch_bounds__(256) void k_mg_copy(const mg_part *__restrict__ parts, uint32_t n_parts, const mg_plan *__restrict__ plan,
                                                  const uint32_t *__restrict__ plan_dst, uint64_t n_pieces, const uint64_t *__restrict__ out_off,
                                                  uint8_t *__restrict__ out_value) {
@@ -146,45 +133,111 @@ __global__ __launch_bounds__(256) void k_mg_copy(const mg_part *__restrict__ par
     const uint32_t sub = threadIdx.x & 7u, k = (uint32_t)(G % n_parts);
     const uint64_t slot = G / n_parts;
     const uint32_t dl = (pl.src_hi_dl >> 16) & 7u;
-    uint8_t *d = out_value + out_off[slot] + plan_dst[G];
-    if (sub < dl) d[sub] = (uint8_t)(((pl.delta >> (7u * sub)) & 0x7fu) | (sub + 1u < dl ? 0x80u : 0u));
     const uint8_t *sp = parts[k].value + (((uint64_t)(pl.src_hi_dl & 0xffffu) << 32) | pl.src_lo);
-    d += dl;
-    const uint64_t n = pl.n;
-    uint64_t o = (uint64_t)sub * 16u;
-    for (; o + 16 <= n; o += 128) {
-        mg_u32x4 v;
-        __builtin_memcpy(&v, sp + o, 16);
-        __builtin_memcpy(d + o, &v, 16);
-    }
-    if (o < n) for (uint64_t z = o; z < n; ++z) d[z] = sp[z];     // the lane that owns the ragged tail (< 16 bytes)
+    fd_list_copy(out_value + out_off[slot] + plan_dst[G], pl.delta, dl, sp, pl.n, sub);
 }
 
-// ---- launchers
-void fd_mg_bitmap_set(const uint32_t *hashes, uint64_t n, uint32_t *bitmap, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_mg_bitmap_set, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hashes, n, bitmap);
+// the last id of every list of ix, once: an index that was loaded carries none.  Derived like lens (fd_api_count.hip): made under lens_mu and
+// complete before it is published, because sibling contexts (query lanes) may share the index and read it from their own streams
+int fd_index_last_ids(fdgpu_ctx *c, const fdgpu_index *ix) {
+    std::lock_guard<std::mutex> lk(ix->lens_mu);
+    if (ix->last_ids || !ix->n_hashes) return FDGPU_OK;
+    uint32_t *l = nullptr;
+    HIPCHK(c, hipMalloc((void **)&l, ix->n_hashes * 4));
+    hipLaunchKernelGGL(k_mg_last_ids, dim3(fd_grid(ix->n_hashes, 4)), dim3(256), 0, c->stream, ix->offsets, ix->value, ix->n_hashes, l);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipFree(l); c->err = std::string("last ids of the index: ") + hipGetErrorString(e); return FDGPU_EHIP; }
+    ix->last_ids = l;
+    return FDGPU_OK;
 }
-void fd_mg_popc(const uint32_t *bitmap, uint64_t n_words, uint32_t *cnt, hipStream_t st) {
-    hipLaunchKernelGGL(k_mg_popc, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, bitmap, n_words, cnt);
+
+extern "C" int fdgpu_index_merge(fdgpu_ctx *c, const fdgpu_index *const *parts, uint64_t n_parts, fdgpu_index **out) { FD_LOCK(c);
+    if (!c || !out || !n_parts || !parts) return FDGPU_EINVAL;
+    *out = nullptr;
+    if (n_parts > MG_MAX_PARTS) FAIL(c, FDGPU_ERANGE, "index merge: at most 64 parts per call (merge in rounds)");
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    uint64_t n_struct = 0, n_post = 0, sum_h = 0, sum_v = 0;
+    std::vector<mg_part> ph(n_parts);
+    for (uint64_t k = 0; k < n_parts; ++k) {
+        const fdgpu_index *p = parts[k];
+        if (!p) return FDGPU_EINVAL;
+        if (k && p->first_id != parts[k - 1]->first_id + parts[k - 1]->n_structures)
+            FAIL(c, FDGPU_EINVAL, "index merge: parts must cover consecutive structure-id ranges in the order given");
+        if (int rc = fd_index_last_ids(c, p)) return rc;
+        ph[k] = {p->hashes, p->offsets, p->value, p->last_ids, p->n_hashes};
+        n_struct += p->n_structures; n_post += p->n_postings; sum_h += p->n_hashes; sum_v += p->value_len;
+    }
+    // hash space: 2^30 unless a part holds an overflowed hash (unmasked OR of the fields)
+    uint32_t max_hash = 0;
+    for (uint64_t k = 0; k < n_parts; ++k)
+        if (parts[k]->n_hashes) {
+            uint32_t h = 0;
+            HIPCHK(c, hipMemcpyAsync(&h, parts[k]->hashes + parts[k]->n_hashes - 1, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            max_hash = std::max(max_hash, h);
+        }
+    const uint64_t n_words = max_hash < (1u << 30) ? (1ull << 25) : (1ull << 27);
+    HIPCHK(c, c->ws[WS_KEYS_A].ensure(n_words * 4));
+    HIPCHK(c, c->ws[WS_KEYS_B].ensure(n_words * 4));
+    HIPCHK(c, c->ws[WS_IDS_A].ensure((n_words + 2) * 8));
+    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(n_words, sum_h)) * 8 + 64));
+    HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
+    HIPCHK(c, c->ws[WS_MISC4].ensure(n_parts * sizeof(mg_part)));
+    uint32_t *bitmap = c->ws[WS_KEYS_A].as<uint32_t>(), *cnt = c->ws[WS_KEYS_B].as<uint32_t>();
+    uint64_t *prefix = c->ws[WS_IDS_A].as<uint64_t>();
+    uint64_t Ht = 0;
+    {
+        StageTimer t(c, "merge_union", sum_h * 4 + n_words * 24);
+        HIPCHK(c, hipMemsetAsync(bitmap, 0, n_words * 4, st));
+        HIPCHK(c, hipMemcpyAsync(c->ws[WS_MISC4].p, ph.data(), n_parts * sizeof(mg_part), hipMemcpyHostToDevice, st));
+        for (uint64_t k = 0; k < n_parts; ++k)
+            if (ph[k].H) hipLaunchKernelGGL(k_mg_bitmap_set, dim3(fd_grid(ph[k].H, 256)), dim3(256), 0, st, ph[k].hashes, ph[k].H, bitmap);
+        hipLaunchKernelGGL(k_mg_popc, dim3(fd_grid(n_words, 256)), dim3(256), 0, st, bitmap, n_words, cnt);
+        fd_exclusive_scan<uint32_t>(cnt, n_words, prefix, c->ws[WS_SCANTMP].as<uint64_t>(), c->ws[WS_TOTAL].as<uint64_t>(), st);
+    }
+    HIPCHK(c, hipGetLastError());
+    int rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &Ht);
+    if (rc) return rc;
+    fdgpu_index *ix = nullptr;
+    if ((rc = fd_index_new(c, true, Ht, FD_VALUE_LATER, true, &ix))) return rc;
+    ix->n_postings = n_post; ix->n_structures = n_struct; ix->first_id = parts[0]->first_id;
+    hipError_t e = c->ws[WS_IDS_B].ensure(std::max<uint64_t>(Ht, 1) * n_parts * 4);
+    if (e == hipSuccess) e = c->ws[WS_MISC0].ensure(std::max<uint64_t>(Ht, 1) * 4);
+    if (e == hipSuccess) e = c->ws[WS_FRAMES].ensure(std::max<uint64_t>(Ht, 1) * n_parts * 16);     // copy plan: 16 + 4 bytes per (slot, part)
+    if (e == hipSuccess) e = c->ws[WS_MISC1].ensure(std::max<uint64_t>(Ht, 1) * n_parts * 4);
+    if (e != hipSuccess) { c->err = std::string("index merge alloc: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
+    uint32_t *pos = c->ws[WS_IDS_B].as<uint32_t>(), *sizes = c->ws[WS_MISC0].as<uint32_t>();
+    {
+        StageTimer t(c, "merge_sizes", sum_v + sum_h * 20 + Ht * n_parts * 8 + Ht * 16);
+        hipLaunchKernelGGL(k_mg_expand, dim3(fd_grid(n_words, 256)), dim3(256), 0, st, bitmap, prefix, n_words, ix->hashes);
+        (void)hipMemsetAsync(pos, 0xff, std::max<uint64_t>(Ht, 1) * n_parts * 4, st);
+        for (uint64_t k = 0; k < n_parts; ++k)
+            if (ph[k].H) hipLaunchKernelGGL(k_mg_pos_fill, dim3(fd_grid(ph[k].H, 256)), dim3(256), 0, st, ph[k].hashes, ph[k].H, bitmap, prefix, pos, (uint32_t)k, (uint32_t)n_parts);
+        (void)hipMemsetAsync(c->ws[WS_TOTAL].as<uint32_t>() + 4, 0, 4, st);      // "a merged list does not fit 32 bits" flag, behind the scan total
+        if (Ht) hipLaunchKernelGGL(k_mg_sizes, dim3(fd_grid(Ht, 256)), dim3(256), 0, st, c->ws[WS_MISC4].as<mg_part>(), (uint32_t)n_parts, pos, Ht, sizes,
+                                   ix->last_ids, c->ws[WS_FRAMES].as<mg_plan>(), c->ws[WS_MISC1].as<uint32_t>(), c->ws[WS_TOTAL].as<uint32_t>() + 4);
+        fd_exclusive_scan<uint32_t>(sizes, Ht, ix->offsets, c->ws[WS_SCANTMP].as<uint64_t>(), c->ws[WS_TOTAL].as<uint64_t>(), st);
+    }
+    e = hipGetLastError();
+    uint64_t vlen = 0;
+    if (e == hipSuccess) { rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &vlen); if (rc) { fdgpu_index_destroy(ix); return rc; } }
+    if (e == hipSuccess) {
+        uint32_t too_long = 0;
+        e = hipMemcpy(&too_long, c->ws[WS_TOTAL].as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && too_long) { fdgpu_index_destroy(ix); FAIL(c, FDGPU_ERANGE, "index merge: a merged posting list reaches 4 GiB"); }
+    }
+    if (e == hipSuccess) { ix->value_len = vlen; e = fd_index_block(c, vlen + FD_VALUE_SLACK, (void **)&ix->value, &ix->cap_value); }
+    if (e != hipSuccess) { c->err = std::string("index merge: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
+    {
+        StageTimer t(c, "merge_copy", sum_v + vlen + Ht * n_parts * 4);
+        if (Ht) hipLaunchKernelGGL(k_mg_copy, dim3(fd_grid(Ht * n_parts, 32)), dim3(256), 0, st, c->ws[WS_MISC4].as<mg_part>(), (uint32_t)n_parts,
+                                   c->ws[WS_FRAMES].as<mg_plan>(), c->ws[WS_MISC1].as<uint32_t>(), Ht * n_parts, ix->offsets, ix->value);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) { c->err = std::string("index merge copy: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
+    *out = ix;
+    return FDGPU_OK;
 }
-void fd_mg_expand(const uint32_t *bitmap, const uint64_t *prefix, uint64_t n_words, uint32_t *out, hipStream_t st) {
-    hipLaunchKernelGGL(k_mg_expand, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, bitmap, prefix, n_words, out);
-}
-void fd_mg_pos_fill(const uint32_t *hashes, uint64_t n, const uint32_t *bitmap, const uint64_t *prefix, uint32_t *pos, uint32_t part, uint32_t n_parts,
-                    hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_mg_pos_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hashes, n, bitmap, prefix, pos, part, n_parts);
-}
-void fd_mg_last_ids(const uint64_t *offsets, const uint8_t *value, uint64_t H, uint32_t *last_ids, hipStream_t st) {
-    if (H) hipLaunchKernelGGL(k_mg_last_ids, dim3((unsigned)((H + 3) / 4)), dim3(256), 0, st, offsets, value, H, last_ids);
-}
-void fd_mg_sizes(const void *parts, uint32_t n_parts, const uint32_t *pos, uint64_t n_slots, uint32_t *sizes, uint32_t *out_last, void *plan, uint32_t *plan_dst,
-                 uint32_t *err_flag, hipStream_t st) {
-    if (n_slots) hipLaunchKernelGGL(k_mg_sizes, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, (const mg_part *)parts, n_parts, pos, n_slots, sizes, out_last,
-                                    (mg_plan *)plan, plan_dst, err_flag);
-}
-void fd_mg_copy(const void *parts, uint32_t n_parts, const void *plan, const uint32_t *plan_dst, uint64_t n_slots, const uint64_t *out_off, uint8_t *out_value,
-                hipStream_t st) {
-    const uint64_t n_pieces = n_slots * n_parts;
-    if (n_pieces) hipLaunchKernelGGL(k_mg_copy, dim3((unsigned)((n_pieces + 31) / 32)), dim3(256), 0, st, (const mg_part *)parts, n_parts, (const mg_plan *)plan, plan_dst,
-                                     n_pieces, out_off, out_value);
-}
+

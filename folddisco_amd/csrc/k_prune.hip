@@ -21,29 +21,12 @@
 // HBM-bound byte work: the value bytes are read twice (sizes, write) and written once; 8 bytes per hash of tables.
 #include "fdgpu_internal.h"
 #include "fd_api_common.h"
+#include "fd_postings.h"
 
 #define PR_LONG_BYTES 16384u      // re-encoded lists at least this long are decoded first
 #define PR_MODE_COPY 0u
 #define PR_MODE_REBASE 1u
 #define PR_MODE_RECODE 2u
-
-__device__ __forceinline__ uint32_t pr_varint_len(uint32_t v) { return v == 0 ? 1u : 1u + (31u - (uint32_t)__clz(v)) / 7u; }
-
-// value and byte length of the varint at the low end of an 8-byte window (<= 5 bytes)
-__device__ __forceinline__ uint32_t pr_varint_at(unsigned long long w, uint32_t *nf) {
-    const unsigned long long stop = ~w & 0x8080808080ull;
-    const uint32_t n = (uint32_t)__ffsll((long long)stop) >> 3;
-    *nf = n;
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 5; ++k) if (k < n) v |= (uint32_t)((w >> (8 * k)) & 0x7full) << (7 * k);
-    return v;
-}
-__device__ __forceinline__ uint32_t pr_first_varint(const uint8_t *__restrict__ p, uint32_t *nf) {
-    unsigned long long w;
-    __builtin_memcpy(&w, p, 8);      // the value buffers carry 16 bytes of slack behind the last list
-    return pr_varint_at(w, nf);
-}
 
 struct pr_args {
     const uint64_t *offsets; const uint8_t *value; const uint32_t *last_ids; uint64_t H;
@@ -57,7 +40,7 @@ __global__ __launch_bounds__(256) void k_pr_plan(pr_args A, uint32_t *__restrict
     if (t >= A.H) return;
     const uint64_t b0 = A.offsets[t], b1 = A.offsets[t + 1];
     uint32_t nf = 0;
-    const uint32_t f = pr_first_varint(A.value + b0, &nf), l = A.last_ids[t];
+    const uint32_t f = fd_first_varint(A.value + b0, &nf), l = A.last_ids[t];
     const uint64_t fl = (uint64_t)f - A.first_id, ll = (uint64_t)l - A.first_id;
     uint32_t m = PR_MODE_COPY, sz = (uint32_t)(b1 - b0), nl = l;
     if (b1 - b0 > 0xffffffffull) atomicOr(err, 2u);                      // a list of 4 GiB or more: FDGPU_ERANGE
@@ -70,7 +53,7 @@ __global__ __launch_bounds__(256) void k_pr_plan(pr_args A, uint32_t *__restrict
         else {
             const uint32_t nfirst = A.first_id + (uint32_t)A.K[fl];
             nl = A.first_id + (uint32_t)A.K[ll];
-            if (nfirst != f) { m = PR_MODE_REBASE; sz = sz - nf + pr_varint_len(nfirst); }
+            if (nfirst != f) { m = PR_MODE_REBASE; sz = sz - nf + fd_varint_len(nfirst); }
         }
     }
     sizes[t] = m == PR_MODE_RECODE ? 0u : sz;
@@ -140,7 +123,7 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
             uint32_t nfj;
-            d[j] = (sb >> j) & 1u ? pr_varint_at(win >> (8 * j), &nfj) : 0u;
+            d[j] = (sb >> j) & 1u ? fd_varint_at(win >> (8 * j), &nfj) : 0u;
             dsum += d[j];
         }
         const uint32_t dinc = pr_scan_add(dsum, lane);
@@ -173,7 +156,7 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
             ln[j] = 0; nd[j] = 0;
             if ((kmask >> j) & 1u) {
                 nd[j] = q ? nid[j] - (uint32_t)(q - 1u) : nid[j];
-                ln[j] = pr_varint_len(nd[j]);
+                ln[j] = fd_varint_len(nd[j]);
                 lsum += ln[j];
                 q = (uint64_t)nid[j] + 1u;
             }
@@ -209,34 +192,25 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
     }
 }
 
-// ---- RE-BASE / VERBATIM lists: eight lanes per list, new head varint first, then the bytes behind the old head
-typedef unsigned int pr_u32x4 __attribute__((ext_vector_type(4)));
+// ---- RE-BASE / VERBATIM lists: eight lanes per list (fd_list_copy), new head varint first, then the bytes behind the old head
 __global__ __launch_bounds__(256) void k_pr_copy(pr_args A, const uint8_t *__restrict__ mode, const uint32_t *__restrict__ sizes,
                                                  const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out_value) {
     const uint64_t t = (uint64_t)blockIdx.x * 32u + (threadIdx.x >> 3);
     if (t >= A.H) return;
     const uint32_t m = mode[t];
     if (m == PR_MODE_RECODE || sizes[t] == 0) return;
-    const uint32_t sub = threadIdx.x & 7u;
     const uint64_t b0 = A.offsets[t], b1 = A.offsets[t + 1];
-    uint8_t *d = out_value + out_off[t];
     const uint8_t *sp = A.value + b0;
     uint64_t n = b1 - b0;
+    uint32_t head = 0, dl = 0;
     if (m == PR_MODE_REBASE) {
         uint32_t nf = 0;
-        const uint32_t f = pr_first_varint(sp, &nf);
-        const uint32_t nfirst = A.first_id + (uint32_t)A.K[(uint64_t)f - A.first_id];
-        const uint32_t dl = pr_varint_len(nfirst);
-        if (sub < dl) d[sub] = (uint8_t)(((nfirst >> (7u * sub)) & 0x7fu) | (sub + 1u < dl ? 0x80u : 0u));
-        d += dl; sp += nf; n -= nf;
+        const uint32_t f = fd_first_varint(sp, &nf);
+        head = A.first_id + (uint32_t)A.K[(uint64_t)f - A.first_id];
+        dl = fd_varint_len(head);
+        sp += nf; n -= nf;
     }
-    uint64_t o = (uint64_t)sub * 16u;
-    for (; o + 16 <= n; o += 128) {
-        pr_u32x4 v;
-        __builtin_memcpy(&v, sp + o, 16);
-        __builtin_memcpy(d + o, &v, 16);
-    }
-    if (o < n) for (uint64_t z = o; z < n; ++z) d[z] = sp[z];
+    fd_list_copy(out_value + out_off[t], head, dl, sp, n, threadIdx.x & 7u);
 }
 
 // ---- non-empty lists -> their slots; offsets[H'] = the new value length
@@ -256,10 +230,6 @@ __global__ void k_pr_nonzero(const uint32_t *__restrict__ sizes, uint64_t H, uin
     if (t < H) flag[t] = sizes[t] ? 1u : 0u;
 }
 
-void fd_mg_last_ids(const uint64_t *offsets, const uint8_t *value, uint64_t H, uint32_t *last_ids, hipStream_t st);
-
-static inline unsigned pr_grid(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
-
 extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uint8_t *keep, uint64_t n_keep, fdgpu_index **out) { FD_LOCK(c);
     if (!c || !ix || !out || (n_keep && !keep)) return FDGPU_EINVAL;
     *out = nullptr;
@@ -272,13 +242,8 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
     hipStream_t st = c->stream;
     const uint64_t H = ix->n_hashes, S = n_keep;
     if (!ix->last_ids && H) {      // a loaded index: last id of every list by one decode pass, kept with the index (as fdgpu_index_merge does)
-        fdgpu_index *mp = const_cast<fdgpu_index *>(ix);
-        hipError_t le = hipSuccess;
-        if (mp->ctx) { mp->last_ids = (uint32_t *)mp->ctx->pool_alloc(H * 4, &le); mp->cap_last = mp->ctx->last_cap; }
-        else le = hipMalloc((void **)&mp->last_ids, H * 4);
-        if (le != hipSuccess) { mp->last_ids = nullptr; c->err = std::string("index remove: ") + hipGetErrorString(le); return FDGPU_EHIP; }
         StageTimer t(c, "prune_last_ids", ix->value_len + H * 12);
-        fd_mg_last_ids(ix->offsets, ix->value, H, mp->last_ids, st);
+        if (int rc = fd_index_last_ids(c, ix)) return rc;
     }
     const uint64_t Hx = std::max<uint64_t>(H, 1);
     HIPCHK(c, c->ws[WS_KEYS_B].ensure((S + 2) * 8 + S + 16));       // K[S + 1] (u64), then keep[S]
@@ -307,10 +272,10 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
         HIPCHK(c, hipMemsetAsync(tot + 1, 0, 16, st));
         fd_exclusive_scan<uint8_t>(kd, S, K, scan_tmp, tot, st);
         if (H) {
-            hipLaunchKernelGGL(k_pr_plan, dim3(pr_grid(H, 256)), dim3(256), 0, st, A, sizes, nlast, mode, recode, is_long, err);
+            hipLaunchKernelGGL(k_pr_plan, dim3(fd_grid(H, 256)), dim3(256), 0, st, A, sizes, nlast, mode, recode, is_long, err);
             fd_exclusive_scan<uint8_t>(recode, H, pre_a, scan_tmp, tot, st);
             fd_exclusive_scan<uint8_t>(is_long, H, pre_b, scan_tmp, tot, st);
-            hipLaunchKernelGGL(k_pr_order, dim3(pr_grid(H, 256)), dim3(256), 0, st, recode, is_long, pre_a, pre_b, H, order);
+            hipLaunchKernelGGL(k_pr_order, dim3(fd_grid(H, 256)), dim3(256), 0, st, recode, is_long, pre_a, pre_b, H, order);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -322,10 +287,10 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
     {
         StageTimer t(c, "prune_sizes", ix->value_len + H * 16);
         if (n_recode)
-            hipLaunchKernelGGL((k_pr_recode<false>), dim3(pr_grid(n_recode, 4)), dim3(256), 0, st, A, order, n_recode, sizes, nlast,
+            hipLaunchKernelGGL((k_pr_recode<false>), dim3(fd_grid(n_recode, 4)), dim3(256), 0, st, A, order, n_recode, sizes, nlast,
                                (unsigned long long *)(tot + 1), (const uint64_t *)nullptr, (uint8_t *)nullptr, err);
         if (H) {
-            hipLaunchKernelGGL(k_pr_nonzero, dim3(pr_grid(H, 256)), dim3(256), 0, st, sizes, H, recode);
+            hipLaunchKernelGGL(k_pr_nonzero, dim3(fd_grid(H, 256)), dim3(256), 0, st, sizes, H, recode);
             fd_exclusive_scan<uint8_t>(recode, H, pre_a, scan_tmp, tot, st);          // slots of the non-empty lists
             fd_exclusive_scan<uint32_t>(sizes, H, pre_b, scan_tmp, tot, st);          // value offsets (empty lists: 0 bytes)
         }
@@ -343,28 +308,22 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
     if (eb & 2u) FAIL(c, FDGPU_ERANGE, "index remove: a posting list reaches 4 GiB");
     if (eb & 1u) FAIL(c, FDGPU_EINVAL, "index remove: the index holds ids outside [first_id, first_id + n_structures)");
     Hn = hv[0]; Vn = hv[1];
-    fdgpu_index *r = new (std::nothrow) fdgpu_index();
-    if (!r) return FDGPU_ENOMEM;
-    r->ctx = c; r->n_hashes = Hn; r->value_len = Vn; r->n_postings = ix->n_postings - hv[2]; r->n_structures = S2; r->first_id = ix->first_id;
-    hipError_t e;
-    r->value = (uint8_t *)c->pool_alloc(Vn + 16, &e); r->cap_value = c->last_cap;
-    if (e == hipSuccess) { r->hashes = (uint32_t *)c->pool_alloc(std::max<uint64_t>(Hn, 1) * 4, &e); r->cap_hashes = c->last_cap; }
-    if (e == hipSuccess) { r->offsets = (uint64_t *)c->pool_alloc((Hn + 1) * 8, &e); r->cap_offsets = c->last_cap; }
-    if (e == hipSuccess) { r->last_ids = (uint32_t *)c->pool_alloc(std::max<uint64_t>(Hn, 1) * 4, &e); r->cap_last = c->last_cap; }
-    if (e != hipSuccess) { c->err = std::string("index remove alloc: ") + hipGetErrorString(e); fdgpu_index_destroy(r); return FDGPU_EHIP; }
+    fdgpu_index *r = nullptr;
+    if (int rc = fd_index_new(c, true, Hn, Vn, true, &r)) return rc;
+    r->n_postings = ix->n_postings - hv[2]; r->n_structures = S2; r->first_id = ix->first_id;
     {
         StageTimer t(c, "prune_write", ix->value_len + Vn + H * 8);
         if (H) {
             if (n_recode)
-                hipLaunchKernelGGL((k_pr_recode<true>), dim3(pr_grid(n_recode, 4)), dim3(256), 0, st, A, order, n_recode, sizes, nlast,
+                hipLaunchKernelGGL((k_pr_recode<true>), dim3(fd_grid(n_recode, 4)), dim3(256), 0, st, A, order, n_recode, sizes, nlast,
                                    (unsigned long long *)(tot + 1), pre_b, r->value, err);
-            hipLaunchKernelGGL(k_pr_copy, dim3(pr_grid(H, 32)), dim3(256), 0, st, A, mode, sizes, pre_b, r->value);
-            hipLaunchKernelGGL(k_pr_compact, dim3(pr_grid(H, 256)), dim3(256), 0, st, ix->hashes, sizes, nlast, pre_a, pre_b, H, r->hashes, r->offsets, r->last_ids);
+            hipLaunchKernelGGL(k_pr_copy, dim3(fd_grid(H, 32)), dim3(256), 0, st, A, mode, sizes, pre_b, r->value);
+            hipLaunchKernelGGL(k_pr_compact, dim3(fd_grid(H, 256)), dim3(256), 0, st, ix->hashes, sizes, nlast, pre_a, pre_b, H, r->hashes, r->offsets, r->last_ids);
         } else {
             (void)hipMemsetAsync(r->offsets, 0, 8, st);
         }
     }
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { c->err = std::string("index remove write: ") + hipGetErrorString(e); fdgpu_index_destroy(r); return FDGPU_EHIP; }
     *out = r;
     return FDGPU_OK;

@@ -253,33 +253,8 @@ __global__ __launch_bounds__(NTHR) void k_qt_score32(qt_args A) {
     uint32_t carry = 0, prev_last = 0;
     auto decode = [&](const q32_win &X, const q32_slot &S) {
         const uint32_t w0 = X.w << 6;
-        // ---- lane-local decode: the varints that END in these 16 bytes; the leading bytes of the first are the tail of the slot before —
-        // the lane below's last four bytes (lane 0 of a continued piece: lane 63 of the window before)
-        uint32_t lb = (uint32_t)__shfl_up((int)S.x4[3], 1, FD_WAVE);
-        if (lane == 0) lb = prev_last;
-        prev_last = (uint32_t)__builtin_amdgcn_readlane((int)S.x4[3], 63);
-        uint32_t cv = 0, sh = 0;
-        if (S.nby && S.rel) {
-            const uint32_t tb = ~lb & 0x80808080u;
-            const uint32_t kc = tb ? (uint32_t)__clz((int)tb) >> 3 : 4u;         // continuation bytes at the end of the look-back
-            if (kc) {
-                const uint32_t x = (lb >> (8u * (4u - kc))) & 0x7f7f7f7fu;
-                cv = (x & 0x7fu) | ((x >> 1) & 0x3f80u) | ((x >> 2) & 0x1fc000u) | ((x >> 3) & 0xfe00000u);
-                sh = 7u * kc;
-            }
-        }
-        uint32_t v[16], T = 0, D = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const uint32_t b = (S.x4[i >> 2] >> (8 * (i & 3))) & 0xffu;
-            cv |= (b & 0x7fu) << (sh & 31u);
-            const bool term = (uint32_t)i < S.nby && !(b & 0x80u);
-            v[i] = term ? cv : 0u;
-            T |= term ? (1u << i) : 0u;
-            D += v[i];
-            sh = term ? 0u : sh + 7u;
-            cv = term ? 0u : cv;
-        }
+        uint32_t v[16], T, D;
+        qt_decode16(S.x4, S.nby, S.nby && S.rel, lane, prev_last, v, T, D);
         // ---- ids: prefix of the lane sums inside the piece, from the piece's checkpoint id (or the window before)
         const uint32_t incl = qt_wave_incl(D, lane);
         const uint32_t fl = S.pstart > w0 ? S.pstart - w0 : 0u;            // the piece's first lane in this window

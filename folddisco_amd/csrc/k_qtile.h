@@ -1,6 +1,6 @@
 // k_qtile.h — arithmetic and wavefront helpers shared by the tiled scoring kernels (k_qtile.hip, k_qscore32.hip): the ranking key and its
 // histogram bins (candidate selection of src/cli/workflows/query_pdb.rs:404-411 over the idf sums of src/controller/count_query.rs:82-220),
-// DPP wave scan, block scan, the row-group hit counter.
+// DPP wave scan, block scan, the row-group hit counter, the lane-local decode of a 16-byte slot of a posting list.
 #pragma once
 #include "fdgpu_internal.h"
 
@@ -51,6 +51,39 @@ __device__ __forceinline__ uint32_t qt_block_excl(uint32_t v, uint32_t tid, uint
 }
 typedef unsigned int qt_u32x4 __attribute__((ext_vector_type(4)));
 struct qt_step { qt_u32x4 w; uint32_t c, pstart, nby, rel; };
+
+// lane-local decode of a lane's 16-byte slot w of a posting list (its first nby bytes belong to the list): the varints that END in these 16
+// bytes.  The leading bytes of the first are the tail of the slot before — the lane below's last four bytes, lane 0: lane 63 of the step
+// before (prev_last, carried from step to step); look_back = false: the slot starts its piece, nothing comes before.  v[i] = value of the
+// varint that ends at byte i (0: none), T = bits of those bytes, D = sum of v
+__device__ __forceinline__ void qt_decode16(const qt_u32x4 &w, uint32_t nby, bool look_back, uint32_t lane, uint32_t &prev_last, uint32_t (&v)[16],
+                                            uint32_t &T, uint32_t &D) {
+    uint32_t lb = (uint32_t)__shfl_up((int)w[3], 1, FD_WAVE);
+    if (lane == 0) lb = prev_last;
+    prev_last = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
+    uint32_t cv = 0, sh = 0;
+    if (look_back) {
+        const uint32_t tb = ~lb & 0x80808080u;
+        const uint32_t kc = tb ? (uint32_t)__clz((int)tb) >> 3 : 4u;         // continuation bytes at the end of the look-back
+        if (kc) {
+            const uint32_t x = (lb >> (8u * (4u - kc))) & 0x7f7f7f7fu;
+            cv = (x & 0x7fu) | ((x >> 1) & 0x3f80u) | ((x >> 2) & 0x1fc000u) | ((x >> 3) & 0xfe00000u);
+            sh = 7u * kc;
+        }
+    }
+    T = 0; D = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const uint32_t b = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
+        cv |= (b & 0x7fu) << (sh & 31u);
+        const bool term = (uint32_t)i < nby && !(b & 0x80u);
+        v[i] = term ? cv : 0u;
+        T |= term ? (1u << i) : 0u;
+        D += v[i];
+        sh = term ? 0u : sh + 7u;
+        cv = term ? 0u : cv;
+    }
+}
 
 // groups (runs of rows that end at a set bit of `ends`) holding at least one set bit of `m`, one 32-row word of a longer row list:
 // adding the non-end hits to the non-end positions lets a hit's carry run up to its group's end bit; carry = the group straddles the word

@@ -321,33 +321,8 @@ __global__ __launch_bounds__(NTHR) void k_qt_score(qt_args A) {
                 for (uint32_t base = s_beg; base < s_end; base += FD_WAVE) {
                     const bool more = base + FD_WAVE < s_end;
                     if (AHEAD && more) prep(base + FD_WAVE, nxt);
-                    // ---- lane-local decode: the varints that END in these 16 bytes; the leading bytes of the first are the tail of the
-                    // slot before — the lane below's last four bytes (lane 0: lane 63 of the step before)
-                    uint32_t lb = (uint32_t)__shfl_up((int)cur.w[3], 1, FD_WAVE);
-                    if (lane == 0) lb = prev_last;
-                    prev_last = (uint32_t)__builtin_amdgcn_readlane((int)cur.w[3], 63);
-                    uint32_t cv = 0, sh = 0;
-                    if (cur.rel) {
-                        const uint32_t tb = ~lb & 0x80808080u;
-                        const uint32_t kc = tb ? (uint32_t)__clz((int)tb) >> 3 : 4u;         // continuation bytes at the end of the look-back
-                        if (kc) {
-                            const uint32_t x = (lb >> (8u * (4u - kc))) & 0x7f7f7f7fu;
-                            cv = (x & 0x7fu) | ((x >> 1) & 0x3f80u) | ((x >> 2) & 0x1fc000u) | ((x >> 3) & 0xfe00000u);
-                            sh = 7u * kc;
-                        }
-                    }
-                    uint32_t v[16], T = 0, D = 0;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const uint32_t b = (cur.w[i >> 2] >> (8 * (i & 3))) & 0xffu;
-                        cv |= (b & 0x7fu) << (sh & 31u);
-                        const bool term = (uint32_t)i < cur.nby && !(b & 0x80u);
-                        v[i] = term ? cv : 0u;
-                        T |= term ? (1u << i) : 0u;
-                        D += v[i];
-                        sh = term ? 0u : sh + 7u;
-                        cv = term ? 0u : cv;
-                    }
+                    uint32_t v[16], T, D;
+                    qt_decode16(cur.w, cur.nby, cur.rel != 0u, lane, prev_last, v, T, D);
                     // ---- ids: prefix of the lane sums inside the row, from the row's checkpoint id (or the step before)
                     const uint32_t incl = qt_wave_incl(D, lane);
                     const uint32_t fl = cur.pstart > base ? cur.pstart - base : 0u;            // the row's first lane in this step
