@@ -1,4 +1,4 @@
-"""`python -m folddisco_amd index|query|update …` — the reference's two hot-path subcommands (and `update`, which it lacks) with its flag names and defaults
+"""`python -m folddisco_amd index|query|update|verify …` — the reference's two hot-path subcommands (and `update` and `verify`, which it lacks) with its flag names and defaults
 (src/cli/main.rs:26-110, src/cli/workflows/build_index.rs:64-241, src/cli/workflows/query_pdb.rs:144-519), driving the
 GPU path through the C ABI.  Structure order = lexicographic path order (the reference uses readdir order, which is
 filesystem dependent; SURVEY §7 hard part 3).  Only the default PDBTrRosetta encoding is supported; input is PDB or mmCIF, optionally gzip."""
@@ -281,6 +281,8 @@ def cmd_update(a):
     (fdgpu_index_remove), the added structures are built at the next ids with the hash parameters of PREFIX.type and merged on the device
     (fdgpu_index_merge).  The four files are written under temporary names beside the output prefix and then renamed over it."""
     plan = _update_plan(a)
+    if a.verify:
+        _verify_files(a.index)
     import folddisco_amd as fd
     from folddisco_amd import indexio, structure
     cfg, keep, add_paths = plan["cfg"], plan["keep"], plan["add_paths"]
@@ -293,6 +295,8 @@ def cmd_update(a):
     v, h, o = indexio.read_index_files(a.index)
     ix = fd.FolddiscoIndex.load(ctx, h, o, v, len(keep))
     del v, h, o
+    if a.verify:                                 # before the prune or the merge uses its offsets and ids as addresses
+        _stop_if_unsound(ix.verify(), a.index)
     if n_kept < len(keep):
         pruned = ix.remove(keep)
         del ix                                   # the loaded index is released once the pruned one exists
@@ -304,6 +308,8 @@ def cmd_update(a):
         ix = _merge_resident(fd, [ix] + parts)
         del parts
         rows += indexio.lookup_rows(n_kept, [indexio.parse_path_by_id_type(x, a.id) for x in add_paths], nres, plddt)
+    if a.verify:                                 # the result, before anything is written
+        _stop_if_unsound(ix.verify(), "the updated index; nothing was written")
     out = a.output or a.index
     tmp = f"{out}.update-tmp{os.getpid()}"
     try:
@@ -323,12 +329,62 @@ def cmd_update(a):
               file=sys.stderr)
 
 
+def _verify_files(prefix):
+    """the file checks of `verify` (indexio.check_index_files) -> the index's arrays and its number of structures; exits with status 2 when a file is
+    missing or unreadable, with status 1 and a [FAIL] line when the files contradict each other"""
+    from folddisco_amd import indexio
+    for ext in INDEX_FILES:
+        if not os.path.isfile(prefix + ext):
+            print(f"[FAIL] {prefix}{ext} not found", file=sys.stderr)
+            sys.exit(2)
+    try:
+        bad = indexio.check_index_files(prefix)
+        if not bad:
+            v, h, o = indexio.read_index_files(prefix)
+            with open(prefix + ".lookup") as f:
+                n = sum(1 for _ in f)
+    except (OSError, ValueError, UnicodeDecodeError) as e:
+        print(f"[FAIL] {prefix}: unreadable ({e})", file=sys.stderr)
+        sys.exit(2)
+    if bad:
+        print("[FAIL] index files are inconsistent: " + "; ".join(bad))
+        sys.exit(1)
+    return v, h, o, n
+
+
+def _stop_if_unsound(report, what):
+    """--verify of query / update: an unsound index ends the command with the verify message and status 1"""
+    if not report.ok:
+        print(f"{report} ({what})")
+        sys.exit(1)
+
+
+def cmd_verify(a):
+    """`verify`: is the index at PREFIX well formed?  File checks (sizes, .lookup ids, chunk_size), then every posting list decoded once, on the
+    device (fdgpu_index_verify) or with --host on the CPU (fdgpu_verify_host; no device is opened).  Exit status 0 / 1, 2 for unreadable input."""
+    from folddisco_amd import indexio
+    v, h, o, n = _verify_files(a.index)
+    if a.host:
+        rep = indexio.verify_host(v, h, o, n, threads=a.threads)
+    else:
+        import folddisco_amd as fd
+        ctx = fd.Context(a.device)
+        rep = fd.FolddiscoIndex.load(ctx, h, o, v, n).verify()
+    print(rep)
+    if a.verbose:
+        print(f"[INFO] {a.index}: {len(h)} hashes, {len(v)} value bytes, {n} structures; checked on the {'host' if a.host else 'device'}"
+              + ("" if rep.list_stage else "; the offsets table is damaged, the lists were not decoded"), file=sys.stderr)
+    sys.exit(0 if rep.ok else 1)
+
+
 def cmd_query(a):
     import folddisco_amd as fd
     from folddisco_amd import indexio, query, structure
     if not a.index:
         sys.exit("[FAIL] -i/--index is required")
     rank, world, dev = _init_dist(a)
+    if a.verify and world == 1:
+        _verify_files(a.index)
     ctx = fd.Context(a.device)
     tids, nres, plddt, db_keys = indexio.load_lookup(a.index + ".lookup")
     cfg = indexio.load_type(a.index + ".type")
@@ -348,6 +404,8 @@ def cmd_query(a):
     else:
         v, h, o = indexio.read_index_files(a.index)
         ix = fd.FolddiscoIndex.load(ctx, h, o, v, len(tids))
+    if a.verify:                                 # before any scoring kernel sees the bytes
+        _stop_if_unsound(ix.verify(), a.index if world == 1 else sp)
     if a.query.endswith((".txt", ".tsv")):
         queries = []
         for line in open(a.query):
@@ -489,6 +547,7 @@ def main(argv=None):
     pq.add_argument("-o", "--output", default="")
     pq.add_argument("-v", "--verbose", action="store_true")
     pq.add_argument("--device", type=int, default=0)
+    pq.add_argument("--verify", action="store_true", help="check the loaded index first (see `verify`) and stop with status 1 if it is damaged")
     pu = sub.add_parser("update")                                    # index update without a rebuild (no counterpart in the reference)
     pu.add_argument("-i", "--index", required=True)
     pu.add_argument("-p", "--pdbs", default="", help="structures to append: a directory or a file, walked and ordered as `index` does")
@@ -500,6 +559,14 @@ def main(argv=None):
     pu.add_argument("--chunk", type=int, default=16384)
     pu.add_argument("--device", type=int, default=0)
     pu.add_argument("-v", "--verbose", action="store_true")
+    pu.add_argument("--verify", action="store_true", help="check the index before it is touched and the result before it is written (see `verify`); "
+                    "status 1 and no file changed if either is damaged")
+    pv = sub.add_parser("verify")                                    # is the index well formed? (no counterpart in the reference: it panics on use)
+    pv.add_argument("-i", "--index", required=True)
+    pv.add_argument("--host", action="store_true", help="decode on the CPU (no device is opened)")
+    pv.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    pv.add_argument("--device", type=int, default=0)
+    pv.add_argument("-v", "--verbose", action="store_true")
     pa = sub.add_parser("analyze")                                   # src/cli/workflows/analyze.rs:19-40 (summary branch)
     pa.add_argument("-i", "--index", required=True)
     pa.add_argument("-p", "--pdbs", default=None)
@@ -529,6 +596,9 @@ def main(argv=None):
         return
     if a.cmd == "update":
         cmd_update(a)
+        return
+    if a.cmd == "verify":
+        cmd_verify(a)
         return
     if a.cmd == "index":
         if a.mmap_on_disk and a.verbose:

@@ -107,6 +107,13 @@ class FoldcompAtom(C.Structure):
                 ("chain", C.c_uint8), ("rser", C.c_uint64)]
 
 
+class VerifyReportC(C.Structure):
+    """fd_verify_report (include/fdgpu.h)"""
+    _fields_ = [("ok", C.c_uint32), ("first_mask", C.c_uint32), ("n_bad", C.c_uint64), ("class_count", C.c_uint64 * 9), ("first_slot", C.c_uint64),
+                ("first_offset", C.c_uint64), ("first_hash", C.c_uint32), ("list_stage", C.c_uint32), ("n_lists", C.c_uint64), ("n_postings", C.c_uint64),
+                ("max_id", C.c_uint64), ("max_list_bytes", C.c_uint64)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("n_struct", C.c_uint64), ("n_res", C.c_uint64), ("res_off", u64p), ("n_xyz", f32p), ("ca_xyz", f32p), ("cb_xyz", f32p),
                 ("aa", u8p), ("cb_valid", u8p), ("chain", u8p), ("resname_std", u8p), ("serial", u64p), ("bfac", f32p),
@@ -187,6 +194,8 @@ SYMBOLS = [
                                          C.POINTER(u32p), C.POINTER(u64p), u64p]),
     ("fdgpu_index_merge", C.c_int, [VP, C.POINTER(VP), C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_index_remove", C.c_int, [VP, VP, u8p, C.c_uint64, C.POINTER(VP)]),
+    ("fdgpu_index_verify", C.c_int, [VP, VP, C.POINTER(VerifyReportC)]),
+    ("fdgpu_verify_host", C.c_int, [u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyReportC)]),
     ("fdgpu_posting_bytes", C.c_int, [VP, VP, u32p, C.c_uint64, u64p]),
     ("fdgpu_index_set_first_id", C.c_int, [VP, C.c_uint64]),
     ("fdgpu_host_libm_matches", C.c_int, [VP]),

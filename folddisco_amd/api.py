@@ -233,6 +233,14 @@ class FolddiscoIndex:
     def save(self, prefix: str):
         self.ctx.check(self.ctx.L.fdgpu_index_save(self.ctx.h, self.h, prefix.encode()))
 
+    def verify(self):
+        """is the resident index well formed (fdgpu_index_verify: csrc/fd_verify.h, one decode pass over every value byte on the device)?
+        -> indexio.VerifyReport; a damaged index is a verdict, not an exception"""
+        from .indexio import VerifyReport
+        r = _lib.VerifyReportC()
+        self.ctx.check(self.ctx.L.fdgpu_index_verify(self.ctx.h, self.h, C.byref(r)))
+        return VerifyReport.from_c(r)
+
     # ---- index update: byte-identical to a fresh build over (kept structures in their order) + (added structures)
     def remove(self, keep) -> "FolddiscoIndex":
         """a new resident index without the structures whose keep[s] is false (fdgpu_index_remove): the kept ones are renumbered

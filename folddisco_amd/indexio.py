@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -182,6 +183,104 @@ def read_index_files(prefix: str):
     hashes = raw[8: 8 + 4 * H].view(np.uint32).copy()
     offsets = raw[8 + 4 * H: 8 + 4 * H + 8 * (H + 1)].copy().view(np.uint64)
     return value, hashes, offsets
+
+
+VERIFY_CLASSES = ("OFFSET_ENDS", "OFFSET_ORDER", "HASH_ORDER", "LIST_END", "VARINT_LONG", "VARINT_FORM", "ZERO_DELTA", "ID_RANGE")      # classes 1..8 (csrc/fd_verify.h)
+
+
+@dataclass
+class VerifyReport:
+    """fd_verify_report: the verdict of FolddiscoIndex.verify / verify_host.  counts: slots per class name; first_*: the lowest bad slot (None when ok);
+    the totals are those of a clean index (0 otherwise)."""
+    ok: bool
+    n_bad: int
+    counts: dict
+    first_slot: int | None
+    first_hash: int | None
+    first_offset: int | None
+    first_classes: tuple
+    list_stage: bool
+    n_lists: int
+    n_postings: int
+    max_id: int
+    max_list_bytes: int
+
+    @staticmethod
+    def from_c(r) -> "VerifyReport":
+        ok = bool(r.ok)
+        return VerifyReport(ok=ok, n_bad=int(r.n_bad), counts={n: int(r.class_count[c + 1]) for c, n in enumerate(VERIFY_CLASSES)},
+                            first_slot=None if ok else int(r.first_slot), first_hash=None if ok else int(r.first_hash),
+                            first_offset=None if ok else int(r.first_offset),
+                            first_classes=tuple(n for c, n in enumerate(VERIFY_CLASSES) if r.first_mask >> c & 1), list_stage=bool(r.list_stage),
+                            n_lists=int(r.n_lists), n_postings=int(r.n_postings), max_id=int(r.max_id), max_list_bytes=int(r.max_list_bytes))
+
+    def __str__(self) -> str:
+        if self.ok:
+            return f"[OK] index is well formed: {self.n_lists} lists, {self.n_postings} postings, max id {self.max_id}, longest list {self.max_list_bytes} bytes"
+        counts = ", ".join(f"{n} {v}" for n, v in self.counts.items() if v)
+        return (f"[FAIL] index is damaged: {self.n_bad} bad slot(s); first at slot {self.first_slot} (hash {self.first_hash}, offset {self.first_offset}): "
+                f"{'+'.join(self.first_classes)}; slots per class: {counts}")
+
+
+def verify_host(value, hashes, offsets, n_structures: int, first_id: int = 0, threads: int = 1) -> VerifyReport:
+    """the index checks of csrc/fd_verify.h on host arrays (fdgpu_verify_host): no context, no device"""
+    value = np.ascontiguousarray(value, dtype=np.uint8)
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(hashes) + 1:
+        raise ValueError(f"offsets: {len(hashes) + 1} entries expected, got {len(offsets)}")
+    r = _lib.VerifyReportC()
+    rc = _lib.load().fdgpu_verify_host(hashes.ctypes.data_as(u32p), offsets.ctypes.data_as(u64p), len(hashes), value.ctypes.data_as(u8p), len(value),
+                                       int(first_id), int(n_structures), max(int(threads), 1), C.byref(r))
+    if rc != 0:
+        raise ValueError(f"fdgpu_verify_host failed ({rc})")
+    return VerifyReport.from_c(r)
+
+
+def check_index_files(prefix: str) -> list:
+    """what can be said about an index's four files without decoding a posting: -> a list of complaints, empty if there is none.
+    chunk_size of PREFIX.type must equal the rows of PREFIX.lookup: `index` and `update` write it so, and so does the reference
+    (build_index.rs:133, 218: the number of input paths, one .lookup row each)."""
+    bad = []
+    for ext in ("", ".offset", ".lookup", ".type"):
+        if not os.path.isfile(prefix + ext):
+            bad.append(f"{prefix}{ext} not found")
+    if bad:
+        return bad
+    osz, vsz = os.path.getsize(prefix + ".offset"), os.path.getsize(prefix)
+    H = None
+    if osz < 16:
+        bad.append(f"{prefix}.offset: {osz} bytes, shorter than an empty table (16)")
+    else:
+        with open(prefix + ".offset", "rb") as f:
+            H = int(np.frombuffer(f.read(8), np.uint64)[0])
+            want = 8 + 4 * H + 8 * (H + 1)
+            if osz != want:
+                bad.append(f"{prefix}.offset: {osz} bytes, its header ({H} hashes) asks for {want}")
+            else:
+                f.seek(want - 8)
+                end = int(np.frombuffer(f.read(8), np.uint64)[0])
+                if end != vsz:
+                    bad.append(f"{prefix}: {vsz} bytes, the last offset of {prefix}.offset is {end}")
+    n_rows, rows_ok = 0, True
+    with open(prefix + ".lookup") as f:
+        for line in f:
+            p = line.rstrip("\n").split("\t")
+            if rows_ok and (len(p) < 4 or p[0] != str(n_rows)):
+                bad.append(f"{prefix}.lookup: row {n_rows + 1} does not start with id {n_rows} (or has fewer than four columns)")
+                rows_ok = False
+            n_rows += 1
+    try:
+        cs = load_type(prefix + ".type").get("chunk_size")
+    except (ValueError, IndexError) as e:
+        cs = None
+        bad.append(f"{prefix}.type does not parse: {e}")
+    else:
+        if not isinstance(cs, int):
+            bad.append(f"{prefix}.type: no integer chunk_size")
+        elif cs != n_rows:
+            bad.append(f"{prefix}.type: chunk_size = {cs}, {prefix}.lookup has {n_rows} rows")
+    return bad
 
 
 def merge_subindices(parts):

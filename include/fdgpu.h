@@ -511,6 +511,38 @@ int fdgpu_index_merge(fdgpu_ctx *ctx, const fdgpu_index *const *parts, uint64_t 
  * Appending is fdgpu_index_build of the new structures at first_id + (kept count) and fdgpu_index_merge of the two. */
 int fdgpu_index_remove(fdgpu_ctx *ctx, const fdgpu_index *ix, const uint8_t *keep, uint64_t n_keep, fdgpu_index **out);
 
+/* ---- index verification -----------------------------------------------------------------------------------------------------
+ * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
+ * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
+ * decoded ids as addresses.  A slot is a position 0 .. n_hashes of the offsets table; class c is bit (c - 1) of a slot's mask.
+ * Every field is a pure function of the index: the device and the host checker fill the same report, bit for bit. */
+#define FD_VERIFY_OFFSET_ENDS 1
+#define FD_VERIFY_OFFSET_ORDER 2
+#define FD_VERIFY_HASH_ORDER 3
+#define FD_VERIFY_LIST_END 4
+#define FD_VERIFY_VARINT_LONG 5
+#define FD_VERIFY_VARINT_FORM 6
+#define FD_VERIFY_ZERO_DELTA 7
+#define FD_VERIFY_ID_RANGE 8
+typedef struct fd_verify_report {
+    uint32_t ok;              /* 1: no slot shows any class */
+    uint32_t first_mask;      /* classes of the lowest bad slot */
+    uint64_t n_bad;           /* slots that show at least one class */
+    uint64_t class_count[9];  /* [c]: slots that show class c (1..8); [0] unused */
+    uint64_t first_slot;      /* the lowest bad slot, its offsets[] entry and its hash (0 for slot n_hashes); all 0 when ok */
+    uint64_t first_offset;
+    uint32_t first_hash;
+    uint32_t list_stage;      /* 1: the table was clean and the lists were decoded */
+    uint64_t n_lists, n_postings, max_id, max_list_bytes;      /* of a clean index (ok == 1), else 0 */
+} fd_verify_report;
+/* Checks a resident index (built, merged, pruned, sliced or loaded; ids first_id .. first_id + n_structures - 1) on the device: a table
+ * kernel, then - only if it found nothing - one decode pass over every value byte.  Returns FDGPU_OK when the check ran, whatever the
+ * verdict.  The list pass reads nothing outside the value bytes + their slack, whatever they hold. */
+int fdgpu_index_verify(fdgpu_ctx *ctx, const fdgpu_index *index, fd_verify_report *report);
+/* The same check on host arrays (the payload of PREFIX.offset and PREFIX), n_threads host threads over slot ranges (0 = 1).  No device. */
+int fdgpu_verify_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes, const uint8_t *value, uint64_t value_len,
+                      uint64_t first_id, uint64_t n_structures, uint32_t n_threads, fd_verify_report *report);
+
 /* `analyze -p`: right-tail hypergeometric test of every encoding (src/controller/summary.rs:543-628, get_enriched_hashes /
  * hypergeometric_test with the reference's log-factorial): p_value[k] = P(X >= query_count[k]) for a sample of total_query draws from a
  * population of total_bg + total_query holding bg_count[k] + query_count[k] successes.  Host threads; no device needed. */
