@@ -1,4 +1,4 @@
-"""`python -m folddisco_amd index|query|update|verify …` — the reference's two hot-path subcommands (and `update` and `verify`, which it lacks) with its flag names and defaults
+"""`python -m folddisco_amd index|query|update|verify|reshard …` — the reference's two hot-path subcommands (and `update`, `verify` and `reshard`, which it lacks) with its flag names and defaults
 (src/cli/main.rs:26-110, src/cli/workflows/build_index.rs:64-241, src/cli/workflows/query_pdb.rs:144-519), driving the
 GPU path through the C ABI.  Structure order = lexicographic path order (the reference uses readdir order, which is
 filesystem dependent; SURVEY §7 hard part 3).  Only the default PDBTrRosetta encoding is supported; input is PDB or mmCIF, optionally gzip."""
@@ -377,6 +377,107 @@ def cmd_verify(a):
     sys.exit(0 if rep.ok else 1)
 
 
+def _reshard_plan(a):
+    """everything `reshard` decides before it opens a device: -> (source prefixes, structures).  Status 2 for missing or unreadable files,
+    status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
+    from folddisco_amd import indexio
+    for name, w in (("--from", a.from_), ("--to", a.to)):
+        if not 1 <= w <= 64:
+            sys.exit(f"[FAIL] reshard: {name} {w} is outside 1..64")
+    if a.from_ == a.to:
+        sys.exit(f"[FAIL] reshard: --from and --to are both {a.to}: nothing to do")
+    srcs = [a.index] if a.from_ == 1 else [_shard_prefix(a.index, k, a.from_) for k in range(a.from_)]
+    need = [a.index + ".lookup", a.index + ".type"] + [s + ext for s in srcs for ext in ("", ".offset")]
+    for f in need:
+        if not os.path.isfile(f):
+            print(f"[FAIL] {f} not found", file=sys.stderr)
+            sys.exit(2)
+    try:
+        bad, n = indexio.check_lookup_type(a.index)
+        for s in srcs:
+            bad += indexio.check_value_offset_pair(s)
+    except (OSError, ValueError, UnicodeDecodeError) as e:
+        print(f"[FAIL] {a.index}: unreadable ({e})", file=sys.stderr)
+        sys.exit(2)
+    if bad:
+        print("[FAIL] index files are inconsistent: " + "; ".join(bad))
+        sys.exit(1)
+    return srcs, n
+
+
+def cmd_reshard(a):
+    """`reshard`: the index at PREFIX (--from 1) or its shards PREFIX.shard<k>ofV (--from V) rewritten as W shards by structure id range
+    (--to W: OUT.shard<r>ofW, the ranges of indexio.shard_bounds, ids absolute — what a W-rank `query` reads) or as the single index (--to 1).
+    Shards are merged and cut on the device (fdgpu_index_merge, fdgpu_index_split) or with --host on the CPU (no device is opened).  Files are
+    written under temporary names and renamed at the end; shard files of another count are left alone."""
+    import shutil
+    from folddisco_amd import indexio
+    srcs, S = _reshard_plan(a)
+    V, W = a.from_, a.to
+    out = a.output or a.index
+    try:
+        loaded = [indexio.read_index_files(s) for s in srcs]
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] {a.index}: unreadable ({e})", file=sys.stderr)
+        sys.exit(2)
+    src_b, dst_b = indexio.shard_bounds(V, S), indexio.shard_bounds(W, S)
+    if a.host:
+        if a.verify:
+            for k, (v, h, o) in enumerate(loaded):
+                _stop_if_unsound(indexio.verify_host(v, h, o, int(src_b[k + 1] - src_b[k]), first_id=int(src_b[k]), threads=a.threads), srcs[k])
+        whole = loaded[0] if V == 1 else indexio.merge_subindices(loaded)
+        del loaded
+        parts = [whole] if W == 1 else indexio.split_host(*whole, bounds=dst_b, first_id=0, threads=a.threads)
+        if a.verify:
+            for r, (v, h, o) in enumerate(parts):
+                _stop_if_unsound(indexio.verify_host(v, h, o, int(dst_b[r + 1] - dst_b[r]), first_id=int(dst_b[r]), threads=a.threads),
+                                 f"part {r} of the result; nothing was written")
+        stats = [(len(h), int(np.count_nonzero(v < 128)), len(v)) for v, h, o in parts]      # a posting ends at every byte without the continuation bit
+        save = [lambda p, x=x: indexio.write_index_files(p, *x) for x in parts]
+    else:
+        import folddisco_amd as fd
+        ctx = fd.Context(a.device)
+        res = [fd.FolddiscoIndex.load(ctx, h, o, v, int(src_b[k + 1] - src_b[k]), first_id=int(src_b[k])) for k, (v, h, o) in enumerate(loaded)]
+        del loaded
+        if a.verify:
+            for k, ix in enumerate(res):
+                _stop_if_unsound(ix.verify(), srcs[k])
+        whole = res[0] if V == 1 else fd.FolddiscoIndexSet(res).merge()
+        del res
+        parts = [whole] if W == 1 else whole.split(dst_b)
+        if a.verify:
+            for r, ix in enumerate(parts):
+                _stop_if_unsound(ix.verify(), f"part {r} of the result; nothing was written")
+        stats = [(ix.num_hashes, ix.num_postings, ix.value_len) for ix in parts]
+        save = [ix.save for ix in parts]
+    finals = [out] if W == 1 else [_shard_prefix(out, r, W) for r in range(W)]
+    side = [".lookup", ".type"] if out != a.index else []
+    tmp = f"{out}.reshard-tmp{os.getpid()}"
+    made = []
+    try:
+        for r, (fin, sv) in enumerate(zip(finals, save)):
+            sv(f"{tmp}.{r}")
+            made += [(f"{tmp}.{r}{ext}", fin + ext) for ext in ("", ".offset")]
+        for ext in side:
+            shutil.copyfile(a.index + ext, tmp + ext)
+            made.append((tmp + ext, out + ext))
+        for t, f in made:
+            os.replace(t, f)
+    finally:
+        for t, _ in made:
+            if os.path.exists(t):
+                os.remove(t)
+        for r in range(len(finals)):
+            for ext in ("", ".offset"):
+                if os.path.exists(f"{tmp}.{r}{ext}"):
+                    os.remove(f"{tmp}.{r}{ext}")
+    per = ", ".join(f"{h} / {p} / {b}" for h, p, b in stats)
+    print(f"[OK] {a.index}: {V} -> {W}, {S} structures, per part lists / postings / bytes: {per}")
+    if a.verbose:
+        print(f"[INFO] wrote {', '.join(finals)}" + (f" and copied .lookup / .type to {out}" if side else "") + f"; merged and cut on the {'host' if a.host else 'device'}; "
+              f"shard files of a count other than {W} are left as they are", file=sys.stderr)
+
+
 def cmd_query(a):
     import folddisco_amd as fd
     from folddisco_amd import indexio, query, structure
@@ -567,6 +668,16 @@ def main(argv=None):
     pv.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
     pv.add_argument("--device", type=int, default=0)
     pv.add_argument("-v", "--verbose", action="store_true")
+    pr = sub.add_parser("reshard")                                   # one index <-> shards by structure id range (no counterpart in the reference)
+    pr.add_argument("-i", "--index", required=True)
+    pr.add_argument("--to", type=int, required=True, help="shards to write (PREFIX.shard<r>ofW); 1 writes the single index")
+    pr.add_argument("--from", dest="from_", type=int, default=1, help="shards to read (PREFIX.shard<k>ofV); 1 (default) reads the single index")
+    pr.add_argument("-o", "--output", default="", help="output prefix (default: beside PREFIX); .lookup and .type are copied to it")
+    pr.add_argument("--host", action="store_true", help="merge and cut on the CPU (no device is opened)")
+    pr.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    pr.add_argument("--device", type=int, default=0)
+    pr.add_argument("--verify", action="store_true", help="check what was loaded and every part, each with its own id range, before anything is written (see `verify`)")
+    pr.add_argument("-v", "--verbose", action="store_true")
     pa = sub.add_parser("analyze")                                   # src/cli/workflows/analyze.rs:19-40 (summary branch)
     pa.add_argument("-i", "--index", required=True)
     pa.add_argument("-p", "--pdbs", default=None)
@@ -599,6 +710,9 @@ def main(argv=None):
         return
     if a.cmd == "verify":
         cmd_verify(a)
+        return
+    if a.cmd == "reshard":
+        cmd_reshard(a)
         return
     if a.cmd == "index":
         if a.mmap_on_disk and a.verbose:

@@ -258,6 +258,18 @@ class FolddiscoIndex:
         part = FolddiscoIndex.build(ctx, batch, first_id=self.first_id + self.n_structures, **hash_params)
         return FolddiscoIndexSet([self, part]).merge()
 
+    def split(self, bounds) -> list:
+        """this index cut by structure id range (fdgpu_index_split), the inverse of FolddiscoIndexSet(parts).merge(): part r holds the ids in
+        [bounds[r], bounds[r + 1]) unchanged and equals a build over those structures with first_id = bounds[r]; bounds ascend from first_id to
+        first_id + n_structures (equal neighbours: an empty part), 1 to 64 parts; this index stays valid"""
+        b = np.ascontiguousarray(bounds, dtype=np.uint64)
+        if b.ndim != 1 or len(b) < 1:
+            raise ValueError("bounds: a 1-d array of n_parts + 1 ids expected")
+        n = len(b) - 1
+        out = (C.c_void_p * max(n, 1))()
+        self.ctx.check(self.ctx.L.fdgpu_index_split(self.ctx.h, self.h, n, _ptr(b, u64p), out))
+        return [FolddiscoIndex(self.ctx, C.c_void_p(out[r]), int(b[r + 1] - b[r]), int(b[r])) for r in range(n)]
+
     # ---- one on-disk index from N ranks (fd_shard_index.hip; SURVEY §8e row 2, Option A)
     def range_bounds(self, n_ranges: int) -> np.ndarray:
         """n_ranges - 1 ascending hash values cutting this index into ranges of about equal posting bytes"""

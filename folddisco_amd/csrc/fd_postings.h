@@ -1,5 +1,5 @@
 // fd_postings.h — the posting-list byte format, stated once for the encoder (k_index.hip), the device merge (k_merge.hip), the removal
-// (k_prune.hip) and the host merge (fdgpu_merge_subindices).
+// (k_prune.hip), the split (k_split.hip) and the host merge (fdgpu_merge_subindices).
 //
 // A posting list is the ascending ids of the structures that hold one hash, as LEB128 varints (7-bit groups, least significant first; bit 7
 // set = another byte follows; 0 is one 0x00 byte; a u32 takes at most five bytes; codec of indextable.rs:93-99, 397-418).  The first varint
@@ -52,6 +52,47 @@ __device__ __forceinline__ void fd_list_copy(uint8_t *__restrict__ d, uint32_t h
         __builtin_memcpy(d + o, &v, 16);
     }
     if (o < n) for (uint64_t z = o; z < n; ++z) d[z] = sp[z];
+}
+
+// ---- a wavefront's walk over one list, 256 bytes per step (four per lane): shared by the removal (k_pr_recode) and the split (k_sp_cross)
+__device__ __forceinline__ uint32_t fd_wave_scan_add(uint32_t v, uint32_t lane) {      // inclusive
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o, 64); if ((int)lane >= o) v += u; }
+    return v;
+}
+__device__ __forceinline__ uint64_t fd_wave_scan_max(uint64_t v, uint32_t lane) {      // inclusive
+    for (int o = 1; o < 64; o <<= 1) { const uint64_t u = __shfl_up(v, o, 64); if ((int)lane >= o && u > v) v = u; }
+    return v;
+}
+__device__ __forceinline__ uint32_t fd_load4(const uint8_t *p) { uint32_t w; __builtin_memcpy(&w, p, 4); return w; }
+// One step: w = the lane's four bytes at p (0 beyond the list's end b1), nxt = its four bytes of the next step, prev_term = the byte before the
+// step's first one ends a varint (the list start counts as one).  Out: tb = terminator bits of the lane's bytes, sb = bytes that start a varint,
+// d[j] / nf[j] = value and byte length of the varint starting at byte j (0 where none starts), dsum = the lane's sum of d, win = the lane's word
+// and the next lane's (lane 63: the next step's first word), which every start decodes from.
+struct fd_step { uint32_t tb, sb, d[4], nf[4], dsum; unsigned long long win; };
+__device__ __forceinline__ void fd_decode_step(uint32_t w, uint32_t nxt, uint64_t p, uint64_t b1, uint32_t lane, bool prev_term, fd_step *s) {
+    uint32_t inm = 0, tb = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const bool in = p + j < b1;
+        inm |= (in ? 1u : 0u) << j;
+        tb |= (in && !((w >> (8 * j)) & 0x80u) ? 1u : 0u) << j;
+    }
+    const uint32_t tb_prev = __shfl_up(tb, 1, 64);
+    const uint32_t before0 = lane ? (tb_prev >> 3) & 1u : (prev_term ? 1u : 0u);
+    s->tb = tb;
+    s->sb = ((tb << 1) | before0) & inm & 0xfu;
+    uint32_t w_hi = __shfl_down(w, 1, 64);
+    const uint32_t n0 = __shfl(nxt, 0, 64);
+    if (lane == 63) w_hi = n0;
+    s->win = ((unsigned long long)w_hi << 32) | w;
+    s->dsum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        uint32_t nfj = 0;
+        s->d[j] = (s->sb >> j) & 1u ? fd_varint_at(s->win >> (8 * j), &nfj) : 0u;
+        s->nf[j] = (s->sb >> j) & 1u ? nfj : 0u;
+        s->dsum += s->d[j];
+    }
 }
 
 // host writer: the varint of v at out, returns its byte length

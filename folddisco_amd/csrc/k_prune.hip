@@ -14,8 +14,9 @@
 //   k_pr_plan       thread per list: head, last id, mode, new size of RE-BASE / VERBATIM lists, long-first order key
 //   k_pr_order      re-encoded lists in the order the decode kernels take them: lists above PR_LONG_BYTES first (a long list is one wavefront's
 //                   serial walk; started first, it overlaps the many short ones instead of trailing them)
-//   k_pr_recode<W>  wavefront per re-encoded list, 256 bytes per step (four per lane): terminator bits -> varint starts, each start decodes from
-//                   the lane's and its neighbour's word, wave scans turn deltas into ids and place the new deltas; W = 0 sizes, W = 1 writes
+//   k_pr_recode<W>  wavefront per re-encoded list, 256 bytes per step (four per lane; fd_decode_step of fd_postings.h, shared with k_split.hip):
+//                   terminator bits -> varint starts, each start decodes from the lane's and its neighbour's word, wave scans turn deltas into
+//                   ids and place the new deltas; W = 0 sizes, W = 1 writes
 //   k_pr_copy       eight lanes per RE-BASE / VERBATIM list, 16 bytes per lane and step, new head first
 //   k_pr_compact    hashes / offsets / last ids of the non-empty lists at their new slots
 // HBM-bound byte work: the value bytes are read twice (sizes, write) and written once; 8 bytes per hash of tables.
@@ -72,16 +73,6 @@ __global__ void k_pr_order(const uint8_t *__restrict__ recode, const uint8_t *__
     order[is_long[t] ? lpre[t] : n_long + (rpre[t] - lpre[t])] = (uint32_t)t;
 }
 
-__device__ __forceinline__ uint32_t pr_scan_add(uint32_t v, uint32_t lane) {      // inclusive
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o, FD_WAVE); if ((int)lane >= o) v += u; }
-    return v;
-}
-__device__ __forceinline__ uint64_t pr_scan_max(uint64_t v, uint32_t lane) {      // inclusive
-    for (int o = 1; o < 64; o <<= 1) { const uint64_t u = __shfl_up(v, o, FD_WAVE); if ((int)lane >= o && u > v) v = u; }
-    return v;
-}
-__device__ __forceinline__ uint32_t pr_load4(const uint8_t *p) { uint32_t w; __builtin_memcpy(&w, p, 4); return w; }
-
 // ---- re-encode: wavefront per list, 64 lanes x 4 bytes per step.  W = false: new byte size, new last id, removed postings; W = true: new bytes.
 template <bool W>
 __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__restrict__ order, uint64_t n_recode, uint32_t *__restrict__ sizes,
@@ -98,35 +89,15 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
     uint32_t out_pos = 0, removed = 0;
     bool prev_term = true;        // the byte before the step's first one ends a varint (the list start counts as one)
     const uint64_t p0 = b0 + 4u * lane;
-    uint32_t cur = p0 < b1 ? pr_load4(A.value + p0) : 0u;
+    uint32_t cur = p0 < b1 ? fd_load4(A.value + p0) : 0u;
     for (uint64_t base = b0; base < b1; base += 256) {
         const uint64_t p = base + 4u * lane, pn = p + 256;
-        const uint32_t nxt = pn < b1 ? pr_load4(A.value + pn) : 0u;      // next step's word, in flight while this one is decoded
-        const uint32_t w = cur;
-        // bytes of this lane inside the list, terminator bits, varint starts
-        uint32_t inm = 0, tb = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const bool in = p + j < b1;
-            inm |= (in ? 1u : 0u) << j;
-            tb |= (in && !((w >> (8 * j)) & 0x80u) ? 1u : 0u) << j;
-        }
-        const uint32_t tb_prev = __shfl_up(tb, 1, FD_WAVE);
-        const uint32_t before0 = lane ? (tb_prev >> 3) & 1u : (prev_term ? 1u : 0u);
-        const uint32_t sb = ((tb << 1) | before0) & inm & 0xfu;
-        // the window behind each start: this lane's word and the next lane's (lane 63: the next step's first word)
-        uint32_t w_hi = __shfl_down(w, 1, FD_WAVE);
-        const uint32_t n0 = __shfl(nxt, 0, FD_WAVE);
-        if (lane == 63) w_hi = n0;
-        const unsigned long long win = ((unsigned long long)w_hi << 32) | w;
-        uint32_t d[4], dsum = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            uint32_t nfj;
-            d[j] = (sb >> j) & 1u ? fd_varint_at(win >> (8 * j), &nfj) : 0u;
-            dsum += d[j];
-        }
-        const uint32_t dinc = pr_scan_add(dsum, lane);
+        const uint32_t nxt = pn < b1 ? fd_load4(A.value + pn) : 0u;      // next step's word, in flight while this one is decoded
+        fd_step ds;
+        fd_decode_step(cur, nxt, p, b1, lane, prev_term, &ds);
+        const uint32_t sb = ds.sb, tb = ds.tb, dsum = ds.dsum;
+        const uint32_t *d = ds.d;
+        const uint32_t dinc = fd_wave_scan_add(dsum, lane);
         uint32_t id = run_id + dinc - dsum;       // old id before this lane's first element
         // keep / remap; the lane's last kept new id for the predecessor scan
         uint32_t nid[4];
@@ -144,7 +115,7 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
                 else ++removed;
             }
         }
-        const uint64_t lmax = pr_scan_max(lane_last, lane);
+        const uint64_t lmax = fd_wave_scan_max(lane_last, lane);
         uint64_t pred = __shfl_up(lmax, 1, FD_WAVE);      // new id + 1 of the last kept element before this lane (0: none)
         if (lane == 0) pred = 0;
         if (prev_new > pred) pred = prev_new;
@@ -161,7 +132,7 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
                 q = (uint64_t)nid[j] + 1u;
             }
         }
-        const uint32_t linc = pr_scan_add(lsum, lane);
+        const uint32_t linc = fd_wave_scan_add(lsum, lane);
         if (W) {
             uint8_t *o = dst + out_pos + (linc - lsum);
 #pragma unroll

@@ -13,13 +13,9 @@ import torch
 import torch.distributed as dist
 
 from .api import REC_DTYPE  # fd_count_rec layout (20 bytes)
+from .indexio import shard_range  # noqa: F401  (defined beside shard_bounds, which `reshard` cuts by without importing torch)
 
 
-def shard_range(rank: int, world: int, n_structures: int):
-    """contiguous, balanced id ranges; the union over ranks is [0, n_structures)"""
-    base, rem = divmod(n_structures, world)
-    lo = rank * base + min(rank, rem)
-    return lo, lo + base + (1 if rank < rem else 0)
 
 
 def rank_hits(recs: np.ndarray, top_n: int | None = None) -> np.ndarray:

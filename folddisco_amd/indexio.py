@@ -237,18 +237,11 @@ def verify_host(value, hashes, offsets, n_structures: int, first_id: int = 0, th
     return VerifyReport.from_c(r)
 
 
-def check_index_files(prefix: str) -> list:
-    """what can be said about an index's four files without decoding a posting: -> a list of complaints, empty if there is none.
-    chunk_size of PREFIX.type must equal the rows of PREFIX.lookup: `index` and `update` write it so, and so does the reference
-    (build_index.rs:133, 218: the number of input paths, one .lookup row each)."""
+def check_value_offset_pair(prefix: str) -> list:
+    """PREFIX and PREFIX.offset (both present) against each other without decoding a posting: the offset file's header against its own size, its
+    last offset against the value file's size -> a list of complaints"""
     bad = []
-    for ext in ("", ".offset", ".lookup", ".type"):
-        if not os.path.isfile(prefix + ext):
-            bad.append(f"{prefix}{ext} not found")
-    if bad:
-        return bad
     osz, vsz = os.path.getsize(prefix + ".offset"), os.path.getsize(prefix)
-    H = None
     if osz < 16:
         bad.append(f"{prefix}.offset: {osz} bytes, shorter than an empty table (16)")
     else:
@@ -262,6 +255,12 @@ def check_index_files(prefix: str) -> list:
                 end = int(np.frombuffer(f.read(8), np.uint64)[0])
                 if end != vsz:
                     bad.append(f"{prefix}: {vsz} bytes, the last offset of {prefix}.offset is {end}")
+    return bad
+
+
+def check_lookup_type(prefix: str):
+    """PREFIX.lookup and PREFIX.type (both present): row k starts with id k, chunk_size equals the rows -> (complaints, rows)"""
+    bad = []
     n_rows, rows_ok = 0, True
     with open(prefix + ".lookup") as f:
         for line in f:
@@ -280,7 +279,20 @@ def check_index_files(prefix: str) -> list:
             bad.append(f"{prefix}.type: no integer chunk_size")
         elif cs != n_rows:
             bad.append(f"{prefix}.type: chunk_size = {cs}, {prefix}.lookup has {n_rows} rows")
-    return bad
+    return bad, n_rows
+
+
+def check_index_files(prefix: str) -> list:
+    """what can be said about an index's four files without decoding a posting: -> a list of complaints, empty if there is none.
+    chunk_size of PREFIX.type must equal the rows of PREFIX.lookup: `index` and `update` write it so, and so does the reference
+    (build_index.rs:133, 218: the number of input paths, one .lookup row each)."""
+    bad = []
+    for ext in ("", ".offset", ".lookup", ".type"):
+        if not os.path.isfile(prefix + ext):
+            bad.append(f"{prefix}{ext} not found")
+    if bad:
+        return bad
+    return check_value_offset_pair(prefix) + check_lookup_type(prefix)[0]
 
 
 def merge_subindices(parts):
@@ -305,3 +317,44 @@ def merge_subindices(parts):
     for p in (ov, oh, oo):
         L.fdgpu_free(p)
     return v, h, o
+
+
+def shard_range(rank: int, world: int, n_structures: int):
+    """contiguous, balanced id ranges; the union over ranks is [0, n_structures)"""
+    base, rem = divmod(n_structures, world)
+    lo = rank * base + min(rank, rem)
+    return lo, lo + base + (1 if rank < rem else 0)
+
+
+def shard_bounds(world: int, n_structures: int) -> np.ndarray:
+    """the world + 1 cut points of shard_range: shard r of a sharded build or a `reshard` holds the ids [bounds[r], bounds[r + 1])"""
+    return np.array([shard_range(r, world, n_structures)[0] for r in range(world)] + [n_structures], dtype=np.uint64)
+
+
+def split_host(value, hashes, offsets, bounds, first_id: int = 0, threads: int = 1):
+    """the cut of an index by structure id range on host arrays (fdgpu_split_host: no context, no device), the inverse of merge_subindices:
+    -> list of (value, hashes, offsets), part r with the ids in [bounds[r], bounds[r + 1]) unchanged"""
+    value = np.ascontiguousarray(value, dtype=np.uint8)
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(hashes) + 1:
+        raise ValueError(f"offsets: {len(hashes) + 1} entries expected, got {len(offsets)}")
+    b = np.ascontiguousarray(bounds, dtype=np.uint64)
+    n = len(b) - 1
+    if b.ndim != 1 or n < 0:
+        raise ValueError("bounds: a 1-d array of n_parts + 1 ids expected")
+    L = _lib.load()
+    ov, oh, oo = (u8p * max(n, 1))(), (u32p * max(n, 1))(), (u64p * max(n, 1))()
+    vl, nh = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+    rc = L.fdgpu_split_host(hashes.ctypes.data_as(u32p), offsets.ctypes.data_as(u64p), len(hashes), value.ctypes.data_as(u8p), len(value), int(first_id),
+                            n, b.ctypes.data_as(u64p), max(int(threads), 1), ov, vl.ctypes.data_as(u64p), oh, oo, nh.ctypes.data_as(u64p))
+    if rc != 0:
+        raise ValueError(f"fdgpu_split_host failed ({rc}): bounds must ascend from first_id (1 to 64 parts) and cover every id of the index")
+    parts = []
+    for r in range(n):
+        V, H = int(vl[r]), int(nh[r])
+        parts.append((np.ctypeslib.as_array(ov[r], shape=(max(V, 1),))[:V].copy(), np.ctypeslib.as_array(oh[r], shape=(max(H, 1),))[:H].copy(),
+                      np.ctypeslib.as_array(oo[r], shape=(H + 1,)).copy()))
+        for p in (ov[r], oh[r], oo[r]):
+            L.fdgpu_free(p)
+    return parts

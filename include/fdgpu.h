@@ -511,6 +511,19 @@ int fdgpu_index_merge(fdgpu_ctx *ctx, const fdgpu_index *const *parts, uint64_t 
  * Appending is fdgpu_index_build of the new structures at first_id + (kept count) and fdgpu_index_merge of the two. */
 int fdgpu_index_remove(fdgpu_ctx *ctx, const fdgpu_index *ix, const uint8_t *keep, uint64_t n_keep, fdgpu_index **out);
 
+/* Cut a resident index by structure id range, ids unchanged: the inverse of fdgpu_index_merge.  bounds[0 .. n_parts] ascend,
+ * bounds[0] == first_id, bounds[n_parts] == first_id + n_structures (equal neighbours: an empty part), 1 <= n_parts <= 64; anything else is
+ * FDGPU_EINVAL with nothing allocated.  out[r] holds, for every hash, the ids in [bounds[r], bounds[r+1]) (a hash without one is absent), with
+ * first_id = bounds[r], n_structures = bounds[r+1] - bounds[r], exact posting counts and per-list last ids: byte-identical to fdgpu_index_build
+ * over those structures with first_id = bounds[r], and fdgpu_index_merge of the parts in order gives `ix` back.  `ix` stays valid.  A decoded
+ * id outside the index's range is FDGPU_EINVAL; on any error every part is destroyed and out[] is all NULL. */
+int fdgpu_index_split(fdgpu_ctx *ctx, const fdgpu_index *ix, uint32_t n_parts, const uint64_t *bounds, fdgpu_index **out /* [n_parts] */);
+/* The same cut on host arrays (the payload of PREFIX.offset and PREFIX), n_threads host threads over slot ranges (0 = 1).  No device.
+ * Every out_* has n_parts entries; the arrays are released with fdgpu_free (out_offsets[r] has out_n_hashes[r] + 1 entries). */
+int fdgpu_split_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes, const uint8_t *value, uint64_t value_len, uint64_t first_id,
+                     uint32_t n_parts, const uint64_t *bounds, uint32_t n_threads, uint8_t **out_value, uint64_t *out_value_len,
+                     uint32_t **out_hashes, uint64_t **out_offsets, uint64_t *out_n_hashes);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
