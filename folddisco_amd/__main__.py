@@ -1,4 +1,4 @@
-"""`python -m folddisco_amd index|query|update|verify|reshard …` — the reference's two hot-path subcommands (and `update`, `verify` and `reshard`, which it lacks) with its flag names and defaults
+"""`python -m folddisco_amd index|query|update|verify|reshard|merge …` — the reference's two hot-path subcommands (and `update`, `verify`, `reshard` and `merge`, which it lacks) with its flag names and defaults
 (src/cli/main.rs:26-110, src/cli/workflows/build_index.rs:64-241, src/cli/workflows/query_pdb.rs:144-519), driving the
 GPU path through the C ABI.  Structure order = lexicographic path order (the reference uses readdir order, which is
 filesystem dependent; SURVEY §7 hard part 3).  Only the default PDBTrRosetta encoding is supported; input is PDB or mmCIF, optionally gzip."""
@@ -478,6 +478,113 @@ def cmd_reshard(a):
               f"shard files of a count other than {W} are left as they are", file=sys.stderr)
 
 
+def _merge_plan(a):
+    """everything `merge` decides before it opens a device: -> (lookup rows per input, type text of the first input, Foldcomp-built?).  Status 2
+    for missing or unreadable files, status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
+    from folddisco_amd import indexio
+    if not 2 <= len(a.index) <= 64:
+        sys.exit(f"[FAIL] merge: {len(a.index)} input(s) given, 2 to 64 are joined in one call")
+    if not a.output:
+        sys.exit("[FAIL] merge: -o/--output is required")
+    if os.path.abspath(a.output) in [os.path.abspath(p) for p in a.index]:
+        sys.exit(f"[FAIL] merge: the output {a.output} is one of the inputs")
+    for p in a.index:
+        for ext in INDEX_FILES:
+            if not os.path.isfile(p + ext):
+                print(f"[FAIL] {p}{ext} not found", file=sys.stderr)
+                sys.exit(2)
+    try:
+        bad = [b for p in a.index for b in indexio.check_index_files(p)]
+        rows = [indexio.read_lookup_rows(p + ".lookup") for p in a.index]
+        texts = []
+        for p in a.index:
+            with open(p + ".type") as f:
+                texts.append(f.read())
+    except (OSError, ValueError, UnicodeDecodeError) as e:
+        print(f"[FAIL] merge: unreadable input ({e})", file=sys.stderr)
+        sys.exit(2)
+    if bad:
+        print("[FAIL] index files are inconsistent: " + "; ".join(bad))
+        sys.exit(1)
+    key = indexio.check_joinable(texts)
+    if key is not None:
+        print(f"[FAIL] merge: the inputs' .type files differ in {key}: indices are joined only if they were built with the same settings"
+              + (" from the same kind of input" if key in ("input_format", "foldcomp_db") else ""))
+        sys.exit(1)
+    total = sum(len(r) for r in rows)
+    if total > 0xffffffff:
+        print(f"[FAIL] merge: {total} structures in all, structure ids are 32 bits")
+        sys.exit(1)
+    return rows, texts[0], indexio.load_type(a.index[0] + ".type").get("input_format") == "FCZDB"
+
+
+def cmd_merge(a):
+    """`merge`: indices that were built separately (each with ids from 0) joined into one, byte for byte what `index` writes over the first
+    input's structures in their order followed by the second's and so on.  Every input is loaded, moved to the running structure count
+    (fdgpu_index_rebase) and released; the moved parts are concatenated per hash on the device (fdgpu_index_merge), or with --host both steps run
+    on the CPU (fdgpu_rebase_host, fdgpu_merge_subindices; no device is opened).  No structure file is read.  The four files are written under
+    temporary names and renamed at the end."""
+    from folddisco_amd import indexio
+    rows, type_text, fczdb = _merge_plan(a)
+    counts = [len(r) for r in rows]
+    S, out = sum(counts), a.output
+    try:
+        if a.host:
+            parts, first = [], 0
+            for p, n in zip(a.index, counts):
+                v, h, o = indexio.read_index_files(p)
+                if a.verify:
+                    _stop_if_unsound(indexio.verify_host(v, h, o, n, threads=a.threads), p)
+                parts.append(indexio.rebase_host(v, h, o, 0, first, n, threads=a.threads) if first else (v, h, o))
+                first += n
+            v, h, o = indexio.merge_subindices(parts)
+            del parts
+            if a.verify:
+                _stop_if_unsound(indexio.verify_host(v, h, o, S, threads=a.threads), "the joined index; nothing was written")
+            stats = (len(h), int(np.count_nonzero(v < 128)), len(v))      # a posting ends at every byte without the continuation bit
+            save = lambda prefix: indexio.write_index_files(prefix, v, h, o)
+        else:
+            import folddisco_amd as fd
+            ctx = fd.Context(a.device)
+            parts, first = [], 0
+            for p, n in zip(a.index, counts):
+                v, h, o = indexio.read_index_files(p)
+                ix = fd.FolddiscoIndex.load(ctx, h, o, v, n)
+                del v, h, o
+                if a.verify:                     # before the rebase or the merge uses its offsets as addresses
+                    _stop_if_unsound(ix.verify(), p)
+                parts.append(ix.rebase(first) if first else ix)      # the loaded index is released once its moved copy exists
+                del ix
+                first += n
+            whole = fd.FolddiscoIndexSet(parts).merge()
+            del parts
+            if a.verify:
+                _stop_if_unsound(whole.verify(), "the joined index; nothing was written")
+            stats = (whole.num_hashes, whole.num_postings, whole.value_len)
+            save = whole.save
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] merge: {e}", file=sys.stderr)
+        sys.exit(2 if isinstance(e, OSError) else 1)
+    tmp = f"{out}.merge-tmp{os.getpid()}"
+    try:
+        save(tmp)
+        with open(tmp + ".lookup", "w", newline="") as f:
+            f.writelines(indexio.join_lookup_rows(rows, keep_db_keys=fczdb))
+        with open(tmp + ".type", "w") as f:
+            f.write(indexio.update_type_text(type_text, S))
+        for ext in INDEX_FILES:
+            os.replace(tmp + ext, out + ext)
+    finally:
+        for ext in INDEX_FILES:
+            if os.path.exists(tmp + ext):
+                os.remove(tmp + ext)
+    print(f"[OK] {out}: {len(a.index)} inputs, {S} structures, lists / postings / bytes: {stats[0]} / {stats[1]} / {stats[2]}")
+    if a.verbose:
+        tids = [r.rstrip("\n").split("\t")[1] for rs in rows for r in rs]
+        print(f"[INFO] joined {', '.join(f'{p} ({n})' for p, n in zip(a.index, counts))} on the {'host' if a.host else 'device'}; "
+              f"{len(tids) - len(set(tids))} duplicate tid(s) across the inputs, kept as they are", file=sys.stderr)
+
+
 def cmd_query(a):
     import folddisco_amd as fd
     from folddisco_amd import indexio, query, structure
@@ -678,6 +785,14 @@ def main(argv=None):
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("--verify", action="store_true", help="check what was loaded and every part, each with its own id range, before anything is written (see `verify`)")
     pr.add_argument("-v", "--verbose", action="store_true")
+    pm = sub.add_parser("merge")                                     # indices built separately -> one index (no counterpart in the reference)
+    pm.add_argument("-i", "--index", nargs="+", required=True, help="2 to 64 single (unsharded) index prefixes, joined in the order given")
+    pm.add_argument("-o", "--output", default="", help="output prefix (required, none of the inputs)")
+    pm.add_argument("--host", action="store_true", help="rebase and merge on the CPU (no device is opened)")
+    pm.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    pm.add_argument("--device", type=int, default=0)
+    pm.add_argument("--verify", action="store_true", help="check every loaded input and the joined index before anything is written (see `verify`)")
+    pm.add_argument("-v", "--verbose", action="store_true")
     pa = sub.add_parser("analyze")                                   # src/cli/workflows/analyze.rs:19-40 (summary branch)
     pa.add_argument("-i", "--index", required=True)
     pa.add_argument("-p", "--pdbs", default=None)
@@ -713,6 +828,9 @@ def main(argv=None):
         return
     if a.cmd == "reshard":
         cmd_reshard(a)
+        return
+    if a.cmd == "merge":
+        cmd_merge(a)
         return
     if a.cmd == "index":
         if a.mmap_on_disk and a.verbose:

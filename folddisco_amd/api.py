@@ -270,6 +270,14 @@ class FolddiscoIndex:
         self.ctx.check(self.ctx.L.fdgpu_index_split(self.ctx.h, self.h, n, _ptr(b, u64p), out))
         return [FolddiscoIndex(self.ctx, C.c_void_p(out[r]), int(b[r + 1] - b[r]), int(b[r])) for r in range(n)]
 
+    def rebase(self, first_id: int) -> "FolddiscoIndex":
+        """this index moved to the ids first_id .. first_id + n_structures - 1 (fdgpu_index_rebase): a new resident index that equals a build over
+        the same structures with that first_id.  Indices built separately, each from id 0, are joined by rebasing every one to the running
+        structure count and FolddiscoIndexSet(parts).merge(); this index stays valid"""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.fdgpu_index_rebase(self.ctx.h, self.h, int(first_id), C.byref(h)))
+        return FolddiscoIndex(self.ctx, h, self.n_structures, int(first_id))
+
     # ---- one on-disk index from N ranks (fd_shard_index.hip; SURVEY §8e row 2, Option A)
     def range_bounds(self, n_ranges: int) -> np.ndarray:
         """n_ranges - 1 ascending hash values cutting this index into ranges of about equal posting bytes"""

@@ -1,5 +1,5 @@
 // fd_postings.h — the posting-list byte format, stated once for the encoder (k_index.hip), the device merge (k_merge.hip), the removal
-// (k_prune.hip), the split (k_split.hip) and the host merge (fdgpu_merge_subindices).
+// (k_prune.hip), the split (k_split.hip), the rebase (k_rebase.hip) and the host merge (fdgpu_merge_subindices).
 //
 // A posting list is the ascending ids of the structures that hold one hash, as LEB128 varints (7-bit groups, least significant first; bit 7
 // set = another byte follows; 0 is one 0x00 byte; a u32 takes at most five bytes; codec of indextable.rs:93-99, 397-418).  The first varint

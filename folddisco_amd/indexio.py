@@ -358,3 +358,62 @@ def split_host(value, hashes, offsets, bounds, first_id: int = 0, threads: int =
         for p in (ov[r], oh[r], oo[r]):
             L.fdgpu_free(p)
     return parts
+
+
+def rebase_host(value, hashes, offsets, first_id: int, new_first_id: int, n_structures: int, threads: int = 1):
+    """an index moved to the ids new_first_id .. new_first_id + n_structures - 1 on host arrays (fdgpu_rebase_host: no context, no device):
+    -> (value, hashes, offsets), what a build over the same structures with first_id = new_first_id gives.  Raises ValueError with the library's
+    code in it: -4 (FDGPU_ERANGE) for ids beyond 32 bits or a list of 4 GiB, -1 (FDGPU_EINVAL) for a damaged index"""
+    value = np.ascontiguousarray(value, dtype=np.uint8)
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(hashes) + 1:
+        raise ValueError(f"offsets: {len(hashes) + 1} entries expected, got {len(offsets)}")
+    L = _lib.load()
+    ov, oh, oo = u8p(), u32p(), u64p()
+    vl = C.c_uint64()
+    rc = L.fdgpu_rebase_host(hashes.ctypes.data_as(u32p), offsets.ctypes.data_as(u64p), len(hashes), value.ctypes.data_as(u8p), len(value), int(first_id),
+                             int(new_first_id), int(n_structures), max(int(threads), 1), C.byref(ov), C.byref(vl), C.byref(oh), C.byref(oo))
+    if rc != 0:
+        raise ValueError(f"fdgpu_rebase_host failed ({rc}): " + ("the new id range or a list exceeds 32 bits" if rc == -4 else
+                         "the index is damaged or holds first ids outside [first_id, first_id + n_structures)"))
+    H = len(hashes)
+    v = np.ctypeslib.as_array(ov, shape=(max(vl.value, 1),))[: vl.value].copy()
+    h = np.ctypeslib.as_array(oh, shape=(max(H, 1),))[:H].copy()
+    o = np.ctypeslib.as_array(oo, shape=(H + 1,)).copy()
+    for p in (ov, oh, oo):
+        L.fdgpu_free(p)
+    return v, h, o
+
+
+def join_lookup_rows(list_of_rows, keep_db_keys: bool):
+    """the rows of PREFIX.lookup after a join of indices (`merge`): the inputs' rows in the order given, tid, nres and plddt verbatim, the id
+    renumbered densely across the inputs; the db_key column renumbered with it for file-built indices (there it equals the id) and kept for
+    Foldcomp-built ones (its database key) -- the convention of update_lookup_rows"""
+    out, i = [], 0
+    for rows in list_of_rows:
+        for row in rows:
+            p = row.rstrip("\n").split("\t")
+            p[0] = str(i)
+            if len(p) > 4 and not keep_db_keys:
+                p[4] = str(i)
+            out.append("\t".join(p) + "\n")
+            i += 1
+    return out
+
+
+def _type_lines(text: str) -> dict:
+    """key -> the whole line of a PREFIX.type text (lines without '=' are ignored, like load_type)"""
+    return {line.split("=", 1)[0].strip(): line.rstrip("\n") for line in text.splitlines() if "=" in line}
+
+
+def check_joinable(type_texts):
+    """can the indices with these PREFIX.type texts be joined?  Every line but chunk_size must be the same text in all of them (hash type, bins,
+    grid width, input format, foldcomp_db, ...): -> the key of the first line that disagrees with the first text (in the first text's order, then
+    keys only a later text has), or None"""
+    first, others = _type_lines(type_texts[0]), [_type_lines(t) for t in type_texts[1:]]
+    keys = list(first) + list(dict.fromkeys(k for o in others for k in o if k not in first))
+    for k in keys:
+        if k != "chunk_size" and any(first.get(k) != o.get(k) for o in others):
+            return k
+    return None

@@ -143,7 +143,8 @@ int fdgpu_index_export(fdgpu_ctx *ctx, const fdgpu_index *ix, uint8_t **value, u
 int fdgpu_index_load(fdgpu_ctx *ctx, const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes,
                      const uint8_t *value, uint64_t value_len, uint64_t n_structures, fdgpu_index **out);
 /* an uploaded index that is one shard of a database (structures first_id .. first_id + n_structures - 1, as written by a sharded
- * build): tells scoring and fdgpu_index_merge where the shard's ids start (0 after fdgpu_index_load) */
+ * build): tells scoring and fdgpu_index_merge where the shard's ids start (0 after fdgpu_index_load).  This only LABELS the index: not a byte
+ * of it changes, the ids inside the lists must already be the absolute ones.  fdgpu_index_rebase REWRITES the lists for another id range. */
 int fdgpu_index_set_first_id(fdgpu_index *ix, uint64_t first_id);
 void fdgpu_index_destroy(fdgpu_index *ix);
 uint64_t fdgpu_index_num_hashes(const fdgpu_index *ix);
@@ -523,6 +524,25 @@ int fdgpu_index_split(fdgpu_ctx *ctx, const fdgpu_index *ix, uint32_t n_parts, c
 int fdgpu_split_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes, const uint8_t *value, uint64_t value_len, uint64_t first_id,
                      uint32_t n_parts, const uint64_t *bounds, uint32_t n_threads, uint8_t **out_value, uint64_t *out_value_len,
                      uint32_t **out_hashes, uint64_t **out_offsets, uint64_t *out_n_hashes);
+
+/* Move a resident index to another id range: *out is a new resident index over the same structures with ids new_first_id ..
+ * new_first_id + n_structures - 1, byte-identical to fdgpu_index_build over those structures with first_id = new_first_id (the first varint of
+ * every list re-encoded, everything behind it moved), with the same hashes and posting count.  Rebase + fdgpu_index_merge joins indices that
+ * were built separately, each with ids from 0; rebase to 0 of an fdgpu_index_split part makes the part a stand-alone index.  Per-list last ids:
+ * shifted with the lists when `ix` carries them (a following fdgpu_index_merge then needs no decode pass); an index from fdgpu_index_load carries
+ * none and neither does its rebased copy, exactly as if it had been loaded (merge, remove and split derive them on first use).  `ix` stays valid;
+ * new_first_id == first_id gives a copy, an index without hashes an empty index (offsets == [0]).
+ * FDGPU_ERANGE with nothing allocated when new_first_id + n_structures exceeds 32 bits (the limit of fdgpu_index_build and
+ * fdgpu_index_set_first_id), FDGPU_ERANGE for a list that would reach 4 GiB, FDGPU_EINVAL for a damaged index (offsets that do not ascend inside
+ * the value bytes, a first varint that leaves its list, a first id outside [first_id, first_id + n_structures)): all found before a byte is
+ * written.  On any error *out is NULL. */
+int fdgpu_index_rebase(fdgpu_ctx *ctx, const fdgpu_index *ix, uint64_t new_first_id, fdgpu_index **out);
+/* The same move on host arrays (the payload of PREFIX.offset and PREFIX), n_threads host threads over slot ranges (0 = 1).  No device.  Same
+ * bytes and same error codes as the device form (and FDGPU_EINVAL when first_id + n_structures exceeds 32 bits); the three arrays are released
+ * with fdgpu_free (out_offsets has n_hashes + 1 entries, out_hashes is a copy of hashes). */
+int fdgpu_rebase_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes, const uint8_t *value, uint64_t value_len, uint64_t first_id,
+                      uint64_t new_first_id, uint64_t n_structures, uint32_t n_threads, uint8_t **out_value, uint64_t *out_value_len,
+                      uint32_t **out_hashes, uint64_t **out_offsets);
 
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
