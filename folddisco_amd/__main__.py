@@ -1,4 +1,4 @@
-"""`python -m folddisco_amd index|query|update|verify|reshard|merge …` — the reference's two hot-path subcommands (and `update`, `verify`, `reshard` and `merge`, which it lacks) with its flag names and defaults
+"""`python -m folddisco_amd index|query|update|verify|reshard|merge|reorder …` — the reference's two hot-path subcommands (and `update`, `verify`, `reshard`, `merge` and `reorder`, which it lacks) with its flag names and defaults
 (src/cli/main.rs:26-110, src/cli/workflows/build_index.rs:64-241, src/cli/workflows/query_pdb.rs:144-519), driving the
 GPU path through the C ABI.  Structure order = lexicographic path order (the reference uses readdir order, which is
 filesystem dependent; SURVEY §7 hard part 3).  Only the default PDBTrRosetta encoding is supported; input is PDB or mmCIF, optionally gzip."""
@@ -585,6 +585,100 @@ def cmd_merge(a):
               f"{len(tids) - len(set(tids))} duplicate tid(s) across the inputs, kept as they are", file=sys.stderr)
 
 
+def _reorder_plan(a):
+    """everything `reorder` decides before it opens a device: -> (lookup rows, new_id, Foldcomp-built?).  Status 2 for missing or unreadable files,
+    status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
+    from folddisco_amd import indexio
+    if (a.by is None) == (a.order is None):
+        sys.exit("[FAIL] reorder: give exactly one of --by KEY and --order FILE")
+    if a.by is not None and a.by not in indexio.ORDER_KEYS:
+        sys.exit(f"[FAIL] reorder: unknown --by key '{a.by}' (one of {', '.join(indexio.ORDER_KEYS)})")
+    need = [a.index + ext for ext in INDEX_FILES] + ([a.order] if a.order is not None else [])
+    for f in need:
+        if not os.path.isfile(f):
+            print(f"[FAIL] {f} not found", file=sys.stderr)
+            sys.exit(2)
+    try:
+        bad = indexio.check_index_files(a.index)
+        rows = indexio.read_lookup_rows(a.index + ".lookup")
+        fczdb = indexio.load_type(a.index + ".type").get("input_format") == "FCZDB"
+        order_tids = None
+        if a.order is not None:
+            with open(a.order, newline="") as f:
+                order_tids = [line.rstrip("\r\n") for line in f]
+            while order_tids and not order_tids[-1]:      # blank lines at the end of the file
+                order_tids.pop()
+    except (OSError, ValueError, UnicodeDecodeError) as e:
+        print(f"[FAIL] reorder: unreadable input ({e})", file=sys.stderr)
+        sys.exit(2)
+    if bad:
+        print("[FAIL] index files are inconsistent: " + "; ".join(bad))
+        sys.exit(1)
+    try:
+        new_id = indexio.order_from_lookup(rows, by=a.by, descending=a.desc, order_tids=order_tids)
+    except ValueError as e:
+        print(f"[FAIL] reorder: {e}")
+        sys.exit(1)
+    return rows, new_id, fczdb
+
+
+def cmd_reorder(a):
+    """`reorder`: the index at PREFIX with its structures in another order (--by tid|nres|plddt [--desc]: PREFIX.lookup sorted by one column,
+    stably; --order FILE: one tid per line), byte for byte what `index` writes over the structures in the new order.  Every posting list is
+    decoded, mapped, put back in ascending order and re-encoded on the device (fdgpu_index_permute), or with --host on the CPU
+    (fdgpu_permute_host; no device is opened).  No structure file is read.  PREFIX.type is copied unchanged; the four files are written under
+    temporary names and renamed at the end."""
+    import shutil
+    from folddisco_amd import indexio
+    rows, new_id, fczdb = _reorder_plan(a)
+    S, out = len(rows), a.output or a.index
+    try:
+        v, h, o = indexio.read_index_files(a.index)
+        before = len(v)
+        if a.host:
+            if a.verify:
+                _stop_if_unsound(indexio.verify_host(v, h, o, S, threads=a.threads), a.index)
+            v, h, o = indexio.permute_host(v, h, o, new_id, threads=a.threads)
+            if a.verify:
+                _stop_if_unsound(indexio.verify_host(v, h, o, S, threads=a.threads), "the reordered index; nothing was written")
+            stats = (len(h), int(np.count_nonzero(v < 128)), len(v))      # a posting ends at every byte without the continuation bit
+            save = lambda prefix: indexio.write_index_files(prefix, v, h, o)
+        else:
+            import folddisco_amd as fd
+            ctx = fd.Context(a.device)
+            src = fd.FolddiscoIndex.load(ctx, h, o, v, S)
+            del v, h, o
+            if a.verify:                             # before the permute uses its offsets and ids as addresses
+                _stop_if_unsound(src.verify(), a.index)
+            ix = src.permute(new_id)
+            del src
+            if a.verify:
+                rep = ix.verify()
+                _stop_if_unsound(rep, "the reordered index; nothing was written")
+            stats = (ix.num_hashes, ix.num_postings, ix.value_len)
+            save = ix.save
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] reorder: {e}", file=sys.stderr)
+        sys.exit(2 if isinstance(e, OSError) else 1)
+    tmp = f"{out}.reorder-tmp{os.getpid()}"
+    try:
+        save(tmp)
+        with open(tmp + ".lookup", "w", newline="") as f:
+            f.writelines(indexio.permute_lookup_rows(rows, new_id, keep_db_keys=fczdb))
+        shutil.copyfile(a.index + ".type", tmp + ".type")
+        for ext in INDEX_FILES:
+            os.replace(tmp + ext, out + ext)
+    finally:
+        for ext in INDEX_FILES:
+            if os.path.exists(tmp + ext):
+                os.remove(tmp + ext)
+    moved = int(np.count_nonzero(new_id != np.arange(S, dtype=np.uint32)))
+    print(f"[OK] {out}: {S} structures reordered ({moved} moved), lists / postings / bytes: {stats[0]} / {stats[1]} / {stats[2]}")
+    if a.verbose:
+        print(f"[INFO] reordered {a.index} {'by ' + a.by + (' (descending)' if a.desc else '') if a.by else 'as ' + a.order + ' says'} on the "
+              f"{'host' if a.host else 'device'}; value bytes {before} -> {stats[2]}", file=sys.stderr)
+
+
 def cmd_query(a):
     import folddisco_amd as fd
     from folddisco_amd import indexio, query, structure
@@ -793,6 +887,17 @@ def main(argv=None):
     pm.add_argument("--device", type=int, default=0)
     pm.add_argument("--verify", action="store_true", help="check every loaded input and the joined index before anything is written (see `verify`)")
     pm.add_argument("-v", "--verbose", action="store_true")
+    po = sub.add_parser("reorder")                                   # the index's structures in another order (no counterpart in the reference)
+    po.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
+    po.add_argument("--by", default=None, help="sort PREFIX.lookup by one column: tid (byte string), nres or plddt (numeric); stable")
+    po.add_argument("--order", default=None, help="text file with one tid per line: the new order; it must name every tid of PREFIX.lookup exactly once")
+    po.add_argument("--desc", action="store_true", help="--by in descending order (ties keep their old order)")
+    po.add_argument("-o", "--output", default="", help="output prefix (default: rewrite PREFIX in place)")
+    po.add_argument("--host", action="store_true", help="reorder on the CPU (no device is opened)")
+    po.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    po.add_argument("--device", type=int, default=0)
+    po.add_argument("--verify", action="store_true", help="check the loaded index and the result before anything is written (see `verify`)")
+    po.add_argument("-v", "--verbose", action="store_true")
     pa = sub.add_parser("analyze")                                   # src/cli/workflows/analyze.rs:19-40 (summary branch)
     pa.add_argument("-i", "--index", required=True)
     pa.add_argument("-p", "--pdbs", default=None)
@@ -831,6 +936,9 @@ def main(argv=None):
         return
     if a.cmd == "merge":
         cmd_merge(a)
+        return
+    if a.cmd == "reorder":
+        cmd_reorder(a)
         return
     if a.cmd == "index":
         if a.mmap_on_disk and a.verbose:

@@ -278,6 +278,18 @@ class FolddiscoIndex:
         self.ctx.check(self.ctx.L.fdgpu_index_rebase(self.ctx.h, self.h, int(first_id), C.byref(h)))
         return FolddiscoIndex(self.ctx, h, self.n_structures, int(first_id))
 
+    def permute(self, new_id) -> "FolddiscoIndex":
+        """this index with its structures in another order (fdgpu_index_permute): new_id[k] = new local position of the structure now at local
+        position k, a permutation of 0 .. n_structures - 1.  A new resident index over the same id range that equals a build over the same
+        structures taken in the new order; this index stays valid"""
+        p = np.asarray(new_id)
+        if p.ndim != 1 or len(p) != self.n_structures or (len(p) and (p.dtype.kind not in "iu" or p.min() < 0 or p.max() > 0xffffffff)):
+            raise ValueError(f"new_id: {self.n_structures} positions 0 .. n - 1 expected")
+        p = np.ascontiguousarray(p, dtype=np.uint32)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.fdgpu_index_permute(self.ctx.h, self.h, _ptr(p, u32p), len(p), C.byref(h)))
+        return FolddiscoIndex(self.ctx, h, self.n_structures, self.first_id)
+
     # ---- one on-disk index from N ranks (fd_shard_index.hip; SURVEY §8e row 2, Option A)
     def range_bounds(self, n_ranges: int) -> np.ndarray:
         """n_ranges - 1 ascending hash values cutting this index into ranges of about equal posting bytes"""

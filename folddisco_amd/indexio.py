@@ -386,6 +386,101 @@ def rebase_host(value, hashes, offsets, first_id: int, new_first_id: int, n_stru
     return v, h, o
 
 
+def permute_host(value, hashes, offsets, new_id, first_id: int = 0, threads: int = 1):
+    """an index with its structures in another order on host arrays (fdgpu_permute_host: no context, no device): new_id[k] = new local position of
+    the structure now at local position k, a permutation of 0 .. n - 1 -> (value, hashes, offsets), what a build over the same structures taken in
+    the new order gives.  Raises ValueError with the library's code in it: -1 (FDGPU_EINVAL) for a new_id that is no permutation, an id outside
+    [first_id, first_id + n) or a damaged index, -4 (FDGPU_ERANGE) for a list of 4 GiB"""
+    value = np.ascontiguousarray(value, dtype=np.uint8)
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(hashes) + 1:
+        raise ValueError(f"offsets: {len(hashes) + 1} entries expected, got {len(offsets)}")
+    p = np.asarray(new_id)
+    if p.ndim != 1 or (len(p) and (p.dtype.kind not in "iu" or p.min() < 0 or p.max() > 0xffffffff)):
+        raise ValueError("fdgpu_permute_host failed (-1): new_id must be a 1-d array of positions 0 .. n - 1")
+    p = np.ascontiguousarray(p, dtype=np.uint32)
+    L = _lib.load()
+    ov, oh, oo = u8p(), u32p(), u64p()
+    vl = C.c_uint64()
+    rc = L.fdgpu_permute_host(hashes.ctypes.data_as(u32p), offsets.ctypes.data_as(u64p), len(hashes), value.ctypes.data_as(u8p), len(value), int(first_id),
+                              p.ctypes.data_as(u32p), len(p), max(int(threads), 1), C.byref(ov), C.byref(vl), C.byref(oh), C.byref(oo))
+    if rc != 0:
+        raise ValueError(f"fdgpu_permute_host failed ({rc}): " + ("a list exceeds 32 bits" if rc == -4 else
+                         "new_id is not a permutation of 0 .. n - 1, or the index is damaged or holds ids outside [first_id, first_id + n)"))
+    H = len(hashes)
+    v = np.ctypeslib.as_array(ov, shape=(max(vl.value, 1),))[: vl.value].copy()
+    h = np.ctypeslib.as_array(oh, shape=(max(H, 1),))[:H].copy()
+    o = np.ctypeslib.as_array(oo, shape=(H + 1,)).copy()
+    for q in (ov, oh, oo):
+        L.fdgpu_free(q)
+    return v, h, o
+
+
+def permute_lookup_rows(rows, new_id, keep_db_keys: bool):
+    """the rows of PREFIX.lookup after a reorder: row k moves to position new_id[k], tid, nres and plddt verbatim, the id renumbered 0 .. n - 1; the
+    db_key column renumbered with it for a file-built index (there it equals the id) and kept for a Foldcomp-built one (its database key) -- the
+    convention of update_lookup_rows"""
+    p = np.asarray(new_id, dtype=np.int64)
+    n = len(rows)
+    if p.ndim != 1 or len(p) != n or (n and not np.array_equal(np.sort(p), np.arange(n))):
+        raise ValueError(f"new_id: a permutation of 0 .. {n - 1} expected")
+    out = [None] * n
+    for row, i in zip(rows, p.tolist()):
+        c = row.rstrip("\n").split("\t")
+        c[0] = str(i)
+        if len(c) > 4 and not keep_db_keys:
+            c[4] = str(i)
+        out[i] = "\t".join(c) + "\n"
+    return out
+
+
+ORDER_KEYS = ("tid", "nres", "plddt")
+
+
+def order_from_lookup(rows, by=None, descending: bool = False, order_tids=None) -> np.ndarray:
+    """the ordering rules of `reorder` -> new_id (new_id[k] = new position of row k).  by: rows sorted by one column of PREFIX.lookup, tid as a byte
+    string, nres and plddt numerically; the sort is stable (ties keep their old order) and descending reverses the key, not the tie order.
+    order_tids: the tids in their new order; ValueError unless it names every tid of the rows exactly once and the rows hold no tid twice.
+    Exactly one of by / order_tids must be given."""
+    if (by is None) == (order_tids is None):
+        raise ValueError("give exactly one of a sort key (--by) and a list of tids (--order)")
+    n = len(rows)
+    cols = [r.rstrip("\n").split("\t") for r in rows]
+    if any(len(c) < 4 for c in cols):
+        raise ValueError("a .lookup row has fewer than four columns")
+    if by is not None:
+        if by not in ORDER_KEYS:
+            raise ValueError(f"unknown sort key '{by}' (one of {', '.join(ORDER_KEYS)})")
+        if by == "tid":
+            keys = [c[1].encode("utf-8", "surrogateescape") for c in cols]
+        elif by == "nres":
+            keys = [int(c[2]) for c in cols]
+        else:
+            keys = [float(c[3]) for c in cols]
+        ranked = sorted(range(n), key=lambda k: keys[k], reverse=descending)      # stable; reverse=True keeps ties in their old order too
+        new_id = np.empty(n, np.uint32)
+        new_id[np.asarray(ranked, dtype=np.int64)] = np.arange(n, dtype=np.uint32)
+        return new_id
+    where = {}
+    for k, c in enumerate(cols):
+        if c[1] in where:
+            raise ValueError(f"tid '{c[1]}' appears twice in .lookup (rows {where[c[1]] + 1} and {k + 1}): an order by tid would be ambiguous")
+        where[c[1]] = k
+    new_id = np.full(n, n, np.int64)
+    for pos, t in enumerate(order_tids):
+        k = where.get(t)
+        if k is None:
+            raise ValueError(f"the order names tid '{t}' (line {pos + 1}), which .lookup does not hold")
+        if new_id[k] != n:
+            raise ValueError(f"the order names tid '{t}' twice (lines {int(new_id[k]) + 1} and {pos + 1})")
+        new_id[k] = pos
+    if len(order_tids) != n:
+        missing = next(cols[k][1] for k in range(n) if new_id[k] == n)
+        raise ValueError(f"the order names {len(order_tids)} of {n} tids; '{missing}' is missing")
+    return new_id.astype(np.uint32)
+
+
 def join_lookup_rows(list_of_rows, keep_db_keys: bool):
     """the rows of PREFIX.lookup after a join of indices (`merge`): the inputs' rows in the order given, tid, nres and plddt verbatim, the id
     renumbered densely across the inputs; the db_key column renumbered with it for file-built indices (there it equals the id) and kept for

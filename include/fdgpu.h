@@ -544,6 +544,23 @@ int fdgpu_rebase_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t 
                       uint64_t new_first_id, uint64_t n_structures, uint32_t n_threads, uint8_t **out_value, uint64_t *out_value_len,
                       uint32_t **out_hashes, uint64_t **out_offsets);
 
+/* Reorder the structures of a resident index: new_id[k] = new local position of the structure now at local position k, a permutation of
+ * 0 .. n - 1 with n == fdgpu_index_num_structures(ix).  *out is a new resident index over the same id range [first_id, first_id + n) that equals,
+ * byte for byte, fdgpu_index_build over the same structures taken in the new order: the same hashes and posting count, every list decoded, mapped
+ * (id -> first_id + new_id[id - first_id]), put back in ascending order and re-encoded, so offsets, value length and the per-list last ids (always
+ * carried by the result) are new.  `ix` stays valid.  FDGPU_EINVAL, on the host and before any device work, when n differs from the index's number
+ * of structures or new_id is not a permutation (a value >= n, a repeated value); FDGPU_EINVAL when a list holds an id outside
+ * [first_id, first_id + n) or the offsets do not ascend inside the value bytes; FDGPU_ERANGE for a list of 4 GiB or more.  On any error *out is
+ * NULL and nothing stays allocated.  Test switches, read per call, that only lower a class boundary of csrc/k_permute.hip: FDGPU_PERM_SORT_BYTES
+ * (longest list sorted in LDS by one wavefront), FDGPU_PERM_LDS_BITS (most structures whose bitmap is kept in LDS). */
+int fdgpu_index_permute(fdgpu_ctx *ctx, const fdgpu_index *ix, const uint32_t *new_id, uint64_t n, fdgpu_index **out);
+/* The same reorder on host arrays (the payload of PREFIX.offset and PREFIX), n_threads host threads over slot ranges (0 = 1); n is the number of
+ * structures.  No device.  Same bytes and same error codes as the device form (and FDGPU_EINVAL when first_id + n exceeds 32 bits or a varint is
+ * malformed); the three arrays are released with fdgpu_free (out_offsets has n_hashes + 1 entries, out_hashes is a copy of hashes). */
+int fdgpu_permute_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes, const uint8_t *value, uint64_t value_len, uint64_t first_id,
+                       const uint32_t *new_id, uint64_t n, uint32_t n_threads, uint8_t **out_value, uint64_t *out_value_len,
+                       uint32_t **out_hashes, uint64_t **out_offsets);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
