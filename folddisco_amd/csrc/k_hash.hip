@@ -5,9 +5,9 @@
 // hashable, CA-CA distance <= cutoff.
 //
 // Mapping: one 64-lane wavefront (= one 64-thread workgroup) per (structure, 64-residue i-tile).
-// Lane l owns residue i = tile_start + l and walks j over the whole structure with
-// wave-uniform (scalar) loads of CA_j, so the CA-distance filter costs ~15 VALU issues per 64
-// pair tests.  Only ~25 % of the tests pass, so running the ~700-instruction descriptor under
+// Lane l owns residue i = tile_start + l and walks j over the structure; CA_j is wave-uniform per
+// step, so the CA-distance filter costs a handful of VALU issues per 64 pair tests (fd_filter_block:
+// ~7 in the index build's kernels).  Only ~25 % of the tests pass, so running the ~700-instruction descriptor under
 // that exec mask would idle 3/4 of the lanes; instead the passing (i, j) are compacted with
 // ballot + mbcnt prefix into a per-wave LDS queue and the descriptor is evaluated in full
 // 64-entry drains (one queue entry per lane).  No MFMA: this is f32/f64 VALU + irregular gather.
@@ -122,12 +122,81 @@ __global__ __launch_bounds__(256) void k_frames(fd_batch_view B, uint32_t n_res,
     frames[r] = F;
 }
 
-// wave-uniform lane index -> v_readlane_b32 (SGPR broadcast), not the ds_bpermute a general __shfl becomes
-__device__ __forceinline__ float bcast_lane(float v, uint32_t k) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)k));
+// ------------------------------------------------------------------ the distance filter of the unordered-pair kernels
+// ONE place for the predicate "j > i, both hashable, !(d2 > d2_max)" of k_pair_count2, k_pair_count_msd and k_pair_emit2: what the count pass
+// counts is what the emit pass emits by construction.  fd_filter_block walks one block of 64 partners j = jb .. jb + 63 for the 64-residue
+// i-tile of the wavefront (lane l = residue i0 + l) and hands `step` the pass ballots of two partners at a time.  Per 64 x 2 pair tests it
+// issues 8 packed f32 instructions and 2 compares, nothing else on the vector unit:
+//   * CA_j is staged in LDS once per block (three planes of 64 floats) and read back with uniform-address ds_read2_b32 — no v_readlane;
+//   * two partners per step in packed f32: v_pk_add_f32 (negated source), v_pk_mul_f32, v_pk_add_f32 — every half rounds like the scalar
+//     instruction and the order is fd_dist2's ((dx·dx + dy·dy) + dz·dz), so each d2 has the bits fd_dist2 gives; NaN passes, as there;
+//   * "i valid and hashable" is one ballot per work item (vim); "j > i" is a scalar mask: (1 << k) - 1 in the work item's first block
+//     (jb == i0, the partners ARE the tile), all ones in every later one; both are ANDed to the compare's result in scalar registers;
+//   * the block is cut into RUNS of partners of one kind — unhashable, or hashable of one residue type (TYPES; without it all hashable
+//     partners are one kind) — by one ballot per block.  A run of unhashable partners is skipped in one scalar step, the run's type is one
+//     v_readlane per run, and the loop ends at the last hashable partner (64 - clz of the hashable ballot).  In amino-acid order
+//     (k_frames_perm) a block holds ~4 runs; in chain order a run may be one partner long, which is correct and only no faster.
+// step(k, t, m0, m1, last): partners jb + k and jb + k + 1 of type t, m0 / m1 = the lanes whose pair passes (m1 = 0 where the run ends at
+// an odd count: the second half of the packed step is computed and masked, there is no separate tail step); last = nothing follows in
+// this work item (last_block's final step; it is made even where the last block has no hashable partner, with m0 = m1 = 0, so that a
+// caller can flush).  run_end(t) follows the last step of every run.  s_cj: 3 * FD_WAVE + 1 floats of LDS (the odd word is read, masked,
+// by a step at k = 63).  One wavefront per workgroup: LDS accesses execute in order, fd_wave_lds_fence() keeps the compiler from reordering.
+typedef float fd_f2 __attribute__((ext_vector_type(2)));
+#define FD_NOT_HASHABLE 0x100u
+
+__device__ __forceinline__ bool fd_lane_of(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }   // the lane's bit of a wave-uniform mask, no VALU
+
+template <bool TYPES, class Step, class RunEnd>
+__device__ __forceinline__ void fd_filter_block(const fd_batch_view &B, float d2_max, const fd_v3 &cai, uint64_t vim, uint32_t i0, uint32_t jb, uint32_t r1,
+                                                float *s_cj, Step &&step, RunEnd &&run_end) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t jl = jb + lane;
+    fd_v3 cj = {0.f, 0.f, 0.f};
+    uint32_t kind = FD_NOT_HASHABLE;
+    if (jl < r1) {
+        cj = fd_load3(B.ca_xyz, jl);
+        if (B.hash_ok[jl]) kind = TYPES ? (uint32_t)B.aa[jl] : 0u;
+    }
+    fd_wave_lds_fence();
+    s_cj[lane] = cj.x; s_cj[FD_WAVE + lane] = cj.y; s_cj[2 * FD_WAVE + lane] = cj.z;
+    fd_wave_lds_fence();
+    const uint64_t okm = __ballot(kind != FD_NOT_HASHABLE);
+    const uint64_t starts = __ballot(kind != (uint32_t)__shfl_up((int)kind, 1, FD_WAVE)) | 1ull;   // bit k: a run starts at partner k
+    const bool last_block = jb + FD_WAVE >= r1;
+    const uint32_t nk = okm ? 64u - (uint32_t)__builtin_clzll(okm) : 0u;
+    const uint32_t nkf = (last_block && nk == 0) ? 1u : nk;      // an empty last block still makes the one step that carries `last`
+    const bool first = jb == i0;
+    const fd_f2 ax = {cai.x, cai.x}, ay = {cai.y, cai.y}, az = {cai.z, cai.z};
+    uint32_t k = 0;
+    while (k < nkf) {
+        const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)kind, (int)k);
+        const uint64_t rest = (starts >> k) >> 1;
+        uint32_t ke = rest ? k + 1u + (uint32_t)__builtin_ctzll(rest) : (uint32_t)FD_WAVE;
+        ke = ke < nkf ? ke : nkf;
+        const bool run_last = last_block && ke >= nkf;
+        const bool dead = t == FD_NOT_HASHABLE;
+        if (dead && !run_last) { k = ke; continue; }
+        const uint64_t vr = dead ? 0ull : vim;
+        uint64_t gt = first ? (1ull << k) - 1ull : ~0ull;      // lanes with i < jb + k
+        do {
+            const fd_f2 xj = {s_cj[k], s_cj[k + 1]}, yj = {s_cj[FD_WAVE + k], s_cj[FD_WAVE + k + 1]}, zj = {s_cj[2 * FD_WAVE + k], s_cj[2 * FD_WAVE + k + 1]};
+            const fd_f2 dx = ax - xj, dy = ay - yj, dz = az - zj;
+            const fd_f2 d2 = (dx * dx + dy * dy) + dz * dz;
+            const uint64_t gt1 = gt << 1 | 1ull;
+            const uint64_t m0 = __ballot(!(d2.x > d2_max)) & vr & gt;
+            const uint64_t m1 = (k + 1u < ke) ? (__ballot(!(d2.y > d2_max)) & vr & gt1) : 0ull;
+            gt = gt1 << 1 | 1ull;
+            const uint32_t k0 = k;
+            k += 2;
+            step(k0, t, m0, m1, run_last && k >= ke);
+        } while (k < ke);
+        k = ke;
+        run_end(t);
+    }
 }
 
 __global__ __launch_bounds__(FD_WAVE) void k_pair_count2(fd_batch_view B, fd_hash_consts C, uint32_t *__restrict__ counts) {
+    __shared__ float s_cj[3 * FD_WAVE + 1];
     uint32_t w = fd_xcd_remap(blockIdx.x, B.n_work);
     if (w >= B.n_work) return;
     const uint32_t s = B.wi_struct[w];
@@ -137,23 +206,13 @@ __global__ __launch_bounds__(FD_WAVE) void k_pair_count2(fd_batch_view B, fd_has
     const bool vi = i < r1 && B.hash_ok[i];
     fd_v3 cai = {0.f, 0.f, 0.f};
     if (vi) cai = fd_load3(B.ca_xyz, i);
-    uint32_t cnt = 0;
-    // j is walked in blocks of 64: one coalesced load per block (lane l holds CA of j = jb + l), then the 64
-    // candidates are broadcast lane by lane with v_readlane — no per-j memory latency in the filter loop
-    for (uint32_t jb = i0; jb < r1; jb += FD_WAVE) {
-        const uint32_t jl = jb + threadIdx.x;
-        const bool jin = jl < r1;
-        fd_v3 cj = {0.f, 0.f, 0.f};
-        if (jin) cj = fd_load3(B.ca_xyz, jl);
-        const uint64_t okm = __ballot(jin && B.hash_ok[jl]);
-        const uint32_t nj = (r1 - jb) < FD_WAVE ? (r1 - jb) : FD_WAVE;
-        for (uint32_t k = 0; k < nj; ++k) {
-            if (!((okm >> k) & 1ull)) continue;  // wave-uniform
-            fd_v3 caj = {bcast_lane(cj.x, k), bcast_lane(cj.y, k), bcast_lane(cj.z, k)};
-            float d2 = fd_dist2(cai, caj);
-            cnt += (vi && (jb + k) > i && !(d2 > C.d2_max)) ? 2u : 0u;
-        }
-    }
+    const uint64_t vim = __ballot(vi);
+    uint32_t cnt = 0;      // unordered pairs of this lane's residue; every one is two keys
+    for (uint32_t jb = i0; jb < r1; jb += FD_WAVE)
+        fd_filter_block<false>(B, C.d2_max, cai, vim, i0, jb, r1, s_cj,
+                               [&](uint32_t, uint32_t, uint64_t m0, uint64_t m1, bool) { cnt += (fd_lane_of(m0) ? 1u : 0u) + (fd_lane_of(m1) ? 1u : 0u); },
+                               [](uint32_t) {});
+    cnt *= 2u;
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, FD_WAVE);
     if (threadIdx.x == 0 && cnt) atomicAdd(&counts[s], cnt);
 }
@@ -197,10 +256,12 @@ __global__ __launch_bounds__(256) void k_frames_perm(fd_batch_view B, fd_frame *
 }
 
 // count pass of the MSD build: counts[bucket * S + s] += keys of structure s that fall into the bucket (both orientations of every
-// unordered pair: (aa_i, aa_j >> 4) and (aa_j, aa_i >> 4)).  The forward keys are two per-lane counters (aa_j is wave-uniform per step), the
-// reverse keys two population counts of the pass ballot per step; everything meets in forty LDS counters.  B = the permuted view.
+// unordered pair: (aa_i, aa_j >> 4) and (aa_j, aa_i >> 4)).  The partners come in runs of one residue type (fd_filter_block; amino-acid order
+// makes them ~16 long), so ONE per-lane pass counter per run serves both orientations: at the end of the run it goes to the lane's forward
+// counter of the run's half (c_lo / c_hi) and, as the reverse keys of bucket (aa_j, aa_i >> 4), into the forty LDS counters.  B = the permuted view.
 __global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_hash_consts C, uint32_t *__restrict__ counts) {
     __shared__ uint32_t s_cnt[FD_WAVE];
+    __shared__ float s_cj[3 * FD_WAVE + 1];
     uint32_t w = fd_xcd_remap(blockIdx.x, B.n_work);
     if (w >= B.n_work) return;
     const uint32_t s = B.wi_struct[w];
@@ -214,34 +275,17 @@ __global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_
     if (vi) { cai = fd_load3(B.ca_xyz, i); aai = B.aa[i]; }
     s_cnt[lane] = 0;
     __syncthreads();
-    // forward keys (aa_i, aa_j >> 4): two counters per lane, the partner's type is wave-uniform per step.  Reverse keys (aa_j, aa_i >> 4): the
-    // partners are visited in amino-acid order, so aa_j changes ~20 times per structure — ONE more counter per lane for the current
-    // partner type, flushed into the LDS bucket counters when the type changes (a wave-uniform, rare branch)
-    uint32_t c_lo = 0, c_hi = 0, rev = 0, cur_aa = 0xffffffffu;
+    const uint64_t vim = __ballot(vi);
+    uint32_t c_lo = 0, c_hi = 0, run = 0;
     const uint32_t hi_i = aai >> 4;
-    for (uint32_t jb = i0; jb < r1; jb += FD_WAVE) {
-        const uint32_t jl = jb + lane;
-        const bool jin = jl < r1;
-        fd_v3 cj = {0.f, 0.f, 0.f};
-        uint32_t aj = 0;
-        if (jin) { cj = fd_load3(B.ca_xyz, jl); aj = B.aa[jl]; }
-        const uint64_t okm = __ballot(jin && B.hash_ok[jl]);
-        const uint32_t nj = (r1 - jb) < FD_WAVE ? (r1 - jb) : FD_WAVE;
-        for (uint32_t k = 0; k < nj; ++k) {
-            if (!((okm >> k) & 1ull)) continue;  // wave-uniform
-            fd_v3 caj = {bcast_lane(cj.x, k), bcast_lane(cj.y, k), bcast_lane(cj.z, k)};
-            const uint32_t aaj = (uint32_t)__builtin_amdgcn_readlane((int)aj, (int)k);
-            if (aaj != cur_aa) {      // wave-uniform
-                if (rev) atomicAdd(&s_cnt[cur_aa * 2u + hi_i], rev);
-                rev = 0; cur_aa = aaj;
-            }
-            const float d2 = fd_dist2(cai, caj);
-            const uint32_t pass = (vi && (jb + k) > i && !(d2 > C.d2_max)) ? 1u : 0u;
-            rev += pass;
-            if (aaj >= 16u) c_hi += pass; else c_lo += pass;
-        }
-    }
-    if (rev) atomicAdd(&s_cnt[cur_aa * 2u + hi_i], rev);
+    for (uint32_t jb = i0; jb < r1; jb += FD_WAVE)
+        fd_filter_block<true>(B, C.d2_max, cai, vim, i0, jb, r1, s_cj,
+                              [&](uint32_t, uint32_t, uint64_t m0, uint64_t m1, bool) { run += (fd_lane_of(m0) ? 1u : 0u) + (fd_lane_of(m1) ? 1u : 0u); },
+                              [&](uint32_t t) {      // t: wave-uniform; FD_NOT_HASHABLE only with run == 0 in every lane
+                                  if (t >= 16u) c_hi += run; else c_lo += run;
+                                  if (run) atomicAdd(&s_cnt[(t * 2u + hi_i) & (FD_WAVE - 1u)], run);
+                                  run = 0;
+                              });
     if (c_lo) atomicAdd(&s_cnt[aai * 2u], c_lo);
     if (c_hi) atomicAdd(&s_cnt[aai * 2u + 1u], c_hi);
     __syncthreads();
@@ -374,7 +418,8 @@ template <int TAB, bool IDS16, bool MSD, bool DT = false>
 __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_view B, const fd_frame *__restrict__ frames, fd_hash_consts C,
                                                         const uint64_t *__restrict__ seg_off, uint32_t *__restrict__ cursor,
                                                         uint32_t *__restrict__ keys, void *__restrict__ ids, uint32_t first_id) {
-    __shared__ uint32_t q[2 * FD_WAVE];
+    __shared__ uint32_t q[3 * FD_WAVE];      // a step queues up to 2 x 64 entries on top of the < 64 left by the drains before it
+    __shared__ float s_cj[3 * FD_WAVE + 1];
     __shared__ uint32_t tab[DT ? 64 + FD_DIST_NTHR + 1 : 64];   // [0,27) exact table (bit patterns), [32,59) the same with float thresholds for the speculative path,
                                                                  // DT: [64, 64 + FD_DIST_NTHR) the squared-distance breakpoints of the two distance fields
     uint32_t w = fd_xcd_remap(blockIdx.x, B.n_work);
@@ -406,46 +451,37 @@ __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_
         for (int k = 0; k < 5; ++k) s_fi[k * FD_WAVE + lane] = fp[k];
     }
     __shared__ uint32_t s_bc[MSD ? FD_WAVE : 1];
-    __shared__ uint64_t s_bb[MSD ? FD_WAVE : 1], s_boff[MSD ? FD_WAVE : 1];
+    __shared__ uint64_t s_bb[MSD ? FD_MSD_BUCKETS : 1], s_boff[MSD ? FD_MSD_BUCKETS : 1];      // forty of each: with 64 the workgroup passes 8 KB and the CU holds 19 of them, not 20
     if (MSD && lane < FD_MSD_BUCKETS) s_boff[lane] = seg_off[(uint64_t)lane * B.n_struct + s];      // where the structure's keys of every bucket start
     __syncthreads();
+    const uint64_t vim = __ballot(vi);
+    const uint32_t lane16 = lane << 16;
     uint32_t qn = 0;  // wave-uniform
-    // single drain site (two inlined copies of the descriptor code would not fit the I-cache); the queue is
-    // flushed on the last candidate. j is walked in blocks of 64: one coalesced load per block, then v_readlane
-    // broadcasts — no per-j memory latency in the filter loop.
+    // single drain site (two inlined copies of the descriptor code would not fit the I-cache): the two ballots of a step are queued one
+    // after the other in front of it, and the step that fd_filter_block marks `last` flushes what is left (up to three drains).
     for (uint32_t jb = i0; jb < r1; jb += FD_WAVE) {
-        const uint32_t jl = jb + lane;
-        const bool jin = jl < r1;
-        fd_v3 cj = {0.f, 0.f, 0.f};
-        if (jin) cj = fd_load3(B.ca_xyz, jl);
-        uint32_t aj = 0;
-        if (MSD && jin) aj = B.aa[jl];
-        const uint64_t okm = __ballot(jin && B.hash_ok[jl]);
-        const uint32_t nj = (r1 - jb) < FD_WAVE ? (r1 - jb) : FD_WAVE;
-        const bool last_block = jb + FD_WAVE >= r1;
-        for (uint32_t k = 0; k < nj; ++k) {
-            const bool last = last_block && k + 1 == nj;
-            if ((okm >> k) & 1ull) {  // wave-uniform
-                fd_v3 caj = {bcast_lane(cj.x, k), bcast_lane(cj.y, k), bcast_lane(cj.z, k)};
-                float d2 = fd_dist2(cai, caj);
-                const uint32_t j = jb + k;
-                bool pass = vi && j > i && !(d2 > C.d2_max);
-                uint64_t m = __ballot(pass);
-                if (m != 0) {
-                    // MSD: bits 22-26 = the partner's residue type (wave-uniform, a scalar OR)
-                    const uint32_t tag = MSD ? ((uint32_t)__builtin_amdgcn_readlane((int)aj, (int)k) << 22) | (j - r0) : (j - r0);
-                    if (pass) q[qn + fd_mbcnt(m)] = (lane << 16) | tag;
-                    qn += (uint32_t)__popcll(m);
+        const uint32_t jrel = jb - r0;
+        fd_filter_block<MSD>(B, C.d2_max, cai, vim, i0, jb, r1, s_cj,
+            [&](uint32_t k, uint32_t t, uint64_t m0, uint64_t m1, bool last) {
+                // queue entry: lane << 16 | partner (relative to the structure); MSD: bits 22-26 = the partner's residue type, the run's
+                const uint32_t tag = (MSD ? t << 22 : 0u) | (jrel + k);
+                if (m0) {
+                    if (fd_lane_of(m0)) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, qn))] = lane16 | tag;
+                    qn += (uint32_t)__popcll(m0);
                 }
-            }
-            while (qn >= FD_WAVE || (last && qn)) {   // on the last candidate up to two drains may be pending
-                fd_wave_lds_fence();
-                uint32_t n = qn < FD_WAVE ? qn : FD_WAVE;
-                qn -= n;
-                drain2<TAB, IDS16, MSD, DT>(B, frames, C, tab, q + qn, n, i0, r0, s, first_id + s, seg_off, cursor, keys, ids, s_fi, s_bc, s_bb, s_boff);
-                fd_wave_lds_fence();
-            }
-        }
+                if (m1) {
+                    if (fd_lane_of(m1)) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, qn))] = lane16 | (tag + 1u);
+                    qn += (uint32_t)__popcll(m1);
+                }
+                while (qn >= FD_WAVE || (last && qn)) {
+                    fd_wave_lds_fence();
+                    uint32_t n = qn < FD_WAVE ? qn : FD_WAVE;
+                    qn -= n;
+                    drain2<TAB, IDS16, MSD, DT>(B, frames, C, tab, q + qn, n, i0, r0, s, first_id + s, seg_off, cursor, keys, ids, s_fi, s_bc, s_bb, s_boff);
+                    fd_wave_lds_fence();
+                }
+            },
+            [](uint32_t) {});
     }
 }
 
