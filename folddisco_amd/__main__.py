@@ -1,4 +1,4 @@
-"""`python -m folddisco_amd index|query|update|verify|reshard|merge|reorder …` — the reference's two hot-path subcommands (and `update`, `verify`, `reshard`, `merge` and `reorder`, which it lacks) with its flag names and defaults
+"""`python -m folddisco_amd index|query|update|verify|reshard|merge|reorder|coords …` — the reference's two hot-path subcommands (and `update`, `verify`, `reshard`, `merge`, `reorder` and `coords`, which it lacks) with its flag names and defaults
 (src/cli/main.rs:26-110, src/cli/workflows/build_index.rs:64-241, src/cli/workflows/query_pdb.rs:144-519), driving the
 GPU path through the C ABI.  Structure order = lexicographic path order (the reference uses readdir order, which is
 filesystem dependent; SURVEY §7 hard part 3).  Only the default PDBTrRosetta encoding is supported; input is PDB or mmCIF, optionally gzip."""
@@ -59,6 +59,9 @@ def _shard_prefix(prefix, rank, world):
 def cmd_index(a):
     import folddisco_amd as fd
     from folddisco_amd import indexio, structure
+    if getattr(a, "coords", False) and int(os.environ.get("WORLD_SIZE", "1")) > 1:      # before any rank opens a device or parses a file
+        print("[FAIL] index --coords writes the coordinate store from one rank only: build the index as it is and run `coords -i PREFIX` afterwards")
+        sys.exit(1)
     rank, world, _dev = _init_dist(a)
     # an input that is a file is a Foldcomp database (build_index.rs:109-123): structures = its entries in key order, names from
     # DB.lookup, ids for the reader = database keys
@@ -86,7 +89,16 @@ def cmd_index(a):
     from concurrent.futures import ThreadPoolExecutor
     tid_pool = ThreadPoolExecutor(1)
     tids_f = tid_pool.submit(lambda: [indexio.parse_path_by_id_type(x, a.id) for x in paths])      # 20 ms of Python per 20,000 paths: under the ingest
-    parts, nres, plddt = _build_chunks(a, fd, structure, ctx, paths, 0, resident=True)
+    cw = None
+    if getattr(a, "coords", False):               # --coords: every parsed chunk goes to the store's section files as well (no second ingest)
+        cw = indexio.CoordWriter(prefix + ".coords")
+        a.coord_sink = cw.add
+    try:
+        parts, nres, plddt = _build_chunks(a, fd, structure, ctx, paths, 0, resident=True)
+    except BaseException:
+        if cw is not None:
+            cw.abort()
+        raise
     t0 = time.perf_counter()
     ix = _merge_resident(fd, parts)
     ctx.synchronize()
@@ -100,6 +112,10 @@ def cmd_index(a):
     indexio.save_type(prefix + ".type", len(paths), grid_width=a.grid, max_residue=a.max_residue, nbin_angle=a.angle, nbin_dist=a.distance, hash_type=HASH_TYPE_NAMES[a.hash_type], multiple_bins=a.multi,
                       **(dict(input_format="FCZDB", foldcomp_db=a.pdbs) if a.fc is not None else {}))
     T["export_write_s"] = time.perf_counter() - t0
+    if cw is not None:
+        t0 = time.perf_counter()
+        cw.close(indexio.index_stamp(prefix))
+        T["coords_s"] = time.perf_counter() - t0
     T["total_s"] = time.perf_counter() - t_all
     T["structures"] = len(paths)
     LAST_TIMINGS.clear()
@@ -137,10 +153,15 @@ REF_SKIP_MAX_RESIDUE = 65535
 
 def _ingest(a, structure, chunk, pos0):
     """native ingest of one chunk of the input (files, or entries pos0 ... of the Foldcomp database) + the reference's warnings"""
+    sink = getattr(a, "coord_sink", None)      # the coordinate store's writer, when one is being written (index --coords, update, coords)
     if a.fc is not None:
-        ps, nres_c, plddt_c, raw, ok = structure.read_packed(a.fc_keys[pos0:pos0 + len(chunk)], threads=a.threads, max_residue=REF_SKIP_MAX_RESIDUE, foldcomp=a.fc)
+        ps, nres_c, plddt_c, raw, ok, *lab = structure.read_packed(a.fc_keys[pos0:pos0 + len(chunk)], threads=a.threads, max_residue=REF_SKIP_MAX_RESIDUE, foldcomp=a.fc,
+                                                                   labels=sink is not None)
     else:
-        ps, nres_c, plddt_c, raw, ok = structure.read_packed(chunk, threads=a.threads, max_residue=REF_SKIP_MAX_RESIDUE)
+        ps, nres_c, plddt_c, raw, ok, *lab = structure.read_packed(chunk, threads=a.threads, max_residue=REF_SKIP_MAX_RESIDUE, labels=sink is not None)
+    if sink is not None:
+        from folddisco_amd import indexio
+        sink(indexio.CoordArrays(ps, lab[0]["chain"], lab[0]["resname_std"], lab[0]["serial"]))
     for k in np.nonzero(ok == 0)[0]:
         print(f"[WARN] {chunk[k]} could not be read. Skipping", file=sys.stderr)
     for k in np.nonzero(raw > REF_SKIP_MAX_RESIDUE)[0]:
@@ -235,6 +256,28 @@ def _cmd_index_sharded(a, fd, indexio, structure, paths, prefix, rank, world):
 INDEX_FILES = ("", ".offset", ".lookup", ".type")
 
 
+def _open_store(path, prefix, n_structures=None):
+    """PREFIX.coords for a command that is about to use it: a store the reader refuses (indexio.CoordStore.open: inconsistent, or its stamp disagrees
+    with the index files at `prefix`; prefix None skips the stamp) ends the command with status 1, an unreadable one with status 2"""
+    from folddisco_amd import indexio
+    try:
+        st = indexio.CoordStore.open(path, check_prefix=prefix)
+        if n_structures is not None and st.n_struct != n_structures:
+            raise indexio.CoordStoreError(f"{path} holds {st.n_struct} structures, the index {n_structures}")
+    except indexio.CoordStoreError as e:
+        print(f"[FAIL] coordinate store refused: {e}")
+        sys.exit(1)
+    except OSError as e:
+        print(f"[FAIL] {path}: unreadable ({e})", file=sys.stderr)
+        sys.exit(2)
+    return st
+
+
+def _tmp_stamp(tmp, n_rows):
+    """the stamp a store gets that is written beside index files still under their temporary names (they are renamed, not rewritten)"""
+    return n_rows, os.path.getsize(tmp), os.path.getsize(tmp + ".offset")
+
+
 def _update_plan(a):
     """everything `update` decides before it touches a device: the index's rows and settings, the keep mask, the files to append.
     Refusals exit with status 1 and change nothing."""
@@ -272,7 +315,8 @@ def _update_plan(a):
         add_paths = _load_paths(a.pdbs, a.recursive)
         if not add_paths:
             sys.exit(f"[FAIL] no structures under {a.pdbs}")
-    return dict(rows=rows, keep=keep, cfg=cfg, type_text=type_text, fczdb=fczdb, add_paths=add_paths)
+    store = _open_store(a.index + ".coords", a.index, len(rows)) if os.path.isfile(a.index + ".coords") else None      # a stale store is refused here
+    return dict(rows=rows, keep=keep, cfg=cfg, type_text=type_text, fczdb=fczdb, add_paths=add_paths, store=store)
 
 
 def cmd_update(a):
@@ -302,6 +346,26 @@ def cmd_update(a):
         del ix                                   # the loaded index is released once the pruned one exists
         ix = pruned
     rows = indexio.update_lookup_rows(plan["rows"], keep, keep_db_keys=plan["fczdb"])
+    out = a.output or a.index
+    tmp = f"{out}.update-tmp{os.getpid()}"
+    cw = None
+    if plan["store"] is not None:                # the store follows the index: the kept slices now, the added structures' arrays as they are parsed
+        cw = indexio.CoordWriter(tmp + ".coords")
+        try:
+            cw.add((plan["store"], None if n_kept == len(keep) else np.nonzero(keep)[0]))
+        except BaseException:
+            cw.abort()
+            raise
+        a.coord_sink = cw.add
+    try:
+        _update_rest(a, fd, indexio, structure, ctx, plan, ix, rows, add_paths, n_kept, keep, out, tmp, cw)
+    except BaseException:
+        if cw is not None:
+            cw.abort()
+        raise
+
+
+def _update_rest(a, fd, indexio, structure, ctx, plan, ix, rows, add_paths, n_kept, keep, out, tmp, cw):
     if add_paths:
         a.timings = {}
         parts, nres, plddt = _build_chunks(a, fd, structure, ctx, add_paths, n_kept, resident=True)
@@ -310,18 +374,19 @@ def cmd_update(a):
         rows += indexio.lookup_rows(n_kept, [indexio.parse_path_by_id_type(x, a.id) for x in add_paths], nres, plddt)
     if a.verify:                                 # the result, before anything is written
         _stop_if_unsound(ix.verify(), "the updated index; nothing was written")
-    out = a.output or a.index
-    tmp = f"{out}.update-tmp{os.getpid()}"
+    exts = INDEX_FILES + ((".coords",) if cw is not None else ())
     try:
         ix.save(tmp)
         with open(tmp + ".lookup", "w", newline="") as f:
             f.writelines(rows)
         with open(tmp + ".type", "w") as f:
             f.write(indexio.update_type_text(plan["type_text"], len(rows)))
-        for ext in INDEX_FILES:
+        if cw is not None:
+            cw.close(_tmp_stamp(tmp, len(rows)))
+        for ext in exts:
             os.replace(tmp + ext, out + ext)
     finally:
-        for ext in INDEX_FILES:
+        for ext in exts:
             if os.path.exists(tmp + ext):
                 os.remove(tmp + ext)
     if a.verbose:
@@ -364,6 +429,9 @@ def cmd_verify(a):
     device (fdgpu_index_verify) or with --host on the CPU (fdgpu_verify_host; no device is opened).  Exit status 0 / 1, 2 for unreadable input."""
     from folddisco_amd import indexio
     v, h, o, n = _verify_files(a.index)
+    if os.path.isfile(a.index + ".coords"):      # part of the file checks: header, sections, res_off, stamp
+        st = _open_store(a.index + ".coords", a.index, n)
+        print(f"[OK] {a.index}.coords: {st.n_struct} structures, {st.n_res} residues, stamp matches the index files")
     if a.host:
         rep = indexio.verify_host(v, h, o, n, threads=a.threads)
     else:
@@ -415,6 +483,8 @@ def cmd_reshard(a):
     srcs, S = _reshard_plan(a)
     V, W = a.from_, a.to
     out = a.output or a.index
+    # a store is checked against the single index's files only (--from 1); beside shards its stamp cannot be checked and it is copied as it is
+    store = _open_store(a.index + ".coords", a.index if V == 1 else None, S) if out != a.index and os.path.isfile(a.index + ".coords") else None
     try:
         loaded = [indexio.read_index_files(s) for s in srcs]
     except (OSError, ValueError) as e:
@@ -461,6 +531,12 @@ def cmd_reshard(a):
         for ext in side:
             shutil.copyfile(a.index + ext, tmp + ext)
             made.append((tmp + ext, out + ext))
+        if side and store is not None:           # the store covers the whole database: it goes with .lookup; its stamp is re-taken where a single index is written
+            if W == 1:
+                indexio.write_coords(tmp + ".coords", [(store, None)], _tmp_stamp(f"{tmp}.0", S))
+            else:
+                shutil.copyfile(a.index + ".coords", tmp + ".coords")
+            made.append((tmp + ".coords", out + ".coords"))
         for t, f in made:
             os.replace(t, f)
     finally:
@@ -511,6 +587,12 @@ def _merge_plan(a):
         print(f"[FAIL] merge: the inputs' .type files differ in {key}: indices are joined only if they were built with the same settings"
               + (" from the same kind of input" if key in ("input_format", "foldcomp_db") else ""))
         sys.exit(1)
+    have = [os.path.isfile(p + ".coords") for p in a.index]
+    if any(have) and not all(have):
+        print("[FAIL] merge: only some inputs have a coordinate store; without one: " + ", ".join(p for p, h in zip(a.index, have) if not h) +
+              " (run `coords -i PREFIX` on them, or remove the others' .coords files)")
+        sys.exit(1)
+    a.stores = [_open_store(p + ".coords", p, len(r)) for p, r in zip(a.index, rows)] if all(have) else None
     total = sum(len(r) for r in rows)
     if total > 0xffffffff:
         print(f"[FAIL] merge: {total} structures in all, structure ids are 32 bits")
@@ -566,16 +648,19 @@ def cmd_merge(a):
         print(f"[FAIL] merge: {e}", file=sys.stderr)
         sys.exit(2 if isinstance(e, OSError) else 1)
     tmp = f"{out}.merge-tmp{os.getpid()}"
+    exts = INDEX_FILES + ((".coords",) if a.stores else ())
     try:
         save(tmp)
         with open(tmp + ".lookup", "w", newline="") as f:
             f.writelines(indexio.join_lookup_rows(rows, keep_db_keys=fczdb))
         with open(tmp + ".type", "w") as f:
             f.write(indexio.update_type_text(type_text, S))
-        for ext in INDEX_FILES:
+        if a.stores:                             # the inputs' stores one after the other, like their .lookup rows
+            indexio.write_coords(tmp + ".coords", [(st, None) for st in a.stores], _tmp_stamp(tmp, S))
+        for ext in exts:
             os.replace(tmp + ext, out + ext)
     finally:
-        for ext in INDEX_FILES:
+        for ext in exts:
             if os.path.exists(tmp + ext):
                 os.remove(tmp + ext)
     print(f"[OK] {out}: {len(a.index)} inputs, {S} structures, lists / postings / bytes: {stats[0]} / {stats[1]} / {stats[2]}")
@@ -619,6 +704,7 @@ def _reorder_plan(a):
     except ValueError as e:
         print(f"[FAIL] reorder: {e}")
         sys.exit(1)
+    a.store = _open_store(a.index + ".coords", a.index, len(rows)) if os.path.isfile(a.index + ".coords") else None      # a stale store is refused here
     return rows, new_id, fczdb
 
 
@@ -661,15 +747,18 @@ def cmd_reorder(a):
         print(f"[FAIL] reorder: {e}", file=sys.stderr)
         sys.exit(2 if isinstance(e, OSError) else 1)
     tmp = f"{out}.reorder-tmp{os.getpid()}"
+    exts = INDEX_FILES + ((".coords",) if a.store is not None else ())
     try:
         save(tmp)
         with open(tmp + ".lookup", "w", newline="") as f:
             f.writelines(indexio.permute_lookup_rows(rows, new_id, keep_db_keys=fczdb))
         shutil.copyfile(a.index + ".type", tmp + ".type")
-        for ext in INDEX_FILES:
+        if a.store is not None:                  # position p of the result holds the structure that was at argsort(new_id)[p]
+            indexio.write_coords(tmp + ".coords", [(a.store, np.argsort(new_id, kind="stable"))], _tmp_stamp(tmp, S))
+        for ext in exts:
             os.replace(tmp + ext, out + ext)
     finally:
-        for ext in INDEX_FILES:
+        for ext in exts:
             if os.path.exists(tmp + ext):
                 os.remove(tmp + ext)
     moved = int(np.count_nonzero(new_id != np.arange(S, dtype=np.uint32)))
@@ -679,17 +768,99 @@ def cmd_reorder(a):
               f"{'host' if a.host else 'device'}; value bytes {before} -> {stats[2]}", file=sys.stderr)
 
 
+def _coords_plan(a):
+    """everything `coords` decides before it parses a structure: -> (keys or paths in id order, Foldcomp database or None, rows).  Status 2 for missing
+    or unreadable index files, status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
+    from folddisco_amd import indexio, structure
+    for ext in INDEX_FILES:
+        if not os.path.isfile(a.index + ext):
+            print(f"[FAIL] {a.index}{ext} not found", file=sys.stderr)
+            sys.exit(2)
+    try:
+        bad, n = indexio.check_lookup_type(a.index)
+        tids, _nres, _plddt, db_keys = indexio.load_lookup(a.index + ".lookup") if not bad else ([], None, None, None)
+        cfg = indexio.load_type(a.index + ".type") if not bad else {}
+    except (OSError, ValueError, IndexError, UnicodeDecodeError) as e:
+        print(f"[FAIL] {a.index}: unreadable ({e})", file=sys.stderr)
+        sys.exit(2)
+    if bad:
+        print("[FAIL] index files are inconsistent: " + "; ".join(bad))
+        sys.exit(1)
+    if cfg.get("input_format") == "FCZDB":       # the database the index names, else the prefix's X_foldcomp sibling — as `query` finds it
+        cands = [cfg.get("foldcomp_db", "")]
+        pfx = a.index[:-len("_folddisco")] if a.index.endswith("_folddisco") else a.index
+        cands += [pfx, pfx + "_foldcomp"]
+        dbp = next((c for c in cands if c and structure.is_foldcomp_db(c)), None)
+        if dbp is None:
+            print(f"[FAIL] coords: Foldcomp database of index {a.index} not found (tried {', '.join(c for c in cands if c)})")
+            sys.exit(1)
+        fc = structure.FoldcompDb(dbp)
+        known = set(int(k) for k in fc.keys)
+        missing = [str(int(k)) for k in db_keys if int(k) not in known]
+        what, items = "database keys", db_keys
+    else:
+        fc = None
+        items = [_resolve_tid(a.index, t) for t in tids]
+        missing = [p for p in items if not os.path.isfile(p)]
+        what = "structure files"
+    if missing:                                  # a store with silent holes would change results
+        print(f"[FAIL] coords: {len(missing)} of the {n} {what} {a.index}.lookup names are missing: " + ", ".join(missing[:10]) + (" ..." if len(missing) > 10 else ""))
+        sys.exit(1)
+    return items, fc, n
+
+
+def cmd_coords(a):
+    """`coords`: PREFIX.coords for an existing index (built here, by the reference or by a multi-rank run): the structures PREFIX.lookup names,
+    found as `query` finds them, parsed in chunks exactly as `index` parses them (a structure `index` skips keeps its slot with no residues) and
+    streamed through indexio.write_coords.  No device is opened."""
+    from folddisco_amd import indexio, structure
+    items, fc, n = _coords_plan(a)
+    out = a.output or a.index + ".coords"
+    a.fc, a.fc_keys = fc, (np.asarray(items, np.uint64) if fc is not None else None)
+    got = []
+    a.coord_sink = got.append
+
+    def pieces():
+        for c0 in range(0, n, a.chunk):
+            _ingest(a, structure, items[c0:c0 + a.chunk], c0)
+            yield got.pop()
+    indexio.write_coords(out, pieces(), lambda: indexio.index_stamp(a.index))
+    st = indexio.CoordStore.open(out, check_prefix=a.index)
+    print(f"[OK] {out}: {st.n_struct} structures, {st.n_res} residues, {os.path.getsize(out)} bytes")
+    if a.verbose:
+        print(f"[INFO] stamp: {', '.join(f'{k} = {v}' for k, v in zip(indexio.STAMP_FIELDS, st.stamp))}", file=sys.stderr)
+
+
+def _resolve_tid(index, t):
+    """a tid of PREFIX.lookup -> the structure file, like resolve_tid_path_from_index_prefix (controller/io.rs:488-528)"""
+    if os.path.isfile(t):
+        return t
+    cand = os.path.join(os.path.dirname(os.path.abspath(index)), t)
+    return cand if os.path.isfile(cand) else t
+
+
 def cmd_query(a):
     import folddisco_amd as fd
     from folddisco_amd import indexio, query, structure
     if not a.index:
         sys.exit("[FAIL] -i/--index is required")
+    if a.coords and a.no_coords:
+        sys.exit("[FAIL] --coords and --no-coords cannot be combined")
     rank, world, dev = _init_dist(a)
     if a.verify and world == 1:
         _verify_files(a.index)
-    ctx = fd.Context(a.device)
     tids, nres, plddt, db_keys = indexio.load_lookup(a.index + ".lookup")
     cfg = indexio.load_type(a.index + ".type")
+    # the coordinate store (PREFIX.coords, or --coords FILE) replaces the parse of every structure file; --no-coords keeps the parse.  A store the
+    # reader refuses ends the command here, before a device is opened: falling back to the files would hide that it is stale
+    store = None
+    store_path = a.coords or (a.index + ".coords" if os.path.isfile(a.index + ".coords") else "")
+    if store_path and not a.no_coords and not a.skip_match:
+        store = _open_store(store_path, a.index if world == 1 else None, len(tids))
+        if a.verbose:
+            print(f"[INFO] coordinates from {store_path}: {store.n_struct} structures, {store.n_res} residues" +
+                  ("" if world == 1 else "; sharded query: the stamp is that of the single index's files and is not checked"), file=sys.stderr)
+    ctx = fd.Context(a.device)
     shard = None
     lo, hi = 0, len(tids)
     if world > 1:
@@ -716,16 +887,12 @@ def cmd_query(a):
     else:
         queries = [(a.pdb, a.query, a.output)]
     # candidate coordinates: resolve tids like resolve_tid_path_from_index_prefix (controller/io.rs:488-528)
-    def resolve(t):
-        if os.path.isfile(t):
-            return t
-        cand = os.path.join(os.path.dirname(os.path.abspath(a.index)), t)
-        return cand if os.path.isfile(cand) else t
+    resolve = lambda t: _resolve_tid(a.index, t)
     db_structs, batch = None, None
     # an index built from a Foldcomp database reads the hit coordinates back from it by db_key (query_pdb.rs:321-343,
     # retrieve.rs:166-178); the database is the one the index names, else INDEX-PREFIX's X_foldcomp sibling (controller/io.rs:422-448)
     fc = None
-    if cfg.get("input_format") == "FCZDB" and not a.skip_match:
+    if cfg.get("input_format") == "FCZDB" and not a.skip_match and store is None:
         cands = [cfg.get("foldcomp_db", "")]
         pfx = a.index[:-len("_folddisco")] if a.index.endswith("_folddisco") else a.index
         cands += [pfx, pfx + "_foldcomp"]
@@ -733,7 +900,10 @@ def cmd_query(a):
         if dbp is None:
             sys.exit(f"[FAIL] Foldcomp database of index {a.index} not found (tried {', '.join(c for c in cands if c)})")
         fc = structure.FoldcompDb(dbp)
-    if not a.skip_match and fc is not None:
+    if store is not None:                        # this rank's id range [lo, hi) of the store: views of the mapping, no structure file is opened
+        batch = ctx.upload(store.slice(lo, hi).ps)
+        db_structs = store.structs(lo, hi)
+    elif not a.skip_match and fc is not None:
         db_structs, _ = structure.read_compact_structures(db_keys[lo:hi], threads=a.threads, foldcomp=fc)
         batch = ctx.upload(fd.PackedStructures.concat([s.as_item() for s in db_structs]))
     elif not a.skip_match:
@@ -804,6 +974,7 @@ def main(argv=None):
     pi.add_argument("-v", "--verbose", action="store_true")
     pi.add_argument("--device", type=int, default=0)
     pi.add_argument("--chunk", type=int, default=16384, help="structures per ingest step and GPU build call (the next chunk is parsed while this one is built; the sub-indices are merged on the device)")
+    pi.add_argument("--coords", action="store_true", help="write PREFIX.coords, the coordinate store `query` reads instead of the structure files, in the same pass (single rank)")
     pi.add_argument("--mmap-on-disk", action="store_true", help="accepted for the reference's command lines (indextable.rs:215-226,247: there the posting array is filled in a file-backed "
                     "mapping of PREFIX instead of anonymous memory, the files are the same): here the array is filled in HBM and streamed to PREFIX either way")
     pq = sub.add_parser("query")
@@ -849,6 +1020,8 @@ def main(argv=None):
     pq.add_argument("-o", "--output", default="")
     pq.add_argument("-v", "--verbose", action="store_true")
     pq.add_argument("--device", type=int, default=0)
+    pq.add_argument("--coords", default="", help="coordinate store to read the database's coordinates from (default: PREFIX.coords when it exists)")
+    pq.add_argument("--no-coords", action="store_true", help="parse the structure files PREFIX.lookup names even when a coordinate store exists")
     pq.add_argument("--verify", action="store_true", help="check the loaded index first (see `verify`) and stop with status 1 if it is damaged")
     pu = sub.add_parser("update")                                    # index update without a rebuild (no counterpart in the reference)
     pu.add_argument("-i", "--index", required=True)
@@ -898,6 +1071,12 @@ def main(argv=None):
     po.add_argument("--device", type=int, default=0)
     po.add_argument("--verify", action="store_true", help="check the loaded index and the result before anything is written (see `verify`)")
     po.add_argument("-v", "--verbose", action="store_true")
+    pc = sub.add_parser("coords")                                    # the coordinate store of an existing index (no counterpart in the reference)
+    pc.add_argument("-i", "--index", required=True)
+    pc.add_argument("-o", "--output", default="", help="file to write (default: PREFIX.coords)")
+    pc.add_argument("-t", "--threads", type=int, default=1, help="host threads of the structure ingest")
+    pc.add_argument("--chunk", type=int, default=16384, help="structures parsed per step")
+    pc.add_argument("-v", "--verbose", action="store_true")
     pa = sub.add_parser("analyze")                                   # src/cli/workflows/analyze.rs:19-40 (summary branch)
     pa.add_argument("-i", "--index", required=True)
     pa.add_argument("-p", "--pdbs", default=None)
@@ -939,6 +1118,9 @@ def main(argv=None):
         return
     if a.cmd == "reorder":
         cmd_reorder(a)
+        return
+    if a.cmd == "coords":
+        cmd_coords(a)
         return
     if a.cmd == "index":
         if a.mmap_on_disk and a.verbose:

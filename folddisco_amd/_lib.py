@@ -135,6 +135,9 @@ SYMBOLS = [
     ("fdgpu_batch_destroy", None, [VP]),
     ("fdgpu_batch_num_structures", C.c_uint64, [VP]),
     ("fdgpu_batch_num_residues", C.c_uint64, [VP]),
+    ("fdgpu_batch_select", C.c_int, [VP, VP, u32p, C.c_uint64, C.POINTER(VP)]),
+    ("fdgpu_batch_concat", C.c_int, [VP, C.POINTER(VP), C.c_uint64, C.POINTER(VP)]),
+    ("fdgpu_batch_export", C.c_int, [VP, VP, C.POINTER(BatchDesc)]),
     ("fdgpu_hash_batch", C.c_int, [VP, VP, C.POINTER(HashParams), C.c_int, C.POINTER(u32p), C.POINTER(u64p)]),
     ("fdgpu_index_build", C.c_int, [VP, VP, C.POINTER(HashParams), C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_index_export", C.c_int, [VP, VP, C.POINTER(u8p), u64p, C.POINTER(u32p), C.POINTER(u64p), u64p]),

@@ -148,6 +148,47 @@ class Batch:
     def __init__(self, ctx: Context, h, n_struct: int):
         self.ctx, self.h, self.n_struct = ctx, h, n_struct
 
+    # ---- the batch follows its index: index.remove(keep) ~ select(np.nonzero(keep)[0]), .permute(new_id) ~ select(np.argsort(new_id)),
+    # .split(bounds)[r] ~ select(range(bounds[r], bounds[r + 1])), FolddiscoIndexSet.merge() ~ Batch.concat(parts)
+    def select(self, ids) -> "Batch":
+        """a new resident batch whose structure k is structure ids[k] of this one (fdgpu_batch_select: a gather on the device, repeats allowed,
+        an empty ids gives an empty batch); this batch stays valid"""
+        a = np.asarray(ids)
+        if a.ndim != 1 or (len(a) and (a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 0xffffffff)):
+            raise ValueError("ids: a 1-d array of structure positions expected")
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.fdgpu_batch_select(self.ctx.h, self.h, _ptr(a, u32p), len(a), C.byref(h)))
+        return Batch(self.ctx, h, len(a))
+
+    @staticmethod
+    def concat(parts) -> "Batch":
+        """the parts one after the other as a new resident batch (fdgpu_batch_concat: 2 to 64 parts, device-to-device copies); the parts stay valid"""
+        parts = list(parts)
+        if not parts:
+            raise ValueError("concat: no parts")
+        ctx = parts[0].ctx
+        arr = (C.c_void_p * len(parts))(*[p.h for p in parts])
+        h = C.c_void_p()
+        ctx.check(ctx.L.fdgpu_batch_concat(ctx.h, arr, len(parts), C.byref(h)))
+        return Batch(ctx, h, sum(p.n_struct for p in parts))
+
+    def export(self) -> PackedStructures:
+        """the batch's arrays back on the host (fdgpu_batch_export) -> PackedStructures; cb_valid is None where the batch has none"""
+        d = BatchDesc()
+        L = self.ctx.L
+        self.ctx.check(L.fdgpu_batch_export(self.ctx.h, self.h, C.byref(d)))
+        S = int(d.n_struct)
+        off = np.ctypeslib.as_array(d.res_off, shape=(S + 1,)).copy()
+        R = int(off[-1])
+        take = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(dt, copy=True)
+        ps = PackedStructures(off, take(d.n_xyz, 3 * R, np.float32), take(d.ca_xyz, 3 * R, np.float32), take(d.cb_xyz, 3 * R, np.float32),
+                              take(d.aa, R, np.uint8), take(d.cb_valid, R, np.uint8) if d.cb_valid else None)
+        for p in (d.res_off, d.n_xyz, d.ca_xyz, d.cb_xyz, d.aa, d.cb_valid):
+            if p:
+                L.fdgpu_free(p)
+        return ps
+
     def __del__(self):
         try:
             if self.h and self.ctx.h:

@@ -310,7 +310,7 @@ extern "C" int fdgpu_last_timings(const fdgpu_ctx *c, const char **names, float 
 }
 
 // ---- batches ---------------------------------------------------------------------------------------------------
-static int build_work_items(fdgpu_ctx *c, fdgpu_batch *b) {
+int fd_build_work_items(fdgpu_ctx *c, fdgpu_batch *b, bool with_hash_ok) {
     // one work item per (structure, 64-residue i-tile)
     std::vector<uint32_t> ws, wi;
     std::vector<uint32_t> ro(b->n_struct + 1);
@@ -331,7 +331,7 @@ static int build_work_items(fdgpu_ctx *c, fdgpu_batch *b) {
         HIPCHK(c, hipMemcpyAsync(b->wi_i0, wi.data(), wi.size() * 4, hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(c, hipMalloc((void **)&b->hash_ok, std::max<uint64_t>(b->n_res, 1)));
-    fd_launch_hash_ok(b->aa, b->cb_valid, b->hash_ok, b->n_res, c->stream);
+    if (with_hash_ok) fd_launch_hash_ok(b->aa, b->cb_valid, b->hash_ok, b->n_res, c->stream);      // (a batch whose arrays are still to be filled: the caller launches it afterwards, k_batch.hip)
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors go out of scope
     return FDGPU_OK;
@@ -358,7 +358,7 @@ extern "C" int fdgpu_batch_upload(fdgpu_ctx *c, const fd_batch_desc *h, fdgpu_ba
         (rc = up((void **)&b->cb_xyz, h->cb_xyz, R * 12)) || (rc = up((void **)&b->aa, h->aa, R))) { fdgpu_batch_destroy(b); return rc; }
     if (h->cb_valid && (rc = up((void **)&b->cb_valid, h->cb_valid, R))) { fdgpu_batch_destroy(b); return rc; }
     (void)rb;
-    if ((rc = build_work_items(c, b))) { fdgpu_batch_destroy(b); return rc; }
+    if ((rc = fd_build_work_items(c, b))) { fdgpu_batch_destroy(b); return rc; }
     *out = b;
     return FDGPU_OK;
 }
@@ -375,7 +375,7 @@ extern "C" int fdgpu_batch_wrap_device(fdgpu_ctx *c, const fd_batch_desc *d, uin
     hipError_t e = hipMemcpy(b->h_res_off.data(), d->res_off, (d->n_struct + 1) * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { c->err = std::string("wrap_device: ") + hipGetErrorString(e); delete b; return FDGPU_EHIP; }
     if (b->h_res_off[d->n_struct] != total_residues) { c->err = "wrap_device: res_off[n] != total_residues"; delete b; return FDGPU_EINVAL; }
-    int rc = build_work_items(c, b);
+    int rc = fd_build_work_items(c, b);
     if (rc) { fdgpu_batch_destroy(b); return rc; }
     *out = b;
     return FDGPU_OK;

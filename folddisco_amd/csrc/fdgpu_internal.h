@@ -214,6 +214,10 @@ struct fdgpu_batch {
     }
 };
 
+// fdgpu_api.hip: res_off, the (structure, 64-residue tile) work items and hash_ok of a batch whose arrays and h_res_off are set; synchronises.
+// with_hash_ok = false leaves hash_ok allocated but unwritten, for a caller that fills aa / cb_valid afterwards (k_batch.hip)
+int fd_build_work_items(fdgpu_ctx *c, fdgpu_batch *b, bool with_hash_ok = true);
+
 #include <atomic>
 static inline uint64_t fd_next_index_uid() { static std::atomic<uint64_t> n{1}; return n.fetch_add(1); }
 struct fdgpu_index {

@@ -512,3 +512,277 @@ def check_joinable(type_texts):
         if k != "chunk_size" and any(first.get(k) != o.get(k) for o in others):
             return k
     return None
+
+
+# ---- PREFIX.coords: the database's coordinates beside its index (this project's own file) ----------------------------------
+# 64-byte header: magic FDCOORD1 | u32 version = 1 | u32 flags (bit 0: cb_valid present) | u64 n_struct | u64 n_res | stamp u64[3] (rows of
+# PREFIX.lookup, bytes of PREFIX, bytes of PREFIX.offset when the store was written) | zero padding.  Then, each on a 64-byte boundary:
+# res_off u64[S + 1] | n_xyz, ca_xyz, cb_xyz f32[3R] each | aa u8[R] | cb_valid u8[R] (flag bit 0) | resname_std u8[R] | chain u8[R] | serial u64[R].
+# Little-endian, section-major (an id range or one structure is one read per section), bytes verbatim from the ingest (fd_parsed).
+COORDS_MAGIC = b"FDCOORD1"
+COORDS_VERSION = 1
+COORDS_HEADER = 64
+COORDS_SECTIONS = (("res_off", np.uint64, None), ("n_xyz", np.float32, 3), ("ca_xyz", np.float32, 3), ("cb_xyz", np.float32, 3), ("aa", np.uint8, 1),
+                   ("cb_valid", np.uint8, 1), ("resname_std", np.uint8, 1), ("chain", np.uint8, 1), ("serial", np.uint64, 1))
+STAMP_FIELDS = ("lookup rows", "value file bytes", "offset file bytes")      # PREFIX.lookup, PREFIX, PREFIX.offset
+
+
+class CoordStoreError(ValueError):
+    """a PREFIX.coords file a reader refuses: inconsistent in itself, or written for other index files than the ones beside it"""
+
+
+def _pad64(n: int) -> int:
+    return (n + 63) & ~63
+
+
+def _coords_layout(S: int, R: int, with_cbv: bool):
+    """-> ({section: (byte offset, elements)}, file size)"""
+    pos, lay = COORDS_HEADER, {}
+    for name, dt, per in COORDS_SECTIONS:
+        if name == "cb_valid" and not with_cbv:
+            continue
+        n = S + 1 if per is None else per * R
+        lay[name] = (pos, n)
+        pos = _pad64(pos + n * np.dtype(dt).itemsize)
+    last = COORDS_SECTIONS[-1]
+    return lay, lay[last[0]][0] + lay[last[0]][1] * np.dtype(last[1]).itemsize      # no padding behind the last section
+
+
+def index_stamp(prefix: str):
+    """what a store remembers of the index files beside it: (rows of PREFIX.lookup, bytes of PREFIX, bytes of PREFIX.offset)"""
+    with open(prefix + ".lookup", "rb") as f:
+        rows = sum(chunk.count(b"\n") for chunk in iter(lambda: f.read(1 << 20), b""))
+    vp = prefix + ".value" if os.path.exists(prefix + ".value") else prefix
+    return rows, os.path.getsize(vp), os.path.getsize(prefix + ".offset")
+
+
+@dataclass
+class CoordArrays:
+    """a run of structures as flat arrays: the batch (PackedStructures) and the per-residue labels the result printer needs"""
+    ps: object              # api.PackedStructures
+    chain: np.ndarray       # u8 [R]
+    resname_std: np.ndarray  # u8 [R]
+    serial: np.ndarray      # u64 [R]
+
+
+class _StructView:
+    """one structure of a CoordStore as query.query_pdb reads it: views, nothing copied"""
+    __slots__ = ("ca_xyz", "chain", "serial")
+
+    def __init__(self, ca_xyz, chain, serial):
+        self.ca_xyz, self.chain, self.serial = ca_xyz, chain, serial
+
+    @property
+    def n(self) -> int:
+        return len(self.chain)
+
+
+class _LazyStructs:
+    """the structures [lo, hi) of a CoordStore as a sequence: len, truthiness, [k]; no per-structure or per-residue object exists before [k] asks"""
+
+    def __init__(self, store, lo, hi):
+        self.store, self.lo, self.hi = store, lo, hi
+
+    def __len__(self):
+        return self.hi - self.lo
+
+    def __bool__(self):
+        return self.hi > self.lo
+
+    def __getitem__(self, k):
+        k = int(k)
+        if k < 0:
+            k += len(self)
+        if not 0 <= k < len(self):
+            raise IndexError(k)
+        st = self.store
+        a, b = int(st.res_off[self.lo + k]), int(st.res_off[self.lo + k + 1])
+        return _StructView(st.ca_xyz[a:b], st.chain[a:b], st.serial[a:b])
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+    def resname_std_all(self) -> np.ndarray:
+        st = self.store
+        return st.resname_std[int(st.res_off[self.lo]):int(st.res_off[self.hi])]
+
+
+class CoordStore:
+    """PREFIX.coords, memory-mapped read-only.  Arrays: res_off u64[S + 1]; n_xyz, ca_xyz, cb_xyz f32[R, 3]; aa, resname_std, chain u8[R];
+    cb_valid u8[R] or None; serial u64[R]; stamp = the three numbers of index_stamp at the time of writing."""
+
+    @staticmethod
+    def open(path: str, check_prefix: str | None = None) -> "CoordStore":
+        """refuses (CoordStoreError) a store whose header, section sizes or res_off are inconsistent, and — with check_prefix — one whose stamp
+        disagrees with the index files at that prefix; OSError for a file that cannot be read"""
+        self = CoordStore()
+        self.path = path
+        size = os.path.getsize(path)
+        if size < COORDS_HEADER:
+            raise CoordStoreError(f"{path}: {size} bytes, shorter than the {COORDS_HEADER}-byte header")
+        mm = np.memmap(path, dtype=np.uint8, mode="r")
+        if bytes(mm[:8]) != COORDS_MAGIC:
+            raise CoordStoreError(f"{path}: not a coordinate store (magic {bytes(mm[:8])!r})")
+        ver, flags = (int(x) for x in mm[8:16].view("<u4"))
+        if ver != COORDS_VERSION:
+            raise CoordStoreError(f"{path}: version {ver}, this reader knows version {COORDS_VERSION}")
+        if flags & ~1:
+            raise CoordStoreError(f"{path}: unknown flag bits {flags:#x}")
+        S, R, *stamp = (int(x) for x in mm[16:56].view("<u8"))
+        if S >= 0xffffffff or R >= 1 << 48:
+            raise CoordStoreError(f"{path}: header claims {S} structures and {R} residues")
+        lay, want = _coords_layout(S, R, bool(flags & 1))
+        if size != want:
+            raise CoordStoreError(f"{path}: {size} bytes, its header ({S} structures, {R} residues) asks for exactly {want}"
+                                  + (" (truncated)" if size < want else " (trailing bytes)"))
+        self.n_struct, self.n_res, self.stamp, self.flags = S, R, tuple(stamp), flags
+        for name, dt, per in COORDS_SECTIONS:
+            if name not in lay:
+                setattr(self, name, None)
+                continue
+            pos, n = lay[name]
+            arr = mm[pos:pos + n * np.dtype(dt).itemsize].view(np.dtype(dt).newbyteorder("<"))
+            setattr(self, name, arr.reshape(-1, 3) if per == 3 else arr)
+        off = self.res_off
+        if int(off[0]) != 0:
+            raise CoordStoreError(f"{path}: res_off[0] is {int(off[0])}, not 0")
+        if S and not bool(np.all(off[1:] >= off[:-1])):
+            k = int(np.nonzero(off[1:] < off[:-1])[0][0])
+            raise CoordStoreError(f"{path}: res_off does not ascend (structure {k}: {int(off[k])} -> {int(off[k + 1])})")
+        if int(off[S]) != R:
+            raise CoordStoreError(f"{path}: res_off[{S}] is {int(off[S])}, the header says {R} residues")
+        if check_prefix is not None:
+            self.check_stamp(check_prefix)
+        return self
+
+    def check_stamp(self, prefix: str):
+        now = index_stamp(prefix)
+        for name, was, isnow in zip(STAMP_FIELDS, self.stamp, now):
+            if was != isnow:
+                raise CoordStoreError(f"{self.path} was written for other index files than those at {prefix}: {name} = {was} in its stamp, {isnow} now "
+                                      f"(rebuild it with `coords -i {prefix}`)")
+
+    def _arrays(self, sl, off) -> CoordArrays:
+        from .api import PackedStructures
+        take = lambda a: None if a is None else a[sl]
+        return CoordArrays(PackedStructures(off, take(self.n_xyz), take(self.ca_xyz), take(self.cb_xyz), take(self.aa), take(self.cb_valid)),
+                           take(self.chain), take(self.resname_std), take(self.serial))
+
+    def slice(self, lo: int, hi: int) -> CoordArrays:
+        """structures [lo, hi): views of the mapping (res_off rebased to 0 is the one copy)"""
+        if not 0 <= lo <= hi <= self.n_struct:
+            raise IndexError(f"slice [{lo}, {hi}) of {self.n_struct} structures")
+        a, b = int(self.res_off[lo]), int(self.res_off[hi])
+        return self._arrays(slice(a, b), np.asarray(self.res_off[lo:hi + 1]) - np.uint64(a))
+
+    def select(self, ids) -> CoordArrays:
+        """structure k of the result = structure ids[k] of the store (a gather: any order, repeats allowed); copies"""
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) and (ids.min() < 0 or ids.max() >= self.n_struct):
+            raise IndexError(f"select: ids outside 0 .. {self.n_struct - 1}")
+        start = np.asarray(self.res_off)[ids].astype(np.int64)
+        lens = np.asarray(self.res_off)[ids + 1].astype(np.int64) - start
+        off = np.zeros(len(ids) + 1, np.uint64)
+        off[1:] = np.cumsum(lens)
+        idx = np.repeat(start - off[:-1].astype(np.int64), lens) + np.arange(int(off[-1]), dtype=np.int64)
+        return self._arrays(idx, off)
+
+    def structs(self, lo: int = 0, hi: int | None = None) -> _LazyStructs:
+        hi = self.n_struct if hi is None else hi
+        if not 0 <= lo <= hi <= self.n_struct:
+            raise IndexError(f"structs [{lo}, {hi}) of {self.n_struct} structures")
+        return _LazyStructs(self, lo, hi)
+
+
+class CoordWriter:
+    """streams a store: add() appends runs of structures to one temporary file per section, close(stamp) assembles header and sections under a
+    temporary name and renames it to `path`; abort() (or a failed close) leaves nothing behind.  write_coords is the whole of it in one call."""
+    BLOCK = 1 << 16      # structures per gathered block of a (store, ids) piece
+
+    def __init__(self, path: str):
+        self.path, self.tmp = path, f"{path}.tmp{os.getpid()}"
+        self.S = self.R = 0
+        self.cbv_seen = self.cbv_missing = False
+        self.files = {name: open(f"{self.tmp}.{name}", "wb") for name, _, _ in COORDS_SECTIONS}
+        self.files["res_off"].write(np.zeros(1, "<u8").tobytes())
+
+    def _add_arrays(self, a: CoordArrays):
+        ps = a.ps
+        n = int(ps.res_off[-1])
+        if not (len(a.chain) == len(a.resname_std) == len(a.serial) == n):
+            raise ValueError("write_coords: label arrays do not match res_off[-1]")
+        put = lambda name, arr, dt: self.files[name].write(np.ascontiguousarray(arr, dtype=np.dtype(dt).newbyteorder("<")).tobytes())
+        put("res_off", np.asarray(ps.res_off[1:], np.uint64) + np.uint64(self.R), np.uint64)
+        for name in ("n_xyz", "ca_xyz", "cb_xyz"):
+            put(name, getattr(ps, name), np.float32)
+        put("aa", ps.aa, np.uint8)
+        if ps.cb_valid is None:
+            self.cbv_missing = self.cbv_missing or n > 0
+            put("cb_valid", np.ones(n, np.uint8), np.uint8)      # a piece without cb_valid contributes ones when another piece has it
+        else:
+            self.cbv_seen = True
+            put("cb_valid", ps.cb_valid, np.uint8)
+        put("resname_std", a.resname_std, np.uint8)
+        put("chain", a.chain, np.uint8)
+        put("serial", a.serial, np.uint64)
+        self.S += ps.n_struct
+        self.R += n
+
+    def add(self, piece):
+        """piece: CoordArrays (raw arrays), or (CoordStore, ids or None) — the structures ids[k] of the store in that order, None = all of it"""
+        if isinstance(piece, CoordArrays):
+            return self._add_arrays(piece)
+        store, ids = piece
+        if ids is None:
+            for lo in range(0, store.n_struct, self.BLOCK):
+                self._add_arrays(store.slice(lo, min(lo + self.BLOCK, store.n_struct)))
+        else:
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            for lo in range(0, len(ids), self.BLOCK):
+                self._add_arrays(store.select(ids[lo:lo + self.BLOCK]))
+
+    def abort(self):
+        for f in self.files.values():
+            f.close()
+        for p in [f"{self.tmp}.{name}" for name, _, _ in COORDS_SECTIONS] + [self.tmp]:
+            if os.path.exists(p):
+                os.remove(p)
+
+    def close(self, stamp):
+        import shutil
+        try:
+            for f in self.files.values():
+                f.close()
+            with_cbv = self.cbv_seen or not self.cbv_missing      # absent only when no piece that has residues carried it
+            lay, size = _coords_layout(self.S, self.R, with_cbv)
+            head = COORDS_MAGIC + np.array([COORDS_VERSION, 1 if with_cbv else 0], "<u4").tobytes() + \
+                np.array([self.S, self.R] + [int(x) for x in stamp], "<u8").tobytes()
+            with open(self.tmp, "wb") as out:
+                out.write(head.ljust(COORDS_HEADER, b"\0"))
+                for name, dt, _ in COORDS_SECTIONS:
+                    if name not in lay:
+                        continue
+                    out.write(b"\0" * (lay[name][0] - out.tell()))
+                    with open(f"{self.tmp}.{name}", "rb") as src:
+                        shutil.copyfileobj(src, out, 1 << 22)
+                    if out.tell() != lay[name][0] + lay[name][1] * np.dtype(dt).itemsize:
+                        raise IOError(f"write_coords: section {name} has {out.tell() - lay[name][0]} bytes")
+                if out.tell() != size:
+                    raise IOError("write_coords: size mismatch")
+            os.replace(self.tmp, self.path)
+        finally:
+            self.abort()
+
+
+def write_coords(path: str, pieces, stamp):
+    """the one writer of PREFIX.coords (`index --coords`, `coords`, `update`, `merge`, `reorder`): the pieces one after the other — each
+    (CoordStore, ids or None) or CoordArrays, see CoordWriter.add; pieces may be a generator — streamed to a temporary name and renamed at the
+    end.  stamp: the three numbers of index_stamp, or a callable that gives them once the pieces are consumed."""
+    w = CoordWriter(path)
+    try:
+        for p in pieces:
+            w.add(p)
+    except BaseException:
+        w.abort()
+        raise
+    w.close(stamp() if callable(stamp) else stamp)

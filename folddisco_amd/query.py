@@ -524,7 +524,10 @@ def query_pdb(ctx: Context, index: FolddiscoIndex, db: Batch, db_structs: list[C
         rows = rows[:top_n]
     match_rows = []
     if not skip_match and rows:
-        std = np.concatenate([s.resname_std() for s in db_structs]) if db_structs else np.zeros(0, np.uint8)
+        if hasattr(db_structs, "resname_std_all"):     # a coordinate store's lazy sequence (indexio.CoordStore.structs): one array, no per-structure objects
+            std = db_structs.resname_std_all()
+        else:
+            std = np.concatenate([s.resname_std() for s in db_structs]) if db_structs else np.zeros(0, np.uint8)
         owned = [k for k, r in enumerate(rows) if lo <= r["nid"] < lo + n_local]       # candidates this rank holds coordinates of
         cand = np.array([rows[k]["nid"] - lo for k in owned], np.uint32)
         ms = retrieve(ctx, db, std, cand, qm, qbatch, ca_distance, nbin_dist=nbin_dist, nbin_angle=nbin_angle, dist_cutoff=dist_cutoff,

@@ -308,11 +308,13 @@ class _ParsedView:
         self.__array_interface__ = {"data": (C.cast(ptr, C.c_void_p).value or 0, False), "shape": (n,), "typestr": np.dtype(dtype).str, "version": 3}
 
 
-def read_packed(paths, threads: int = 0, max_residue: int = 0, foldcomp=None):
+def read_packed(paths, threads: int = 0, max_residue: int = 0, foldcomp=None, labels: bool = False):
     """Native ingest straight into the flat batch layout (no per-structure Python objects): -> (PackedStructures, nres u64[S],
     plddt f32[S], nres_raw u64[S], ok u8[S]).  What the index workflow needs: coordinates for the GPU, nres / plddt for .lookup.
     With foldcomp = FoldcompDb, paths are database keys.  The coordinate / residue-type arrays are views of the library's arrays (a copy
-    of them was a fifth of the ingest's wall time: ~40 bytes per residue into fresh pages); the per-structure columns are copies."""
+    of them was a fifth of the ingest's wall time: ~40 bytes per residue into fresh pages); the per-structure columns are copies.
+    labels=True appends a sixth element: dict(chain u8[R], resname_std u8[R], serial u64[R]) of the same fd_parsed, as views like the coordinates
+    (what the coordinate store keeps beside the batch, indexio.write_coords)."""
     from . import _lib
     from .api import PackedStructures
     L = _lib.load()
@@ -327,4 +329,6 @@ def read_packed(paths, threads: int = 0, max_residue: int = 0, foldcomp=None):
                           zero(P.cb_xyz, 3 * R, np.float32).reshape(-1, 3), zero(P.aa, R, np.uint8), zero(P.cb_valid, R, np.uint8))
     nres = np.diff(off).astype(np.uint64)
     plddt, raw, okf = view(P.plddt, S, np.float32), view(P.nres_raw, S, np.uint64), view(P.ok, S, np.uint8)
+    if labels:
+        return ps, nres, plddt, raw, okf, dict(chain=zero(P.chain, R, np.uint8), resname_std=zero(P.resname_std, R, np.uint8), serial=zero(P.serial, R, np.uint64))
     return ps, nres, plddt, raw, okf

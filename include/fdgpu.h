@@ -111,6 +111,23 @@ void fdgpu_batch_destroy(fdgpu_batch *b);
 uint64_t fdgpu_batch_num_structures(const fdgpu_batch *b);
 uint64_t fdgpu_batch_num_residues(const fdgpu_batch *b);
 
+/* ---- operations on a resident batch ------------------------------------------------------------------------
+ * A resident database is an fdgpu_index and the fdgpu_batch of its coordinates.  Every id-mapping index operation has a batch counterpart, so
+ * the pair stays addressable by the candidate ids scoring returns: fdgpu_index_remove(keep) ~ select of the kept ids in ascending order,
+ * fdgpu_index_permute(new_id) ~ select of argsort(new_id), part r of fdgpu_index_split(bounds) ~ select of bounds[r] .. bounds[r + 1] - 1,
+ * fdgpu_index_merge ~ fdgpu_batch_concat.  Bytes are copied verbatim.  The results own their memory (fdgpu_batch_destroy); the sources stay valid.
+ *
+ * fdgpu_batch_select: structure k of *out = structure ids[k] of b, in the order given — a gather: repeats are allowed, n = 0 gives an empty batch,
+ * a source without cb_valid gives a result without it.  Checked on the host before anything is launched: an id >= the batch's structures is
+ * FDGPU_EINVAL, a result of 2^32 residues or more FDGPU_ERANGE (the sum is 64-bit: repeats can reach it).  On any error *out is NULL. */
+int fdgpu_batch_select(fdgpu_ctx *ctx, const fdgpu_batch *b, const uint32_t *ids, uint64_t n, fdgpu_batch **out);
+/* the parts one after the other (2 .. 64 parts, a part may be empty; anything else FDGPU_EINVAL): device-to-device copies.  If only some parts
+ * carry cb_valid the others contribute ones.  FDGPU_ERANGE for 2^32 residues or structures.  On any error *out is NULL. */
+int fdgpu_batch_concat(fdgpu_ctx *ctx, const fdgpu_batch *const *parts, uint64_t n_parts, fdgpu_batch **out);
+/* the five arrays and res_off of a resident batch back on the host: host_out is filled like the fd_batch_desc of fdgpu_batch_upload, every array
+ * released with fdgpu_free; cb_valid = NULL where the batch has none. */
+int fdgpu_batch_export(fdgpu_ctx *ctx, const fdgpu_batch *b, fd_batch_desc *host_out);
+
 /* ---- S1: per-structure hashes -------------------------------------------------------------
  * Replaces get_geometric_hash_as_u32_from_structure (src/controller/feature.rs:198-231)
  * followed by the caller's sort_unstable(); dedup() (src/controller/mod.rs:343-345), for every
