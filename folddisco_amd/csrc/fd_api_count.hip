@@ -221,6 +221,7 @@ extern "C" int fdgpu_count_query(fdgpu_ctx *c, const fdgpu_index *ix, const uint
     if (!c || !ix || !out || !n_out || (nq && (!q_hash || !q_node || !q_edge_j || !q_idf)) || (ix->n_structures && !penalty && !ix->penalty)) return FDGPU_EINVAL;
     *out = nullptr; *n_out = 0;
     reset_timings(c);
+    c->last_count_path = 0;
     hipStream_t st = c->stream;
     const uint64_t S = ix->n_structures;
     if (S == 0 || nq == 0) { *out = (fd_count_rec *)malloc(sizeof(fd_count_rec)); return *out ? FDGPU_OK : FDGPU_ENOMEM; }
@@ -230,6 +231,7 @@ extern "C" int fdgpu_count_query(fdgpu_ctx *c, const fdgpu_index *ix, const uint
     rows_hash.reserve(nq); rows_meta.reserve(nq);
     const bool packed = fd_cq_rows(q_hash, q_node, q_edge_j, q_idf, 0, nq, rows_hash, rows_meta) && nq < (1ull << 18);
     const uint32_t words = (uint32_t)((S + 31) / 32);
+    c->last_count_path = FDGPU_PATH_ROWS | (packed ? FDGPU_PATH_PACKED : 0u);
     // workspace
     HIPCHK(c, c->ws[WS_MISC0].ensure(nq * 4));   // query hashes in row order
     HIPCHK(c, c->ws[WS_MISC3].ensure(nq * 8));   // row metadata
@@ -371,6 +373,7 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
     if (!c || !ix || !out || !out_off || !q_off || (ix->n_structures && !penalty && !ix->penalty)) return FDGPU_EINVAL;
     *out = nullptr; *out_off = nullptr;
     reset_timings(c);
+    c->last_count_path = 0;
     hipStream_t st = c->stream;
     const uint64_t S = ix->n_structures, nq = q_off[n_queries];
     const bool cq_trace = getenv("FDGPU_TRACE") != nullptr;       // host-side stage stamps on stderr (measurement aid)
@@ -473,6 +476,8 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
         need_rows();
     }
     if (e != hipSuccess) { free(ooff); c->err = std::string("count_query_batch workspace: ") + hipGetErrorString(e); return FDGPU_EHIP; }
+    c->last_count_path = (tiled ? FDGPU_PATH_TILED : 0u) | (qt32 ? FDGPU_PATH_SUMS32 : 0u) | (tiled && stream_cap ? FDGPU_PATH_STREAM : 0u) |
+                         (tiled_big ? FDGPU_PATH_SLICED : 0u) | (!tiled && !tiled_big ? FDGPU_PATH_ROWS : 0u) | (packed ? FDGPU_PATH_PACKED : 0u);
     // the rows' inputs: hashes, metadata, the queries' row ranges and — when the caller knows them — the rows' list positions.  The tiled motif path
     // sends them up in ONE block packed in page-locked memory ([metadata | list positions | row ranges | hashes] in ws[WS_MISC3]): one copy launch, not four
     uint32_t *d_qhash = c->ws[WS_MISC0].as<uint32_t>();
@@ -682,7 +687,10 @@ int fd_count_query_batch_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t n_qu
         }
         if (overflow) {   // more ties at the cut-off than the selection's slots hold: the compacting path ranks that call
             free(ooff); fdgpu_free(rr);
-            return fd_count_query_batch_impl(c, ix, n_queries, q_off, q_hash, q_node, q_edge_j, q_idf, penalty, top_n, out, out_off, false, nullptr, known_segments);
+            const uint32_t first_path = c->last_count_path;
+            const int rc2 = fd_count_query_batch_impl(c, ix, n_queries, q_off, q_hash, q_node, q_edge_j, q_idf, penalty, top_n, out, out_off, false, nullptr, known_segments);
+            c->last_count_path = first_path | FDGPU_PATH_OVERFLOW;
+            return rc2;
         }
         (void)tot;
         uint64_t w = 0;
@@ -796,6 +804,12 @@ extern "C" int fdgpu_count_query_batch_top(fdgpu_ctx *c, const fdgpu_index *ix, 
                                            const uint32_t *q_node, const uint32_t *q_edge_j, const float *q_idf, const float *penalty,
                                            uint32_t top_n, fd_count_rec **out, uint64_t **out_off) { FD_LOCK(c);
     return fd_count_query_batch_impl(c, ix, n_queries, q_off, q_hash, q_node, q_edge_j, q_idf, penalty, top_n, out, out_off, true, nullptr);
+}
+
+extern "C" int fdgpu_debug_last_count_path(fdgpu_ctx *c, uint32_t *flags) { FD_LOCK(c);
+    if (!c || !flags) return FDGPU_EINVAL;
+    *flags = c->last_count_path;
+    return FDGPU_OK;
 }
 
 // The length penalty nres^(-lp) of the index's structures (count_query.rs:200), kept on the device: count queries may then pass

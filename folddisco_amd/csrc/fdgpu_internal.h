@@ -102,6 +102,7 @@ struct fdgpu_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
+    uint32_t last_count_path = 0;          // FDGPU_PATH_* decisions of the last count call (fdgpu_debug_last_count_path: tests at the dispatch's switches)
     fd_devbuf ws[WS_COUNT];
     bool timing = false;
     // Every entry point that takes the context locks it: concurrent callers (the reference calls its seams from rayon workers,

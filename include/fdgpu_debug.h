@@ -39,6 +39,19 @@ int fdgpu_debug_host_components(const uint32_t *edge_i, const uint32_t *edge_j, 
                                 uint64_t **comp_off, uint64_t *n_comps);
 int fdgpu_debug_hash_is_symmetric(uint32_t hash_type, const uint32_t *hashes, uint64_t n, uint8_t *out);
 
+/* Which form the LAST count call on this context took (fdgpu_count_query, fdgpu_count_query_batch[_top], fdgpu_count_query_maps_top): the
+ * booleans its dispatch computed, one bit each, so that a test at one of the dispatch's switches can tell which side it landed on.
+ * OVERFLOW: the device selection met more ties at a cut than it holds and the call was ranked again by the compacting path — the other bits then
+ * still describe the first attempt.  0 = no count call yet, or one that returned before the dispatch (no structures, no rows). */
+#define FDGPU_PATH_TILED 1u          /* scores per tile of structures in LDS (k_qtile.hip / k_qscore32.hip) */
+#define FDGPU_PATH_SUMS32 2u         /* 32-bit idf sums over the planned slot stream (k_qscore32.hip) */
+#define FDGPU_PATH_STREAM 4u         /* pass B reads the decoded stream pass A left */
+#define FDGPU_PATH_SLICED 8u         /* one query of thousands of rows on the tiles, rows in slices */
+#define FDGPU_PATH_ROWS 16u          /* occupancy rows (k_query.hip) */
+#define FDGPU_PATH_PACKED 32u        /* packed (count, idf sum) accumulators: every row's idf below 32 */
+#define FDGPU_PATH_OVERFLOW 64u      /* selection overflow, ranked by the compacting path */
+int fdgpu_debug_last_count_path(fdgpu_ctx *ctx, uint32_t *flags);
+
 #ifdef __cplusplus
 }
 #endif
