@@ -697,7 +697,7 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
     // residues visited in amino-acid order) and every bucket is sorted by the remaining 24 bits — three 8-bit passes instead of four.
     // FDGPU_MSD=0 selects the structure-major stream + four passes (A/B measurements, tests).
     const bool msd_env = [] { const char *e = getenv("FDGPU_MSD"); return !(e && e[0] == '0'); }();      // read per call: tests flip it
-    // its elements are 6 bytes too, but the bucket carries the top six hash bits: key = (hash & 0xffffff) << 8 | local id bits 23:16 — 2^24 structures
+    // its elements are 6 bytes too, but the bucket carries the top six hash bits: u32 plane = hash[7:0] << 24 | local id, u16 plane = hash[23:8] — 2^24 structures
     const bool msd = msd_env && !own && !force32 && S <= (1ull << 24) && n_cfg == 1 && p->hash_type == FDGPU_HASH_PDBTR && S > 0;
     const bool el6 = ids16 || msd;                       // 6-byte sort elements
     const int codec = msd ? 2 : ids16 ? 1 : 0;           // of the sorted stream (k_index.hip)
@@ -783,11 +783,12 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
         }
     }
     int cur;
-    if (msd) {      // every bucket by hash bits [0, 24) = key bits [8, 32): three passes; the bucket holds the other six
+    if (msd) {      // every bucket by hash bits [0, 24): three passes (hash[7:0] = u32 plane bits 31:24, hash[23:8] = the u16 plane); the bucket holds the other six
+        static const fd_rs_digit digits[3] = {{0, 24}, {1, 0}, {1, 8}};
         HIPCHK(c, c->ws[WS_GHIST].ensure((size_t)256 * fd_rs_seg_num_tiles(P, NB) * 4));
         HIPCHK(c, c->ws[WS_TOT].ensure(fd_rs_seg_tot_words(P, NB) * 8));
         HIPCHK(c, c->ws[WS_SEG_TAB].ensure(fd_rs_seg_tab_bytes(P, NB)));
-        cur = fd_radix_sort_pairs16_seg(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, c->ws[WS_SEGOFF].as<uint64_t>(), S, NB, 8, 3, c->ws[WS_GHIST].as<uint32_t>(),
+        cur = fd_radix_sort_pairs16_seg(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, c->ws[WS_SEGOFF].as<uint64_t>(), S, NB, digits, 3, c->ws[WS_GHIST].as<uint32_t>(),
                                         c->ws[WS_TOT].as<uint64_t>(), c->ws[WS_SEG_TAB].p, st, c, c->ws[WS_MISC3].as<unsigned long long>() + 4);
     } else if (ids16) cur = fd_radix_sort_pairs16(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, 32, c->ws[WS_GHIST].as<uint32_t>(), c->ws[WS_TOT].as<uint64_t>(), st, c);
     else cur = sort_pairs(c, ka, (uint32_t *)ia, kb, (uint32_t *)ib, P, 32);   // all 32 bits: unmasked field overflow can set bits 30-31

@@ -309,8 +309,9 @@ void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const f
 uint32_t fd_rs_seg_num_tiles(uint64_t n, uint32_t n_seg);
 uint64_t fd_rs_seg_tot_words(uint64_t n, uint32_t n_seg);
 size_t fd_rs_seg_tab_bytes(uint64_t n, uint32_t n_seg);
+struct fd_rs_digit { uint32_t plane, shift; };      // where a pass's 8-bit digit lives: plane 0 = the u32 words, 1 = the u16 words; bits [shift, shift + 8)
 int fd_radix_sort_pairs16_seg(uint32_t *keys_a, uint16_t *vals_a, uint32_t *keys_b, uint16_t *vals_b, uint64_t n, const uint64_t *seg_off, uint64_t stride,
-                              uint32_t n_seg, int shift0, int passes, uint32_t *ghist, uint64_t *tot, void *seg_tab, hipStream_t st, fdgpu_ctx *timing_ctx = nullptr,
+                              uint32_t n_seg, const fd_rs_digit *digits, int passes, uint32_t *ghist, uint64_t *tot, void *seg_tab, hipStream_t st, fdgpu_ctx *timing_ctx = nullptr,
                               unsigned long long *overflow = nullptr);      // overflow: set when a (bucket, digit) run reaches 2^32 keys (the result is then invalid)
 void fd_launch_row_count(const fd_batch_view &B, const fd_hash_consts &C, uint32_t *row_cnt, float cutoff, hipStream_t st);
 void fd_launch_row_emit(const fd_batch_view &B, const fd_hash_consts &C, const uint64_t *row_off, uint32_t *keys, float cutoff, uint32_t *ids,

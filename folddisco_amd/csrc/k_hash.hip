@@ -383,12 +383,12 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
             // the type bits: such a hash raises wide_flag and the build is redone with 8-byte elements; its key still lands in a counted slot)
             if ((((h_ij | h_ji) >> 30) || (h_ij >> 24) != bf || (h_ji >> 24) != br) && C.wide_flag) atomicOr(C.wide_flag, 1ull);
             const uint64_t pf = s_bb[bf] + sf, pr = s_bb[br] + sr;
-            const uint32_t hi = s >> 16;      // the position says which bucket (the top six hash bits): the key keeps the other 24 and id bits 23:16
-            const uint16_t lo = (uint16_t)(s & 0xffffu);
-            keys[pf] = (h_ij << 8) | hi;
-            keys[pr] = (h_ji << 8) | hi;
-            ((uint16_t *)ids)[pf] = lo;
-            ((uint16_t *)ids)[pr] = lo;
+            // the position says which bucket (the top six hash bits); the other 24 are the three sorted digits: the u32 plane keeps
+            // hash[7:0] << 24 | s (s < 2^24), the u16 plane hash[23:8] — a histogram pass of the sort reads only its digit's plane
+            keys[pf] = (h_ij << 24) | s;
+            keys[pr] = (h_ji << 24) | s;
+            ((uint16_t *)ids)[pf] = (uint16_t)(h_ij >> 8);
+            ((uint16_t *)ids)[pr] = (uint16_t)(h_ji >> 8);
         }
         return;
     }

@@ -20,8 +20,9 @@ struct enc_item { uint32_t len; uint32_t head; uint32_t delta; uint32_t hash; };
 // three element encodings of the sorted stream:
 //   V = uint32_t      : keys[p] = hash,                      vals[p] = structure id
 //   V = uint16_t      : keys[p] = hash << 2 | (local >> 16), vals[p] = local & 0xffff, id = first_id + local  (6-byte elements, 2^18 structures)
-//   V = uint16_t, B24 : keys[p] = hash << 8 | (local >> 16)  — the MSD build's stream: the top six hash bits ARE the bucket the position p lies
-//                       in (bucket b = [seg_off[b * S], seg_off[(b + 1) * S])), the key keeps the other 24 and eight more id bits (2^24 structures)
+//   V = uint16_t, B24 : keys[p] = hash[7:0] << 24 | local, vals[p] = hash[23:8]  — the MSD build's stream (digit planes: k_sort.hip): the top six
+//                       hash bits ARE the bucket the position p lies in (bucket b = [seg_off[b * S], seg_off[(b + 1) * S])), the two planes keep
+//                       the other 24 and the whole local id (2^24 structures): hash = bucket << 24 | val << 8 | key >> 24, id = first_id + (key & 0xffffff)
 template <typename V> struct enc_codec;
 template <> struct enc_codec<uint32_t> {
     static __device__ __forceinline__ uint32_t hash(uint32_t k) { return k; }
@@ -103,7 +104,7 @@ __device__ __forceinline__ void enc_load_classify(const uint32_t *__restrict__ k
 #pragma unroll
             for (int j = 0; j < ENC_ITEMS; ++j) if (base + j < n) hb[j] = K.at(base + j) << 24;
         }
-        ph = pb << 24 | pk >> 8; pid = first_id + (((pk & 255u) << 16) | pv);
+        ph = pb << 24 | pv << 8 | pk >> 24; pid = first_id + (pk & 0xffffffu);
     } else { ph = enc_codec<V>::hash(pk); pid = enc_codec<V>::id(pk, (V)pv, first_id); }
     if (pred_id) *pred_id = pid;     // id of the element before the thread's first one (undefined for element 0)
     bool have_prev = base > 0;
@@ -111,7 +112,7 @@ __device__ __forceinline__ void enc_load_classify(const uint32_t *__restrict__ k
     for (int j = 0; j < ENC_ITEMS; ++j) {
         uint64_t p = base + j;
         uint32_t h, id;
-        if (B24) { h = hb[j] | k[j] >> 8; id = first_id + (((k[j] & 255u) << 16) | v[j]); }
+        if (B24) { h = hb[j] | v[j] << 8 | k[j] >> 24; id = first_id + (k[j] & 0xffffffu); }
         else { h = enc_codec<V>::hash(k[j]); id = enc_codec<V>::id(k[j], (V)v[j], first_id); }
         bool in = p < n;
         bool head = !have_prev || ph != h;

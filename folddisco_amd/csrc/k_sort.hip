@@ -204,7 +204,9 @@ __global__ __launch_bounds__(RS_BINS) void k_rs_scan_tot(uint64_t *__restrict__ 
 //      other's partial lines in L2: PMC traffic 1.03x algorithmic).
 // Full tiles run without any bounds predicate.  The kernel sits at 5.9 ms per pass against 4.8 ms for its own memory
 // skeleton (a load / LDS / store copy of the tile without ranking, measured once: HISTORY.md).
-template <int THREADS, int ITEMS, typename V, bool FULL>
+// DV: the pass's digit is bits [shift, shift + 8) of the PAYLOAD, not of the key (digit planes of the segmented sort) — both are in
+// registers and in LDS already, so the loads, the LDS traffic and the stores are the same either way.
+template <int THREADS, int ITEMS, typename V, bool FULL, bool DV = false>
 __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ keys_in, const V *__restrict__ vals_in,
                                                  uint32_t *__restrict__ keys_out, V *__restrict__ vals_out, uint64_t n, uint32_t shift,
                                                  uint32_t mask, const uint32_t *__restrict__ ghist_row, const uint64_t *__restrict__ dbase,
@@ -235,7 +237,7 @@ __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ ke
     uint32_t *cnt = s_cnt[wid];
 #pragma unroll
     for (int c = 0; c < ITEMS; ++c) {
-        const uint32_t d = (key[c] >> shift) & mask;
+        const uint32_t d = ((DV ? (uint32_t)val[c] : key[c]) >> shift) & mask;
         uint32_t plo = ~0u, phi = ~0u;
         bool ok = true;
         if (!FULL) {
@@ -278,7 +280,7 @@ __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ ke
 #pragma unroll
     for (int c = 0; c < ITEMS; ++c) {
         if (FULL || (uint32_t)(c * 64) + lane < n_wave) {
-            uint32_t pos = cnt[(key[c] >> shift) & mask] + rnk[c];
+            uint32_t pos = cnt[((DV ? (uint32_t)val[c] : key[c]) >> shift) & mask] + rnk[c];
             s_keys[pos] = key[c];
             s_vals[pos] = val[c];
         }
@@ -289,14 +291,14 @@ __device__ __forceinline__ void rs_scatter4_body(const uint32_t *__restrict__ ke
         for (int c = 0; c < ITEMS; ++c) {
             uint32_t k = c * THREADS + tid;
             const uint32_t kk = s_keys[k], vv = (uint32_t)s_vals[k];
-            long long g = (long long)k + s_gofs[(kk >> shift) & mask];
+            long long g = (long long)k + s_gofs[((DV ? vv : kk) >> shift) & mask];
             keys_out[g] = kk;
             vals_out[g] = (V)vv;
         }
     } else {
         for (uint32_t k = tid; k < n_tile; k += THREADS) {
             const uint32_t kk = s_keys[k], vv = (uint32_t)s_vals[k];
-            long long g = (long long)k + s_gofs[(kk >> shift) & mask];
+            long long g = (long long)k + s_gofs[((DV ? vv : kk) >> shift) & mask];
             keys_out[g] = kk;
             vals_out[g] = (V)vv;
         }
@@ -328,7 +330,10 @@ __global__ __launch_bounds__(THREADS) void k_rs_scatter4(const uint32_t *__restr
 
 // ------------------------------------------------------------------------ segmented form (MSD index build)
 // The keys arrive partitioned into n_seg buckets (k_pair_emit2<.., MSD>: bucket = top six hash bits) and every bucket is sorted on its own
-// by the remaining 24 hash bits: three passes instead of four.  Tiles stay aligned to multiples of TILE in memory (16-byte loads, full
+// by the remaining 24 hash bits: three passes instead of four.  The 6-byte element is two planes, and the caller says for every pass where its
+// digit lives (fd_rs_digit: plane, shift).  The MSD build splits the 48 bits so that only the first digit shares a plane with the id —
+// u32 plane = hash[7:0] << 24 | local id, u16 plane = hash[23:8] — and the histogram of passes 2 and 3 reads 2 bytes per element, not 4;
+// the scatter holds both planes in registers and LDS anyway and takes the digit from either at no cost.  Tiles stay aligned to multiples of TILE in memory (16-byte loads, full
 // lines); a tile that a bucket boundary cuts becomes two partial "virtual tiles".  Virtual tiles are numbered bucket by bucket, every
 // bucket's first one at a multiple of RS_SCAN_CHUNK, so that a scan chunk never spans two buckets (the padding tiles are empty).
 // rs_seg_tab lives in device memory: bstart[b] = first key of bucket b, vt0[b] = its first virtual tile.
@@ -371,34 +376,52 @@ __device__ __forceinline__ void rs_seg_lookup(const rs_vtile *__restrict__ D, ui
     const rs_vtile d = D[v];
     *seg = d.seg; *lo = d.lo; *cnt = d.cnt;
 }
-template <int THREADS, int ITEMS>
-__global__ __launch_bounds__(THREADS) void k_rs_hist_seg(const uint32_t *__restrict__ keys, const rs_vtile *__restrict__ D, uint32_t shift, uint32_t mask,
+// The tile histogram of one pass.  K is the element type of the plane that holds the digit (the u32 words or the u16 words) and only that plane is
+// read: 4 or 2 bytes per element.  Full tiles use 16-byte loads (4 or 8 elements each; a full virtual tile starts at a multiple of TILE elements,
+// so they are aligned in both planes), partial tiles the element-wise loop.
+// COPIES: the tile's histogram is kept COPIES times in LDS, interleaved (word = digit * COPIES + lane % COPIES: the copies of one digit lie in
+// different banks), so that lanes that meet in one digit serialise on COPIES addresses, not one; the copies are summed when the row is written.
+// With one copy the LDS atomics, not the bytes, bound the u16 plane's passes.
+#define RS_HIST_COPIES 8
+template <int THREADS, int ITEMS, typename K, int COPIES>
+__global__ __launch_bounds__(THREADS) void k_rs_hist_seg(const K *__restrict__ keys, const rs_vtile *__restrict__ D, uint32_t shift, uint32_t mask,
                                                          uint32_t *__restrict__ ghist, uint32_t nbv) {
     constexpr int TILE = THREADS * ITEMS;
-    __shared__ uint32_t h[RS_BINS];
+    constexpr int EPW = 4 / (int)sizeof(K), LOADS = ITEMS / (4 * EPW);      // elements per 32-bit word, 16-byte loads per thread
+    static_assert(ITEMS % (4 * EPW) == 0 && LOADS >= 1, "whole 16-byte loads");
+    __shared__ uint32_t hs[RS_BINS * COPIES];
     const uint32_t v = fd_xcd_remap(blockIdx.x, nbv);
     if (v >= nbv) return;
     uint32_t seg, cnt;
     uint64_t base;
     rs_seg_lookup(D, v, &seg, &base, &cnt);
-    for (int k = threadIdx.x; k < RS_BINS; k += THREADS) h[k] = 0;
+    for (int k = threadIdx.x; k < RS_BINS * COPIES; k += THREADS) hs[k] = 0;
+    uint32_t *h = hs + (threadIdx.x & (COPIES - 1));
     __syncthreads();
     if (cnt == TILE) {
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         const u32x4 *k4 = reinterpret_cast<const u32x4 *>(keys + base);
+        u32x4 x[LOADS];
 #pragma unroll
-        for (int k = 0; k < ITEMS / 4; ++k) {
-            u32x4 x = __builtin_nontemporal_load(&k4[k * THREADS + threadIdx.x]);
-            atomicAdd(&h[(x.x >> shift) & mask], 1u);
-            atomicAdd(&h[(x.y >> shift) & mask], 1u);
-            atomicAdd(&h[(x.z >> shift) & mask], 1u);
-            atomicAdd(&h[(x.w >> shift) & mask], 1u);
+        for (int k = 0; k < LOADS; ++k) x[k] = __builtin_nontemporal_load(&k4[k * THREADS + threadIdx.x]);
+#pragma unroll
+        for (int k = 0; k < LOADS; ++k) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+#pragma unroll
+                for (int e = 0; e < EPW; ++e) atomicAdd(&h[((x[k][w] >> (shift + 8u * sizeof(K) * e)) & mask) * COPIES], 1u);
+            }
         }
     } else {
-        for (uint32_t k = threadIdx.x; k < cnt; k += THREADS) atomicAdd(&h[(keys[base + k] >> shift) & mask], 1u);
+        for (uint32_t k = threadIdx.x; k < cnt; k += THREADS) atomicAdd(&h[(((uint32_t)keys[base + k] >> shift) & mask) * COPIES], 1u);
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < RS_BINS; k += THREADS) ghist[(uint64_t)v * RS_BINS + k] = h[k];
+    for (int k = threadIdx.x; k < RS_BINS; k += THREADS) {
+        uint32_t t = 0;
+#pragma unroll
+        for (int c = 0; c < COPIES; ++c) t += hs[k * COPIES + c];
+        ghist[(uint64_t)v * RS_BINS + k] = t;
+    }
 }
 // per bucket: exclusive scan over its chunks of every digit's chunk sums + the bucket's digit totals.  grid (16, n_seg)
 __global__ __launch_bounds__(1024) void k_rs_scan_chunks_seg(uint64_t *__restrict__ csum, const rs_seg_tab *__restrict__ T, uint64_t *__restrict__ tot) {
@@ -426,7 +449,7 @@ __global__ __launch_bounds__(RS_BINS) void k_rs_scan_tot_seg(uint64_t *__restric
     uint64_t ex = block_excl_scan_u64(x, sm, &t);
     tot[(uint64_t)b * RS_BINS + threadIdx.x] = ex + T->bstart[b];
 }
-template <int THREADS, int ITEMS, typename V>
+template <int THREADS, int ITEMS, typename V, bool DV>
 __global__ __launch_bounds__(THREADS) void k_rs_scatter4_seg(const uint32_t *__restrict__ keys_in, const V *__restrict__ vals_in, uint32_t *__restrict__ keys_out,
                                                              V *__restrict__ vals_out, const rs_vtile *__restrict__ D, uint32_t shift, uint32_t mask,
                                                              const uint32_t *__restrict__ ghist, uint32_t nbv, const uint64_t *__restrict__ dbase) {
@@ -444,10 +467,10 @@ __global__ __launch_bounds__(THREADS) void k_rs_scatter4_seg(const uint32_t *__r
     rs_seg_lookup(D, v, &seg, &base, &cnt);
     if (!cnt) return;
     if (cnt == TILE)
-        rs_scatter4_body<THREADS, ITEMS, V, true>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
+        rs_scatter4_body<THREADS, ITEMS, V, true, DV>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
                                                   TILE, s_keys, s_vals, s_cnt, s_gofs, sm);
     else
-        rs_scatter4_body<THREADS, ITEMS, V, false>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
+        rs_scatter4_body<THREADS, ITEMS, V, false, DV>(keys_in, vals_in, keys_out, vals_out, 0, shift, mask, ghist + (uint64_t)v * RS_BINS, dbase + (uint64_t)seg * RS_BINS, base,
                                                    cnt, s_keys, s_vals, s_cnt, s_gofs, sm);
 }
 
@@ -500,10 +523,11 @@ static int radix_sort_pairs_t(uint32_t *keys_a, V *vals_a, uint32_t *keys_b, V *
 uint32_t fd_rs_seg_num_tiles(uint64_t n, uint32_t n_seg) { return (uint32_t)(n / 8192 + 2) + n_seg * (RS_SCAN_CHUNK + 1); }
 uint64_t fd_rs_seg_tot_words(uint64_t n, uint32_t n_seg) { return (uint64_t)n_seg * RS_BINS + (uint64_t)(fd_rs_seg_num_tiles(n, n_seg) / RS_SCAN_CHUNK + 2) * RS_BINS; }
 size_t fd_rs_seg_tab_bytes(uint64_t n, uint32_t n_seg) { return ((sizeof(rs_seg_tab) + 15) & ~(size_t)15) + (size_t)fd_rs_seg_num_tiles(n, n_seg) * sizeof(rs_vtile); }
-// Stable sort of every bucket [seg_off[b * stride], seg_off[(b + 1) * stride]) by key bits [shift0, shift0 + 8 * passes): 6-byte elements.
+// Stable sort of every bucket [seg_off[b * stride], seg_off[(b + 1) * stride]) by the 8-bit digits digits[0 .. passes), least significant
+// first: 6-byte elements, a digit is bits [shift, shift + 8) of the u32 plane (plane 0) or of the u16 plane (plane 1).
 // seg_off / seg_tab are device memory; nothing is synchronised.  Returns the buffer (0 = a, 1 = b) that holds the result.
 int fd_radix_sort_pairs16_seg(uint32_t *keys_a, uint16_t *vals_a, uint32_t *keys_b, uint16_t *vals_b, uint64_t n, const uint64_t *seg_off, uint64_t stride,
-                              uint32_t n_seg, int shift0, int passes, uint32_t *ghist, uint64_t *tot, void *seg_tab, hipStream_t st, fdgpu_ctx *tc,
+                              uint32_t n_seg, const fd_rs_digit *digits, int passes, uint32_t *ghist, uint64_t *tot, void *seg_tab, hipStream_t st, fdgpu_ctx *tc,
                               unsigned long long *overflow) {
     if (n == 0 || n_seg == 0 || n_seg > RS_MAX_SEG) return 0;
     constexpr int THREADS = 512, ITEMS = 16;
@@ -515,12 +539,14 @@ int fd_radix_sort_pairs16_seg(uint32_t *keys_a, uint16_t *vals_a, uint32_t *keys
     hipLaunchKernelGGL(k_rs_seg_desc, dim3((nbv + 255) / 256), dim3(256), 0, st, T, (uint32_t)(THREADS * ITEMS), nbv, D);
     int cur = 0;
     for (int pass = 0; pass < passes; ++pass) {
-        const uint32_t shift = (uint32_t)(shift0 + 8 * pass), mask = 255u;
+        const uint32_t shift = digits[pass].shift, mask = 255u;
+        const bool dv = digits[pass].plane == 1;
         uint32_t *ki = cur ? keys_b : keys_a, *ko = cur ? keys_a : keys_b;
         uint16_t *vi = cur ? vals_b : vals_a, *vo = cur ? vals_a : vals_b;
         {
-            StageTimer t(tc, "rs_hist", n * 4 + (uint64_t)nbv * RS_BINS * 4);
-            hipLaunchKernelGGL((k_rs_hist_seg<THREADS, ITEMS>), dim3(grid), dim3(THREADS), 0, st, ki, D, shift, mask, ghist, nbv);
+            StageTimer t(tc, "rs_hist", n * (dv ? 2 : 4) + (uint64_t)nbv * RS_BINS * 4);      // only the digit's plane is read
+            if (dv) hipLaunchKernelGGL((k_rs_hist_seg<THREADS, ITEMS, uint16_t, RS_HIST_COPIES>), dim3(grid), dim3(THREADS), 0, st, vi, D, shift, mask, ghist, nbv);
+            else hipLaunchKernelGGL((k_rs_hist_seg<THREADS, ITEMS, uint32_t, RS_HIST_COPIES>), dim3(grid), dim3(THREADS), 0, st, ki, D, shift, mask, ghist, nbv);
         }
         {
             StageTimer t(tc, "rs_scan", (uint64_t)nbv * RS_BINS * 8);
@@ -531,7 +557,8 @@ int fd_radix_sort_pairs16_seg(uint32_t *keys_a, uint16_t *vals_a, uint32_t *keys
         }
         {
             StageTimer t(tc, "rs_scatter", n * 12);
-            hipLaunchKernelGGL((k_rs_scatter4_seg<THREADS, ITEMS, uint16_t>), dim3(grid), dim3(THREADS), 0, st, ki, vi, ko, vo, D, shift, mask, ghist, nbv, tot);
+            if (dv) hipLaunchKernelGGL((k_rs_scatter4_seg<THREADS, ITEMS, uint16_t, true>), dim3(grid), dim3(THREADS), 0, st, ki, vi, ko, vo, D, shift, mask, ghist, nbv, tot);
+            else hipLaunchKernelGGL((k_rs_scatter4_seg<THREADS, ITEMS, uint16_t, false>), dim3(grid), dim3(THREADS), 0, st, ki, vi, ko, vo, D, shift, mask, ghist, nbv, tot);
         }
         cur ^= 1;
     }
