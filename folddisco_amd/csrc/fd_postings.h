@@ -21,6 +21,15 @@ __host__ __device__ __forceinline__ uint32_t fd_varint_len(uint32_t v) {
 #endif
 }
 
+// the len = fd_varint_len(v) bytes of the varint of v in the low bytes of a word, continuation bits set, the bytes above them zero; no branch on v.
+// The 7-bit groups spread to one byte each (byte 4 = v >> 28); the len - 1 bytes below the last one carry bit 7: 0x80808080 shifted down by the
+// 5 - len bytes that carry none (a shift of 0 .. 40 bits, so len = 0 is defined too: with v = 0 it gives 0, the encoder's "nothing to write").
+__host__ __device__ __forceinline__ uint64_t fd_varint_pack(uint32_t v, uint32_t len) {
+    const uint32_t g = (v & 0x7fu) | (v & 0x3f80u) << 1 | (v & 0x1fc000u) << 2 | (v & 0xfe00000u) << 3;
+    const uint32_t cont = (uint32_t)(0x80808080ull >> (40u - 8u * len));
+    return (uint64_t)(v >> 28) << 32 | (g | cont);
+}
+
 // value and byte length of the varint at the low end of an 8-byte window
 __device__ __forceinline__ uint32_t fd_varint_at(unsigned long long w, uint32_t *nf) {
     const unsigned long long stop = ~w & 0x8080808080ull;            // terminator bits of the first five bytes

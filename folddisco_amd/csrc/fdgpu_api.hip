@@ -672,8 +672,56 @@ extern "C" uint64_t fdgpu_index_value_len(const fdgpu_index *ix) { return ix ? i
 extern "C" uint64_t fdgpu_index_num_postings(const fdgpu_index *ix) { return ix ? ix->n_postings : 0; }
 extern "C" uint64_t fdgpu_index_num_structures(const fdgpu_index *ix) { return ix ? ix->n_structures : 0; }
 
-// force32: 8-byte sort elements.  Returns FDGPU_RETRY_WIDE (internal) when the 6-byte form met a hash beyond 30 bits.
 #define FDGPU_RETRY_WIDE 1000
+// The encoder on a sorted stream of P elements (codec: k_index.hip; S structures; for codec 2 WS_SEGOFF holds the stream's [40][S] table): sizes
+// per tile, their three scans, the totals read back, an index of exactly that size, the write pass.  WS_MISC3 was cleared by the caller (words 0-2
+// receive the totals, 3-4 are the build's wide / overflow flags).  Shared by the build and by fdgpu_debug_encode_stream.
+static int encode_sorted_stream(fdgpu_ctx *c, const uint32_t *ks, const void *is, int codec, uint64_t first_id, uint64_t P, uint64_t S, fdgpu_index **out) {
+    hipStream_t st = c->stream;
+    const bool el6 = codec != 0;
+    int rc;
+    uint32_t nt = std::max<uint32_t>(fd_enc_num_tiles(P), 1);
+    HIPCHK(c, c->ws[WS_TILE_B].ensure((size_t)(nt + 1) * 4));
+    HIPCHK(c, c->ws[WS_TILE_H].ensure((size_t)(nt + 1) * 4));
+    HIPCHK(c, c->ws[WS_TILE_P].ensure((size_t)(nt + 1) * 4));
+    HIPCHK(c, c->ws[WS_TILE_BO].ensure((size_t)(nt + 2) * 8));
+    HIPCHK(c, c->ws[WS_TILE_HO].ensure((size_t)(nt + 2) * 8));
+    HIPCHK(c, c->ws[WS_TILE_PO].ensure((size_t)(nt + 2) * 8));
+    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(nt, S)) * 8 + 64));
+    uint64_t tot[5] = {0, 0, 0, 0, 0};
+    uint64_t nt_eff = P ? fd_enc_num_tiles(P) : 0;
+    {
+        StageTimer t(c, "encode_sizes", P * (el6 ? 6 : 8));
+        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_B].p, 0, (size_t)(nt + 1) * 4, st));
+        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_H].p, 0, (size_t)(nt + 1) * 4, st));
+        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_P].p, 0, (size_t)(nt + 1) * 4, st));
+        fd_launch_enc_sizes(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_B].as<uint32_t>(), c->ws[WS_TILE_H].as<uint32_t>(), c->ws[WS_TILE_P].as<uint32_t>(),
+                            c->ws[WS_SEGOFF].as<uint64_t>(), S, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
+        uint64_t *totd = c->ws[WS_MISC3].as<uint64_t>();
+        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_B].as<uint32_t>(), nt_eff, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 0, st);
+        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_H].as<uint32_t>(), nt_eff, c->ws[WS_TILE_HO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 1, st);
+        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_P].as<uint32_t>(), nt_eff, c->ws[WS_TILE_PO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 2, st);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(tot, c->ws[WS_MISC3].p, 40, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (tot[4]) FAIL(c, FDGPU_ERANGE, "index build: one (residue-pair bucket, key digit) group holds 2^32 keys or more; build the shard in several calls and merge");
+    if (el6 && tot[3]) return FDGPU_RETRY_WIDE;
+    fdgpu_index *ix = nullptr;
+    if ((rc = fd_index_new(c, true, tot[1], tot[0], true, &ix))) return rc;
+    ix->n_postings = tot[2]; ix->n_structures = S; ix->first_id = first_id;
+    {
+        StageTimer t(c, "encode_write", P * (el6 ? 6 : 8) + ix->value_len + ix->n_hashes * 12);
+        fd_launch_enc_write(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_TILE_HO].as<uint64_t>(), ix->value, ix->hashes, ix->offsets,
+                            ix->last_ids, c->ws[WS_MISC3].as<uint64_t>(), ix->n_hashes, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { c->err = std::string("encode launch: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
+    *out = ix;
+    return FDGPU_OK;
+}
+
+// force32: 8-byte sort elements.  Returns FDGPU_RETRY_WIDE (internal) when the 6-byte form met a hash beyond 30 bits.
 static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, uint64_t first_id, fdgpu_index **out, bool force32) {
     if (!c || !b || !p || !out) return FDGPU_EINVAL;
     *out = nullptr;
@@ -794,45 +842,7 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
     else cur = sort_pairs(c, ka, (uint32_t *)ia, kb, (uint32_t *)ib, P, 32);   // all 32 bits: unmasked field overflow can set bits 30-31
     const uint32_t *ks = cur ? kb : ka;
     const void *is = cur ? ib : ia;
-    uint32_t nt = std::max<uint32_t>(fd_enc_num_tiles(P), 1);
-    HIPCHK(c, c->ws[WS_TILE_B].ensure((size_t)(nt + 1) * 4));
-    HIPCHK(c, c->ws[WS_TILE_H].ensure((size_t)(nt + 1) * 4));
-    HIPCHK(c, c->ws[WS_TILE_P].ensure((size_t)(nt + 1) * 4));
-    HIPCHK(c, c->ws[WS_TILE_BO].ensure((size_t)(nt + 2) * 8));
-    HIPCHK(c, c->ws[WS_TILE_HO].ensure((size_t)(nt + 2) * 8));
-    HIPCHK(c, c->ws[WS_TILE_PO].ensure((size_t)(nt + 2) * 8));
-    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(nt, S)) * 8 + 64));
-    uint64_t tot[5] = {0, 0, 0, 0, 0};
-    uint64_t nt_eff = P ? fd_enc_num_tiles(P) : 0;
-    {
-        StageTimer t(c, "encode_sizes", P * (el6 ? 6 : 8));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_B].p, 0, (size_t)(nt + 1) * 4, st));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_H].p, 0, (size_t)(nt + 1) * 4, st));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_P].p, 0, (size_t)(nt + 1) * 4, st));
-        fd_launch_enc_sizes(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_B].as<uint32_t>(), c->ws[WS_TILE_H].as<uint32_t>(), c->ws[WS_TILE_P].as<uint32_t>(),
-                            c->ws[WS_SEGOFF].as<uint64_t>(), S, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
-        uint64_t *totd = c->ws[WS_MISC3].as<uint64_t>();
-        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_B].as<uint32_t>(), nt_eff, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 0, st);
-        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_H].as<uint32_t>(), nt_eff, c->ws[WS_TILE_HO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 1, st);
-        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_P].as<uint32_t>(), nt_eff, c->ws[WS_TILE_PO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 2, st);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(tot, c->ws[WS_MISC3].p, 40, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (tot[4]) FAIL(c, FDGPU_ERANGE, "index build: one (residue-pair bucket, key digit) group holds 2^32 keys or more; build the shard in several calls and merge");
-    if (el6 && tot[3]) return FDGPU_RETRY_WIDE;
-    fdgpu_index *ix = nullptr;
-    if ((rc = fd_index_new(c, true, tot[1], tot[0], true, &ix))) return rc;
-    ix->n_postings = tot[2]; ix->n_structures = S; ix->first_id = first_id;
-    {
-        StageTimer t(c, "encode_write", P * (el6 ? 6 : 8) + ix->value_len + ix->n_hashes * 12);
-        fd_launch_enc_write(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_TILE_HO].as<uint64_t>(), ix->value, ix->hashes, ix->offsets,
-                            ix->last_ids, c->ws[WS_MISC3].as<uint64_t>(), ix->n_hashes, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { c->err = std::string("encode launch: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
-    *out = ix;
-    return FDGPU_OK;
+    return encode_sorted_stream(c, ks, is, codec, first_id, P, S, out);
 }
 
 extern "C" int fdgpu_index_build(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, uint64_t first_id, fdgpu_index **out) { FD_LOCK(c);
@@ -840,6 +850,29 @@ extern "C" int fdgpu_index_build(fdgpu_ctx *c, const fdgpu_batch *b, const fd_ha
     int rc = index_build_impl(c, b, p, first_id, out, e32 && e32[0] == '1');
     if (rc == FDGPU_RETRY_WIDE) rc = index_build_impl(c, b, p, first_id, out, true);
     return rc;
+}
+
+// Test-only (include/fdgpu_debug.h): the encoder alone on a caller-made stream, 8-byte elements (codec 0).
+extern "C" int fdgpu_debug_encode_stream(fdgpu_ctx *c, const uint32_t *hashes, const uint32_t *ids, uint64_t n, fdgpu_index **out) { FD_LOCK(c);
+    if (!c || !out || (n && (!hashes || !ids))) return FDGPU_EINVAL;
+    *out = nullptr;
+    if (n >= 0xffffffffull) FAIL(c, FDGPU_ERANGE, "encode_stream: 2^32 elements or more");
+    uint64_t S = 0;
+    for (uint64_t p = 0; p < n; ++p) {
+        if (p && (hashes[p - 1] > hashes[p] || (hashes[p - 1] == hashes[p] && ids[p - 1] > ids[p]))) FAIL(c, FDGPU_EINVAL, "encode_stream: the stream is not sorted by (hash, id)");
+        S = std::max<uint64_t>(S, (uint64_t)ids[p] + 1);
+    }
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->ws[WS_MISC3].ensure(512));
+    HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC3].p, 0, 64, st));
+    HIPCHK(c, c->ws[WS_KEYS_A].ensure(std::max<uint64_t>(n, 1) * 4));
+    HIPCHK(c, c->ws[WS_IDS_A].ensure(std::max<uint64_t>(n, 1) * 4));
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(c->ws[WS_KEYS_A].p, hashes, n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ws[WS_IDS_A].p, ids, n * 4, hipMemcpyHostToDevice, st));
+    }
+    return encode_sorted_stream(c, c->ws[WS_KEYS_A].as<uint32_t>(), c->ws[WS_IDS_A].p, 0, 0, n, S, out);
 }
 
 // A large device-to-host copy into ordinary (pageable) memory.  The runtime's own path stages through one internal buffer and one

@@ -186,52 +186,89 @@ __global__ __launch_bounds__(ENC_THREADS) void k_enc_sizes(const uint32_t *__res
 }
 
 // pass 2: write varint bytes, sparse hashes and list start offsets
+#define ENC_LDS_BYTES (ENC_TILE * 5 + 32)
+// a tile of ENC_TILE five-byte varints behind the largest alignment shift, rounded up to the dword the varint writer ORs into and to the
+// 16 bytes the zeroing and the write-out move at a time
+static_assert(ENC_LDS_BYTES % 16 == 0 && (ENC_TILE * 5 + 15 + 15) / 16 * 16 <= ENC_LDS_BYTES, "s_bytes: a full tile of five-byte varints must fit");
 template <typename V, bool B24>
 __global__ __launch_bounds__(ENC_THREADS) void k_enc_write(const uint32_t *__restrict__ keys, const V *__restrict__ ids, uint64_t n, uint32_t first_id,
                                                            const uint64_t *__restrict__ tile_byte_off, const uint64_t *__restrict__ tile_head_off,
                                                            uint8_t *__restrict__ value, uint32_t *__restrict__ hashes, uint64_t *__restrict__ offsets,
                                                            uint32_t *__restrict__ last_ids, const uint64_t *__restrict__ bo) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     __shared__ uint64_t sm[ENC_THREADS / 64];
     // varint bytes of the tile are assembled in LDS (pre-shifted by the global misalignment) and leave as
     // 16-byte stores instead of one global byte store per byte
-    __shared__ __attribute__((aligned(16))) uint8_t s_bytes[ENC_TILE * 5 + 32];
-    uint64_t base = (uint64_t)blockIdx.x * ENC_TILE + (uint64_t)threadIdx.x * ENC_ITEMS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_bytes[ENC_LDS_BYTES];
+    uint32_t *const s_dw = reinterpret_cast<uint32_t *>(s_bytes);
+    const uint64_t base = (uint64_t)blockIdx.x * ENC_TILE + (uint64_t)threadIdx.x * ENC_ITEMS;
     enc_item it[ENC_ITEMS];
     uint32_t bytes = 0, heads = 0;
     uint32_t run_id = 0;   // id of the element before item k (for the per-list last ids)
     enc_load_classify<V, B24>(keys, ids, n, base, first_id, it, bo, &run_id);
 #pragma unroll
     for (int k = 0; k < ENC_ITEMS; ++k) { bytes += it[k].len; heads += it[k].head; }
-    uint64_t tot;
-    uint64_t ex = block_excl_scan_packed(((uint64_t)bytes << 32) | heads, sm, &tot);
+    // block_excl_scan_packed, opened up: the tile's length is known after its first barrier, so the bytes the tile will use are zeroed
+    // between the two (the writer below ORs into them)
+    const uint64_t mine = ((uint64_t)bytes << 32) | heads;
+    const uint64_t inc = wave_incl_scan64(mine);
+    if ((threadIdx.x & 63) == 63) sm[threadIdx.x >> 6] = inc;
     const uint64_t tile_b0 = tile_byte_off[blockIdx.x];
     const uint32_t shift = (uint32_t)(tile_b0 & 15ull);
-    uint32_t lo = shift + (uint32_t)(ex >> 32);           // LDS position of this thread's first byte
-    uint64_t boff = tile_b0 + (ex >> 32);
-    uint64_t hoff = tile_head_off[blockIdx.x] + (uint32_t)ex;
-#pragma unroll
-    for (int k = 0; k < ENC_ITEMS; ++k) {
-        if (it[k].head) {
-            hashes[hoff] = it[k].hash;
-            offsets[hoff] = boff;
-            if (hoff) last_ids[hoff - 1] = run_id;            // the list before this head ends on the preceding element
-            ++hoff;
-        }
-        run_id = it[k].head ? it[k].delta : run_id + it[k].delta;
-        if (base + k + 1 == n) last_ids[hoff - 1] = run_id;    // last element: its own id
-        uint32_t v = it[k].delta;
-        for (uint32_t b = 0; b < it[k].len; ++b) {
-            uint32_t byte = v & 0x7fu;
-            v >>= 7;
-            s_bytes[lo++] = (uint8_t)(byte | (b + 1 < it[k].len ? 0x80u : 0u));
-        }
-        boff += it[k].len;
-    }
     __syncthreads();
+    uint64_t ex = inc - mine, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < ENC_THREADS / 64; ++w) {
+        const uint64_t t = sm[w];
+        if (w < (threadIdx.x >> 6)) ex += t;
+        tot += t;
+    }
     const uint32_t tile_len = (uint32_t)(tot >> 32);
     const uint32_t end = shift + tile_len;                 // LDS range [shift, end) holds the tile's bytes
+    for (uint32_t c = threadIdx.x * 16; c < end; c += ENC_THREADS * 16) *reinterpret_cast<u32x4 *>(s_bytes + c) = u32x4{0u, 0u, 0u, 0u};
+    __syncthreads();
+    const uint32_t lo = shift + (uint32_t)(ex >> 32);      // LDS position of this thread's first byte
+    // list heads and the stream's last element: one item in ~700 of a protein index, so everything they need (64-bit offsets, the running id)
+    // stays out of the byte path
+    const bool tail = base < n && n - base <= ENC_ITEMS;
+    if (heads | (tail ? 1u : 0u)) {
+        uint64_t hoff = tile_head_off[blockIdx.x] + (uint32_t)ex;
+        const uint64_t boff = tile_b0 + (ex >> 32);
+        const uint32_t k_last = tail ? (uint32_t)(n - base) - 1u : ENC_ITEMS;
+        uint32_t pre = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < ENC_ITEMS; ++k) {
+            if (it[k].head) {
+                hashes[hoff] = it[k].hash;
+                offsets[hoff] = boff + pre;
+                if (hoff) last_ids[hoff - 1] = run_id;            // the list before this head ends on the preceding element
+                ++hoff;
+            }
+            run_id = it[k].head ? it[k].delta : run_id + it[k].delta;
+            if (k == k_last) last_ids[hoff - 1] = run_id;         // last element: its own id
+            pre += it[k].len;
+        }
+    }
+    // The thread's varints are adjacent in the output: each is packed in a register (fd_varint_pack) and appended to a 64-bit accumulator that
+    // holds the bytes of the dword being filled (at most 3 pending + 5 new).  Every item ORs the accumulator's low dword into LDS — complete or
+    // not: the bits are final, the next item's OR adds the rest — so the only branch is the second dword a five-byte varint can complete.  An OR
+    // and not a store, because a thread's first and last dwords also hold its neighbours' bytes.  A thread without bytes ORs zeros at its position.
+    uint32_t pos = lo;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < ENC_ITEMS; ++k) {
+        const uint32_t len = it[k].len;
+        acc |= fd_varint_pack(len ? it[k].delta : 0u, len) << (8u * (pos & 3u));
+        atomicOr(&s_dw[pos >> 2], (uint32_t)acc);
+        const uint32_t npos = pos + len;
+        const uint32_t filled = (npos >> 2) - (pos >> 2);          // dwords completed by this item: 0, 1, or 2
+        if (filled > 1) { atomicOr(&s_dw[(pos >> 2) + 1], (uint32_t)(acc >> 32)); acc = 0; }
+        else acc = filled ? acc >> 32 : acc;
+        pos = npos;
+    }
+    atomicOr(&s_dw[pos >> 2], (uint32_t)acc);      // pos <= end: inside s_bytes (static_assert above)
+    __syncthreads();
     uint8_t *gbase = value + (tile_b0 - shift);            // 16-byte aligned (value comes from hipMalloc)
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     for (uint32_t c = threadIdx.x * 16; c < end; c += ENC_THREADS * 16) {
         if (c >= shift && c + 16 <= end) {
             *reinterpret_cast<u32x4 *>(gbase + c) = *reinterpret_cast<const u32x4 *>(s_bytes + c);

@@ -28,6 +28,12 @@ int fdgpu_debug_gunzip(const uint8_t *in, uint64_t n, uint8_t **out, uint64_t *n
  * gfx950 arithmetic bit for bit with the host.  op: 0 sinf, 1 cosf, 2 acosf, 3 atanf, 4 atan2f(a, b). */
 int fdgpu_debug_libm(fdgpu_ctx *ctx, int op, const float *a, const float *b, float *out, uint64_t n);
 
+/* The posting encoder alone (csrc/k_index.hip: the sizes pass, the scans, the write pass — the tail of fdgpu_index_build) on a stream the caller
+ * made: n elements (hashes[p], ids[p]) sorted by (hash, id), equal neighbours allowed (they collapse to one posting), as the 8-byte elements of
+ * the build (u32 hash, u32 id; first_id 0).  *out: a resident index of max(ids) + 1 structures, released with fdgpu_index_destroy.  Lets a test
+ * place list heads, varint lengths, duplicates and byte alignments where proteins never put them.  FDGPU_EINVAL for an unsorted stream. */
+int fdgpu_debug_encode_stream(fdgpu_ctx *ctx, const uint32_t *hashes, const uint32_t *ids, uint64_t n, fdgpu_index **out);
+
 /* Host-only pieces of the retrieval glue for graphs of more than 64 nodes (csrc/fd_host_query.hip), callable without a GPU.
  * fdgpu_debug_host_components: the graph of the found residue pairs (edge_i[e] -> edge_j[e], nodes numbered by first appearance,
  * src/controller/graph.rs:16-26) and its strongly + weakly connected components of at least node_count nodes, each sorted by node, the list sorted
