@@ -239,6 +239,7 @@ SYMBOLS = [
     ("fdgpu_debug_merge_gathered", C.c_int, [VP, C.c_uint32, C.c_uint64, C.c_uint32, u8p, C.POINTER(C.POINTER(CountRec)), C.POINTER(u64p)]),
     ("fdgpu_debug_libm", C.c_int, [VP, C.c_int, f32p, f32p, f32p, C.c_uint64]),
     ("fdgpu_debug_last_count_path", C.c_int, [VP, u32p]),
+    ("fdgpu_debug_last_retrieve_path", C.c_int, [VP, u32p]),
     ("fdgpu_debug_encode_stream", C.c_int, [VP, u32p, u32p, C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_ingest_stats", None, [C.POINTER(C.c_double), C.c_int]),
     ("fdgpu_debug_gunzip", C.c_int, [u8p, C.c_uint64, C.POINTER(u8p), u64p]),

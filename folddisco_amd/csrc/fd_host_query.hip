@@ -205,6 +205,9 @@ static void fd_rb_prepare(uint64_t n_queries, const fd_query_map *const *qms, fl
             key[k] = ((uint64_t)m->hash[k] << 32) | (uint32_t)k;
             q_sizes[t] = std::max(q_sizes[t], std::max(m->qi[k], m->qj[k]) + 1);
         }
+        // the rescue (retrieve.rs:479-515) looks a residue of `indices` up in the candidate pairs whether or not a map entry names it: the tables indexed by
+        // query residue cover those residues too (a residue all of whose pairs lie beyond the cutoff, or a hand-made map)
+        for (uint64_t k = 0; k < m->n_indices; ++k) q_sizes[t] = std::max(q_sizes[t], (uint32_t)std::min<uint64_t>((uint64_t)m->indices[k] + 1, 0xffffffffull));
         if (m->n > 256) {
             for (int pass = 0; pass < 4; ++pass) {           // entries arrive in ascending k: a stable sort by hash keeps the first entry first
                 const int sh = 32 + 8 * pass;
@@ -394,6 +397,7 @@ static int fd_rb_device_glue(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t 
     A.cap_matches = cap_m; A.cap_res = cap_res; A.cap_prob = cap_prob; A.cap_pts = cap_pts;
     // the split form of the glue (k_rs_setup + a wavefront per component, k_retrieve.hip); FDGPU_RS_SPLIT=0: k_rs_slots alone (read per call: tests compare the two)
     if (!(getenv("FDGPU_RS_SPLIT") && getenv("FDGPU_RS_SPLIT")[0] == '0')) {
+        c->last_retrieve_path |= FDGPU_RPATH_SPLIT;
         auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
         const size_t o_big = 0, o_head = o_big + up16(n_cand * 4), o_nodes = o_head + n_cand * 32, o_comps = o_nodes + n_cand * FD_WAVE * 4,
                      o_work = o_comps + n_cand * 2 * FD_WAVE * 8, o_np = o_work + up16(cap_m * 8), o_gq = o_np + cap_m * 16, o_gr = o_gq + cap_m * 2 * FD_WAVE * 4,
@@ -419,6 +423,7 @@ static int fd_rb_device_glue(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t 
         cnt_h[1] = cv[RS_CNT_STRIDE]; cnt_h[2] = cv[2 * RS_CNT_STRIDE];
     }
     const uint32_t dflags = (uint32_t)cnt_h[4];
+    c->last_retrieve_path |= (dflags == 0 ? FDGPU_RPATH_DEVICE_DONE : 0u) | (dflags & 1u ? FDGPU_RPATH_LIMIT : 0u) | (dflags & 2u ? FDGPU_RPATH_CAPACITY : 0u);
     auto D2 = t_now();
     if (dflags == 0) {
         const uint64_t nm = cnt_h[0], nprob = cnt_h[1] >> 40, npts = cnt_h[1] & ((1ull << 40) - 1ull);
@@ -490,11 +495,17 @@ extern "C" int fdgpu_retrieve_batch(fdgpu_ctx *c, const fdgpu_batch *db, const u
     return fd_retrieve_batch_impl(c, db, resname_std, n_queries, cand, cand_off, qms, qb, q_struct, p, ca_distance_cutoff, node_count, partial_fit, matches, match_off,
                                   residues, res_off, nullptr);
 }
+extern "C" int fdgpu_debug_last_retrieve_path(fdgpu_ctx *c, uint32_t *flags) { FD_LOCK(c);
+    if (!c || !flags) return FDGPU_EINVAL;
+    *flags = c->last_retrieve_path;
+    return FDGPU_OK;
+}
 // prep: the maps' tables when the caller has built them already (fd_rb_prepare with the same maps and ca_distance_cutoff), else null
 static int fd_retrieve_batch_impl(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t *resname_std, uint64_t n_queries, const uint32_t *cand,
                                   const uint64_t *cand_off, const fd_query_map *const *qms, const fdgpu_batch *qb, const uint32_t *q_struct,
                                   const fd_hash_params *p, float ca_distance_cutoff, uint32_t node_count, uint32_t partial_fit, fd_match_rec **matches,
                                   uint64_t **match_off, int32_t **residues, uint64_t **res_off, const fd_rb_prep *prep, fd_rb_dev_out *dev_out) { FD_LOCK(c);
+    if (c) c->last_retrieve_path = 0;      // also for a call rejected below: the flags describe the LAST call
     if (!c || !db || !qb || !p || !matches || !match_off || !residues || !res_off || !cand_off || (n_queries && (!qms || !q_struct))) return FDGPU_EINVAL;
     *matches = nullptr; *match_off = nullptr; *residues = nullptr; *res_off = nullptr;
     const uint64_t n_cand = cand_off[n_queries];
@@ -530,6 +541,7 @@ static int fd_retrieve_batch_impl(fdgpu_ctx *c, const fdgpu_batch *db, const uin
     for (uint64_t t = 0; t < n_queries; ++t) max_nq = std::max<uint64_t>(max_nq, qms[t]->n_indices);
     const char *hg_env = getenv("FDGPU_HOST_GLUE");      // 1 forces the host path (tests compare the two)
     const bool dev_glue = !(hg_env && hg_env[0] == '1') && !two_pass && !partial_fit && max_nq <= FD_WAVE && max_nq > 0 && n_cand > 0 && n_cand < (1ull << 20);
+    c->last_retrieve_path = (two_pass ? FDGPU_RPATH_TWO_PASS : 0u) | (dev_glue ? FDGPU_RPATH_DEVICE_TRIED : 0u);
     if (dev_glue) {
         bool done = false;
         rc = fd_rb_device_glue(c, db, resname_std, n_queries, cand, cand_off, qms, qb, q_struct, p, node_count, *prep, T0, matches, match_off, residues, res_off, &done, dev_out);
@@ -811,7 +823,7 @@ static int fd_retrieve_batch_impl(fdgpu_ctx *c, const fdgpu_batch *db, const uin
                 if (two_pass) { plan_cache[slot][ci].q_idx = q_idx; plan_cache[slot][ci].r_idx = r_idx; plan_cache[slot][ci].sub_idf = sub_idf; }   // a query residue without a target leaves work for the rescue: its votes come from pairs whose partner is mapped
                 bool unmatched = false;
                 for (uint64_t pos = 0; pos < NQ && !unmatched; ++pos) unmatched = std::find(q_idx.begin(), q_idx.end(), qm->indices[pos]) == q_idx.end();
-                if (unmatched) {
+                if (unmatched && !r_idx.empty()) {       // (a component without any mapped residue — a single node under node_count = 1 — has no partner to count votes for and marks nothing)
                     ++n_rc;
                     if (two_pass) plan_cache[slot][ci].rc_ord = n_rc;
                     for (uint32_t r : r_idx) if (r < Rt) { o.marks.push_back(r); o.mark_ord.push_back(n_rc); }

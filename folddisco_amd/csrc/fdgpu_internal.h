@@ -102,6 +102,7 @@ struct fdgpu_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
+    uint32_t last_retrieve_path = 0;       // FDGPU_RPATH_* decisions of the last fdgpu_retrieve_batch call (fdgpu_debug_last_retrieve_path)
     uint32_t last_count_path = 0;          // FDGPU_PATH_* decisions of the last count call (fdgpu_debug_last_count_path: tests at the dispatch's switches)
     fd_devbuf ws[WS_COUNT];
     bool timing = false;
@@ -513,7 +514,7 @@ struct rs_query_dev {
     uint32_t qh_off, n_hashes;   // sorted unique hashes of the query: hashes[qh_off ..), kfirst / sym parallel to them
     uint32_t map_off;            // its query-map entries: map_qi / map_qj / map_idf [map_off ..)
     uint32_t idx_off, n_idx;     // all_query_indices
-    uint32_t q_size;             // 1 + largest query residue index any entry names
+    uint32_t q_size;             // 1 + largest query residue index any entry or `indices` names
     uint32_t q_res0;             // first residue of the query structure in the query batch
     uint32_t pad;
 };

@@ -58,6 +58,16 @@ int fdgpu_debug_hash_is_symmetric(uint32_t hash_type, const uint32_t *hashes, ui
 #define FDGPU_PATH_OVERFLOW 64u      /* selection overflow, ranked by the compacting path */
 int fdgpu_debug_last_count_path(fdgpu_ctx *ctx, uint32_t *flags);
 
+/* Which way the LAST fdgpu_retrieve / fdgpu_retrieve_batch call on this context went (tests at the dispatch's switches): stage names alone cannot
+ * tell a call that the device glue declined from one that never started it.  0 = no such call yet. */
+#define FDGPU_RPATH_DEVICE_TRIED 1u  /* the device glue (k_retrieve.hip) was started */
+#define FDGPU_RPATH_DEVICE_DONE 2u   /* ... and produced the result */
+#define FDGPU_RPATH_LIMIT 4u         /* ... a slot beyond the kernel's limits (nodes, found triples, lists): host path for the whole call */
+#define FDGPU_RPATH_CAPACITY 8u      /* ... the output buffers' capacity: host path for the whole call */
+#define FDGPU_RPATH_TWO_PASS 16u     /* found triples and candidate pairs in two scans */
+#define FDGPU_RPATH_SPLIT 32u        /* the device glue in its split form (k_rs_setup / k_rs_comp, k_rs_slots for the listed slots) */
+int fdgpu_debug_last_retrieve_path(fdgpu_ctx *ctx, uint32_t *flags);
+
 #ifdef __cplusplus
 }
 #endif
