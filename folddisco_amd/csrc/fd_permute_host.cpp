@@ -3,21 +3,11 @@
 // re-varint.  Two passes over slot ranges, one range per thread: the new length of every list, then, behind a serial prefix sum, the bytes; both
 // passes run the same routine (permute_list), once without and once with a destination.  The same checks as the device form, so the same error
 // code for the same input; nothing is allocated for the result before the sizes pass has found every list sound.
-#include <algorithm>
-#include <cstdlib>
 #include <cstring>
-#include <thread>
-#include <vector>
 #include "../../include/fdgpu.h"
+#include "fd_postings_host.h"
 
 namespace {
-unsigned put_varint(uint32_t v, uint8_t *out) {
-    unsigned n = 0;
-    do { uint8_t byte = v & 0x7f; v >>= 7; out[n++] = byte | (v ? 0x80 : 0); } while (v);
-    return n;
-}
-unsigned varint_len(uint32_t v) { unsigned n = 1; while (v >>= 7) ++n; return n; }
-
 struct pm_in { const uint64_t *offsets; const uint8_t *value; uint64_t value_len, first_id, S; const uint32_t *new_id; };
 
 // list k: its mapped ids in ascending order into ids (scratch), the new byte length into *len, the bytes to dst when dst is not null.
@@ -29,27 +19,21 @@ unsigned permute_list(const pm_in &A, uint64_t k, std::vector<uint32_t> &ids, ui
     if (b1 - b0 > 0xffffffffull) return 2u;
     ids.clear();
     uint64_t run = 0;
-    uint32_t v = 0;
-    unsigned s = 0;
-    for (uint64_t q = b0; q < b1; ++q) {
-        const uint8_t b = A.value[q];
-        if (s > 28 || (s == 28 && (b & 0x70))) return 1u;      // a sixth byte, or a fifth one with more than four payload bits
-        v |= (uint32_t)(b & 0x7f) << s;
-        s += 7;
-        if (b & 0x80) continue;
-        run += v;                                  // the head is absolute: 0 + head
+    for (uint64_t q = b0; q < b1;) {
+        const fd_varint_read vr = fd_read_varint(A.value, q, b1);
+        if (vr.st != FD_VR_OK) return 1u;          // a sixth byte, a fifth one with more than four payload bits, or a varint that leaves the list
+        run += vr.v;                               // the head is absolute: 0 + head
         if (run < A.first_id || run - A.first_id >= A.S) return 1u;
         ids.push_back((uint32_t)A.first_id + A.new_id[run - A.first_id]);
-        v = 0; s = 0;
+        q += vr.n;
     }
-    if (s) return 1u;                              // the last varint leaves the list
     std::sort(ids.begin(), ids.end());
     uint64_t n = 0;
     uint32_t prev = 0;
     for (size_t j = 0; j < ids.size(); ++j) {
         const uint32_t d = j ? ids[j] - prev : ids[j];
-        if (dst) n += put_varint(d, dst + n);
-        else n += varint_len(d);
+        if (dst) n += fd_put_varint(d, dst + n);
+        else n += fd_varint_len_host(d);
         prev = ids[j];
     }
     if (n > 0xffffffffull) return 2u;
@@ -74,16 +58,10 @@ extern "C" int fdgpu_permute_host(const uint32_t *hashes, const uint64_t *offset
         }
     }
     const pm_in A{offsets, value, value_len, first_id, n, new_id};
-    const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>(n_threads ? n_threads : 1, (H + 31) / 32));      // at least 32 slots per thread
+    const uint64_t T = fd_host_threads(n_threads, H, 32);
     std::vector<uint64_t> len(H);
-    auto over_ranges = [&](auto &&f) {
-        std::vector<std::thread> th;
-        for (uint64_t t = 1; t < T; ++t) th.emplace_back(f, t);
-        f(0);
-        for (auto &x : th) x.join();
-    };
     std::vector<unsigned> err(T, 0);
-    over_ranges([&](uint64_t t) {
+    fd_over_ranges(T, [&](uint64_t t) {
         std::vector<uint32_t> ids;
         for (uint64_t k = H * t / T; k < H * (t + 1) / T; ++k) err[t] |= permute_list(A, k, ids, &len[k], nullptr);
     });
@@ -91,16 +69,16 @@ extern "C" int fdgpu_permute_host(const uint32_t *hashes, const uint64_t *offset
     for (unsigned e : err) eb |= e;
     if (eb & 1u) return FDGPU_EINVAL;
     if (eb & 2u) return FDGPU_ERANGE;
-    uint64_t *O = (uint64_t *)malloc((H + 1) * 8);
-    uint32_t *Hh = (uint32_t *)malloc(std::max<uint64_t>(H, 1) * 4);
-    if (!O || !Hh) { free(O); free(Hh); return FDGPU_ENOMEM; }
     uint64_t nv = 0;
-    for (uint64_t k = 0; k < H; ++k) { O[k] = nv; nv += len[k]; }
-    O[H] = nv;
-    uint8_t *V = (uint8_t *)malloc(std::max<uint64_t>(nv, 1));
-    if (!V) { free(O); free(Hh); return FDGPU_ENOMEM; }
+    for (uint64_t k = 0; k < H; ++k) nv += len[k];
+    uint8_t *V;
+    uint32_t *Hh;
+    uint64_t *O;
+    if (!fd_alloc_result(nv, H, &V, &Hh, &O)) return FDGPU_ENOMEM;
+    O[0] = 0;
+    for (uint64_t k = 0; k < H; ++k) O[k + 1] = O[k] + len[k];
     if (H) memcpy(Hh, hashes, H * 4);
-    over_ranges([&](uint64_t t) {
+    fd_over_ranges(T, [&](uint64_t t) {
         std::vector<uint32_t> ids;
         uint64_t l = 0;
         for (uint64_t k = H * t / T; k < H * (t + 1) / T; ++k) (void)permute_list(A, k, ids, &l, V + O[k]);

@@ -1,5 +1,7 @@
 // fd_postings.h — the posting-list byte format, stated once for the encoder (k_index.hip), the device merge (k_merge.hip), the removal
-// (k_prune.hip), the split (k_split.hip), the rebase (k_rebase.hip) and the host merge (fdgpu_merge_subindices).
+// (k_prune.hip), the split (k_split.hip), the rebase (k_rebase.hip), the reorder (k_permute.hip), the checker's first varints (k_verify.hip)
+// and the host merge (fdgpu_merge_subindices).  Its host-safe part — the varint writer and reader — is fd_postings_host.h, which the host
+// forms of those operations (fd_split_host.cpp, fd_rebase_host.cpp, fd_permute_host.cpp) take without this header's HIP include.
 //
 // A posting list is the ascending ids of the structures that hold one hash, as LEB128 varints (7-bit groups, least significant first; bit 7
 // set = another byte follows; 0 is one 0x00 byte; a u32 takes at most five bytes; codec of indextable.rs:93-99, 397-418).  The first varint
@@ -9,6 +11,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "fd_postings_host.h"
+
+#ifndef FD_WAVE                 // fd_device.h defines it; tools/check_varint_pack.cpp parses this header for the host without that one
+#define FD_WAVE 64
+#endif
 
 #define FD_VALUE_SLACK 16      // bytes behind an index's value array: fd_first_varint reads 8 bytes at the start of a list of any length
 
@@ -63,15 +70,39 @@ __device__ __forceinline__ void fd_list_copy(uint8_t *__restrict__ d, uint32_t h
     if (o < n) for (uint64_t z = o; z < n; ++z) d[z] = sp[z];
 }
 
-// ---- a wavefront's walk over one list, 256 bytes per step (four per lane): shared by the removal (k_pr_recode) and the split (k_sp_cross)
-__device__ __forceinline__ uint32_t fd_wave_scan_add(uint32_t v, uint32_t lane) {      // inclusive
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o, 64); if ((int)lane >= o) v += u; }
+// the ln = fd_varint_len(v) bytes of the varint of v at o, byte by byte (ln = 0: nothing)
+__device__ __forceinline__ void fd_varint_store(uint8_t *o, uint32_t v, uint32_t ln) {
+    for (uint32_t b = 0; b < ln; ++b) { o[b] = (uint8_t)((v & 0x7fu) | (b + 1 < ln ? 0x80u : 0u)); v >>= 7; }
+}
+
+// is id one of the index's S structures first_id .. first_id + S - 1?  *loc = its local position (meaningless when not)
+__device__ __forceinline__ bool fd_id_local(uint32_t id, uint32_t first_id, uint64_t S, uint64_t *loc) {
+    *loc = (uint64_t)id - first_id;
+    return id >= first_id && *loc < S;
+}
+
+// ---- wavefront reductions and inclusive scans
+__device__ __forceinline__ uint32_t fd_wave_sum(uint32_t v) {
+    for (int o = FD_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, FD_WAVE);
     return v;
 }
-__device__ __forceinline__ uint64_t fd_wave_scan_max(uint64_t v, uint32_t lane) {      // inclusive
-    for (int o = 1; o < 64; o <<= 1) { const uint64_t u = __shfl_up(v, o, 64); if ((int)lane >= o && u > v) v = u; }
+__device__ __forceinline__ uint32_t fd_wave_max(uint32_t v) {
+    for (int o = FD_WAVE / 2; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(v, o, FD_WAVE); v = u > v ? u : v; }
     return v;
 }
+__device__ __forceinline__ uint32_t fd_wave_scan_add(uint32_t v, uint32_t lane) {
+    for (int o = 1; o < FD_WAVE; o <<= 1) { const uint32_t u = __shfl_up(v, o, FD_WAVE); if ((int)lane >= o) v += u; }
+    return v;
+}
+template <class T>      // uint32_t or uint64_t
+__device__ __forceinline__ T fd_wave_scan_max(T v, uint32_t lane) {
+    for (int o = 1; o < FD_WAVE; o <<= 1) { const T u = __shfl_up(v, o, FD_WAVE); if ((int)lane >= o && u > v) v = u; }
+    return v;
+}
+
+// ---- a wavefront's walk over one list, 256 bytes per step (four per lane).  fd_wave_walk: the removal (k_pr_recode) and the reorder's SORT class
+// (k_pm_sort).  fd_decode_step alone, with carries of their own: the reorder's BITMAP class (k_pm_bitmap: eight wavefronts per step, ids through
+// fd_lane_starts) and the split (k_sp_cross, which keeps a copy of fd_wave_walk's loop for its speed — see there)
 __device__ __forceinline__ uint32_t fd_load4(const uint8_t *p) { uint32_t w; __builtin_memcpy(&w, p, 4); return w; }
 // One step: w = the lane's four bytes at p (0 beyond the list's end b1), nxt = its four bytes of the next step, prev_term = the byte before the
 // step's first one ends a varint (the list start counts as one).  Out: tb = terminator bits of the lane's bytes, sb = bytes that start a varint,
@@ -86,13 +117,13 @@ __device__ __forceinline__ void fd_decode_step(uint32_t w, uint32_t nxt, uint64_
         inm |= (in ? 1u : 0u) << j;
         tb |= (in && !((w >> (8 * j)) & 0x80u) ? 1u : 0u) << j;
     }
-    const uint32_t tb_prev = __shfl_up(tb, 1, 64);
+    const uint32_t tb_prev = __shfl_up(tb, 1, FD_WAVE);
     const uint32_t before0 = lane ? (tb_prev >> 3) & 1u : (prev_term ? 1u : 0u);
     s->tb = tb;
     s->sb = ((tb << 1) | before0) & inm & 0xfu;
-    uint32_t w_hi = __shfl_down(w, 1, 64);
-    const uint32_t n0 = __shfl(nxt, 0, 64);
-    if (lane == 63) w_hi = n0;
+    uint32_t w_hi = __shfl_down(w, 1, FD_WAVE);
+    const uint32_t n0 = __shfl(nxt, 0, FD_WAVE);
+    if (lane == FD_WAVE - 1) w_hi = n0;
     s->win = ((unsigned long long)w_hi << 32) | w;
     s->dsum = 0;
 #pragma unroll
@@ -103,10 +134,32 @@ __device__ __forceinline__ void fd_decode_step(uint32_t w, uint32_t nxt, uint64_
         s->dsum += s->d[j];
     }
 }
-
-// host writer: the varint of v at out, returns its byte length
-static inline unsigned fd_put_varint(uint64_t v, uint8_t *out) {
-    unsigned n = 0;
-    do { uint8_t byte = v & 0x7f; v >>= 7; out[n++] = byte | (v ? 0x80 : 0); } while (v);
-    return n;
+// g(j, id) for every byte j of the lane's four at which a varint starts, id = its absolute id, given the id before the lane's first element.
+// The add sits inside the test on purpose: a step in which no lane starts a varint at byte j skips the whole body.
+template <class G>
+__device__ __forceinline__ void fd_lane_starts(const fd_step &s, uint32_t id, G &&g) {
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+        if ((s.sb >> j) & 1u) { id += s.d[j]; g(j, id); }
+}
+// f(step, id before the lane's first element) for every step of the list at value[b0 .. b1), all 64 lanes of the wavefront together.  The walk owns what one step hands to the
+// next: the next step's word (loaded while this one is decoded; lane 63's window ends in it), whether the byte before the step ends a varint (one
+// that straddles the step edge starts in this step and ends in the next), and the id of the last element so far.
+template <class F>
+__device__ __forceinline__ void fd_wave_walk(const uint8_t *__restrict__ value, uint64_t b0, uint64_t b1, uint32_t lane, F &&f) {
+    uint32_t run_id = 0;          // id of the last element decoded so far (the list's head is absolute: 0 + head)
+    bool prev_term = true;        // the byte before the step's first one ends a varint (the list start counts as one)
+    const uint64_t p0 = b0 + 4u * lane;
+    uint32_t cur = p0 < b1 ? fd_load4(value + p0) : 0u;
+    for (uint64_t base = b0; base < b1; base += 4u * FD_WAVE) {
+        const uint64_t p = base + 4u * lane, pn = p + 4u * FD_WAVE;
+        const uint32_t nxt = pn < b1 ? fd_load4(value + pn) : 0u;      // next step's word, in flight while this one is decoded
+        fd_step s;
+        fd_decode_step(cur, nxt, p, b1, lane, prev_term, &s);
+        const uint32_t dinc = fd_wave_scan_add(s.dsum, lane);
+        f(s, run_id + dinc - s.dsum);
+        run_id += __shfl(dinc, FD_WAVE - 1, FD_WAVE);
+        prev_term = (__shfl(s.tb, FD_WAVE - 1, FD_WAVE) >> 3) & 1u;
+        cur = nxt;
+    }
 }

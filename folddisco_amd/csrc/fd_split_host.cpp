@@ -1,21 +1,12 @@
 // fd_split_host.cpp — fdgpu_split_host: the cut of an index by structure id range (k_split.hip) on host arrays, one list after the other.
 // No device and no HIP call: this file also builds with a plain host compiler.  Every thread cuts a range of slots into buffers of its own, the
 // parts are the threads' buffers in slot order.
-#include <algorithm>
-#include <cstdlib>
 #include <cstring>
-#include <thread>
-#include <vector>
 #include "../../include/fdgpu.h"
+#include "fd_postings_host.h"
 
 namespace {
 struct sh_piece { std::vector<uint8_t> value; std::vector<uint32_t> hashes; std::vector<uint64_t> ends; };      // ends: value bytes after every list
-
-unsigned put_varint(uint64_t v, uint8_t *out) {
-    unsigned n = 0;
-    do { uint8_t byte = v & 0x7f; v >>= 7; out[n++] = byte | (v ? 0x80 : 0); } while (v);
-    return n;
-}
 
 // slots [k0, k1) -> out[r] for every part; false: an id outside the bounds, ids that do not ascend or a varint that leaves its list
 bool cut_range(const uint32_t *hashes, const uint64_t *offsets, const uint8_t *value, uint64_t value_len, uint32_t NP, const uint64_t *bounds,
@@ -27,15 +18,9 @@ bool cut_range(const uint32_t *hashes, const uint64_t *offsets, const uint8_t *v
         uint32_t r = 0;
         bool first = true, open = false;      // open: the list already has a piece in part r
         while (p < b1) {
-            uint64_t d = 0, q = p;
-            unsigned shift = 0;
-            for (;; ++q) {
-                if (q >= b1 || shift > 28) return false;
-                d |= (uint64_t)(value[q] & 0x7f) << shift;
-                shift += 7;
-                if (!(value[q] & 0x80)) break;
-            }
-            ++q;
+            const fd_varint_read vr = fd_read_varint(value, p, b1);
+            if (vr.st == FD_VR_LEAVES || vr.st == FD_VR_SIXTH) return false;      // a fifth byte is taken with every payload bit: the range test below sees the id
+            const uint64_t d = vr.v, q = p + vr.n;
             if (!first && d == 0) return false;
             id += d;
             if (id < bounds[r] || id >= bounds[NP]) return false;
@@ -45,7 +30,7 @@ bool cut_range(const uint32_t *hashes, const uint64_t *offsets, const uint8_t *v
             if (!open) { o.hashes.push_back(hashes[k]); o.ends.push_back(0); open = true; }
             if (head) {
                 uint8_t tmp[10];
-                const unsigned n = put_varint(id, tmp);
+                const unsigned n = fd_put_varint(id, tmp);
                 o.value.insert(o.value.end(), tmp, tmp + n);
             } else o.value.insert(o.value.end(), value + p, value + q);
             o.ends.back() = o.value.size();
@@ -66,25 +51,18 @@ extern "C" int fdgpu_split_host(const uint32_t *hashes, const uint64_t *offsets,
     for (uint32_t r = 0; r < n_parts; ++r) { out_value[r] = nullptr; out_hashes[r] = nullptr; out_offsets[r] = nullptr; out_value_len[r] = 0; out_n_hashes[r] = 0; }
     if (bounds[0] != first_id || bounds[n_parts] > 0xffffffffull) return FDGPU_EINVAL;
     for (uint32_t r = 0; r < n_parts; ++r) if (bounds[r] > bounds[r + 1]) return FDGPU_EINVAL;
-    const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>(n_threads ? n_threads : 1, (H + 4095) / 4096));
+    const uint64_t T = fd_host_threads(n_threads, H, 4096);
     std::vector<std::vector<sh_piece>> got(T, std::vector<sh_piece>(n_parts));
     std::vector<char> ok(T, 1);
-    {
-        std::vector<std::thread> th;
-        auto work = [&](uint64_t t) { ok[t] = cut_range(hashes, offsets, value, value_len, n_parts, bounds, H * t / T, H * (t + 1) / T, got[t].data()) ? 1 : 0; };
-        for (uint64_t t = 1; t < T; ++t) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
-    }
+    fd_over_ranges(T, [&](uint64_t t) { ok[t] = cut_range(hashes, offsets, value, value_len, n_parts, bounds, H * t / T, H * (t + 1) / T, got[t].data()) ? 1 : 0; });
     for (uint64_t t = 0; t < T; ++t) if (!ok[t]) return FDGPU_EINVAL;
     for (uint32_t r = 0; r < n_parts; ++r) {
         uint64_t nh = 0, nv = 0;
         for (uint64_t t = 0; t < T; ++t) { nh += got[t][r].hashes.size(); nv += got[t][r].value.size(); }
-        uint8_t *V = (uint8_t *)malloc(std::max<uint64_t>(nv, 1));
-        uint32_t *Hh = (uint32_t *)malloc(std::max<uint64_t>(nh, 1) * 4);
-        uint64_t *O = (uint64_t *)malloc((nh + 1) * 8);
-        if (!V || !Hh || !O) {
-            free(V); free(Hh); free(O);
+        uint8_t *V;
+        uint32_t *Hh;
+        uint64_t *O;
+        if (!fd_alloc_result(nv, nh, &V, &Hh, &O)) {
             for (uint32_t q = 0; q < r; ++q) { free(out_value[q]); free(out_hashes[q]); free(out_offsets[q]); out_value[q] = nullptr; out_hashes[q] = nullptr; out_offsets[q] = nullptr; }
             return FDGPU_ENOMEM;
         }

@@ -1,9 +1,7 @@
 // fd_verify_host.cpp — fdgpu_verify_host: the index checks of fd_verify.h on host arrays, one list after the other, byte by byte.
 // No device and no HIP call: this file also builds with a plain host compiler (and its sanitizers) for runs over hostile input.
-#include <algorithm>
-#include <thread>
-#include <vector>
 #include "fd_verify.h"
+#include "fd_postings_host.h"
 
 namespace {
 struct vf_part {
@@ -58,12 +56,9 @@ void list_range(const uint64_t *offsets, const uint8_t *value, uint64_t first_id
 
 template <typename F>
 vf_part run_ranges(uint64_t n, uint32_t n_threads, F f) {
-    const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>(n_threads ? n_threads : 1, (n + 4095) / 4096));
+    const uint64_t T = fd_host_threads(n_threads, n, 4096);
     std::vector<vf_part> parts(T);
-    std::vector<std::thread> th;
-    for (uint64_t t = 1; t < T; ++t) th.emplace_back([&, t] { f(n * t / T, n * (t + 1) / T, &parts[t]); });
-    f(0, n / T, &parts[0]);
-    for (auto &x : th) x.join();
+    fd_over_ranges(T, [&](uint64_t t) { f(n * t / T, n * (t + 1) / T, &parts[t]); });
     vf_part all;
     for (auto &p : parts) all.add(p);
     return all;

@@ -652,6 +652,21 @@ int fd_index_new(fdgpu_ctx *c, bool pooled, uint64_t H, uint64_t value_len, bool
     *out = ix;
     return FDGPU_OK;
 }
+__global__ void k_ix_order(const uint8_t *__restrict__ sel, const uint8_t *__restrict__ is_long, const uint64_t *__restrict__ sel_pre,
+                           const uint64_t *__restrict__ long_pre, uint64_t H, uint32_t *__restrict__ order, uint32_t *__restrict__ place) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= H || (sel && !sel[t])) return;
+    const uint64_t n_long = long_pre[H];
+    const uint64_t g = is_long[t] ? long_pre[t] : n_long + ((sel ? sel_pre[t] : t) - long_pre[t]);
+    order[g] = (uint32_t)t;
+    if (place) place[t] = (uint32_t)g;
+}
+void fd_order_long_first(const uint8_t *sel, const uint8_t *is_long, uint64_t H, uint64_t *sel_pre, uint64_t *long_pre, uint64_t *scan_tmp,
+                         uint64_t *total_dev, uint32_t *order, uint32_t *place, hipStream_t st) {
+    if (sel) fd_exclusive_scan<uint8_t>(sel, H, sel_pre, scan_tmp, total_dev, st);
+    fd_exclusive_scan<uint8_t>(is_long, H, long_pre, scan_tmp, total_dev, st);
+    hipLaunchKernelGGL(k_ix_order, dim3(fd_grid(H, 256)), dim3(256), 0, st, sel, is_long, sel_pre, long_pre, H, order, place);
+}
 extern "C" void fdgpu_index_destroy(fdgpu_index *ix) {
     if (!ix) return;
     FD_LOCK(ix->ctx);     // the blocks go back to the context's pool

@@ -256,6 +256,31 @@ int fd_index_last_ids(fdgpu_ctx *c, const fdgpu_index *ix);      // k_merge.hip:
 hipError_t fd_count_postings(fdgpu_ctx *c, const uint8_t *value, uint64_t n, uint64_t *out);      // terminators of n value bytes; synchronises
 static inline unsigned fd_grid(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
 
+// ---- what the operations on a resident index share (k_prune.hip, k_split.hip, k_rebase.hip, k_permute.hip)
+// error bits their kernels raise; the message is the operation's own
+#define FD_IXERR_DAMAGED 1u      // offsets that do not ascend inside the value bytes, a varint that leaves its list, an id outside [first_id, first_id + n_structures)
+#define FD_IXERR_LONG 2u         // a list of 4 GiB or more
+#define FD_LONG_LIST_BYTES 16384u      // decoded lists at least this long are taken first (removal, split)
+// order[] = the selected lists (sel[t] != 0; sel = null: every list) in the order the decode kernels take them: the long ones (is_long[t]) first —
+// a long list is one wavefront's serial walk; started first, it overlaps the many short ones instead of trailing them — each class in list order;
+// place[t] (may be null) = the list's place in that order.  Runs the two prefix scans (sel_pre unused when sel is null; both [H + 1], sel_pre[H]
+// = the number of selected lists, long_pre[H] = of long ones; *total_dev = the last scan's total) and the order kernel on st.
+void fd_order_long_first(const uint8_t *sel, const uint8_t *is_long, uint64_t H, uint64_t *sel_pre, uint64_t *long_pre, uint64_t *scan_tmp,
+                         uint64_t *total_dev, uint32_t *order, uint32_t *place, hipStream_t st);
+// a loaded index carries no last ids: one decode pass makes them, kept with the index, under the operation's own stage name
+static inline int fd_index_last_ids_staged(fdgpu_ctx *c, const fdgpu_index *ix, const char *stage) {
+    if (ix->last_ids || !ix->n_hashes) return FDGPU_OK;
+    StageTimer t(c, stage, ix->value_len + ix->n_hashes * 12);
+    return fd_index_last_ids(c, ix);
+}
+// the failure tail of an operation: the stream's work may still write into the n indexes that were made (null entries: not made), so it ends
+// before their blocks go back to the pool
+static inline int fd_index_op_failed(fdgpu_ctx *c, int rc, fdgpu_index *const *made, size_t n = 1) {
+    (void)hipStreamSynchronize(c->stream);
+    for (size_t k = 0; k < n; ++k) fdgpu_index_destroy(made[k]);
+    return rc;
+}
+
 // batched scoring with the ranked selection left on the device (fdgpu_api.hip; consumed by the sharded query, fd_comm.hip)
 struct fd_cq_dev_out {
     bool got = false, overflow = false; const void *recs = nullptr; const void *state = nullptr; uint32_t top_n = 0, cap = 0;

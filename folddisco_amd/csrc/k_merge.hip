@@ -53,11 +53,6 @@ __global__ void k_mg_pos_fill(const uint32_t *__restrict__ hashes, uint64_t n, c
     pos[g * n_parts + part] = (uint32_t)t;
 }
 
-__device__ __forceinline__ uint32_t mg_wave_sum(uint32_t v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, FD_WAVE);
-    return v;
-}
-
 // last structure id of every list of an index that carries no last_ids (fdgpu_index_load): one wavefront per list, the last id is
 // the sum over the list's bytes of (byte & 0x7f) << 7 * (position inside its varint)
 __global__ __launch_bounds__(256) void k_mg_last_ids(const uint64_t *__restrict__ offsets, const uint8_t *__restrict__ value, uint64_t H, uint32_t *__restrict__ last_ids) {
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(256) void k_mg_last_ids(const uint64_t *__restrict_
         acc += in ? (byte & 0x7fu) << (7u * (pin < 5u ? pin : 4u)) : 0u;
         carry = tm ? 63u - (uint32_t)(63 - __clzll(tm)) : carry + 64u;
     }
-    acc = mg_wave_sum(acc);
+    acc = fd_wave_sum(acc);
     if (lane == 0) last_ids[t] = acc;
 }
 

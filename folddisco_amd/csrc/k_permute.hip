@@ -7,17 +7,18 @@
 // has at least one byte), so the byte length — known from the offsets alone — bounds what a list needs:
 //
 //   SORT    lists of at most PM_SORT_BYTES bytes (the bulk): one wavefront per list.  The mapped ids go to the wavefront's LDS buffer while the list
-//           is decoded (fd_decode_step, 256 bytes per step); ids that are already ascending are left alone (the identity, or a permutation that
+//           is decoded (fd_wave_walk, 256 bytes per step); ids that are already ascending are left alone (the identity, or a permutation that
 //           keeps the order of this list's ids), the others take a bitonic network on the next power of two, then 64 ids per step are re-delta'd
 //   BITMAP  longer lists: one workgroup per list and a bitmap of n_structures bits — a posting list is a set of ids in [0, n), so setting bit
 //           new_id[id] for every decoded id and reading the bitmap in ascending order sorts it without a comparison.  The workgroup decodes
-//           2 KiB per step (eight wavefronts, one fd_decode_step each, their id sums joined through LDS), then takes 512 bitmap words per step:
+//           2 KiB per step (eight wavefronts, one fd_decode_step and fd_lane_starts each, their id sums joined through LDS), then takes 512 bitmap words per step:
 //           popcount gives a word's ids, a workgroup scan of the varint lengths their places, a workgroup max scan the id in front of a word.
 //           The bitmap lives in the workgroup's LDS while n_structures <= PM_LDS_BITS (160 KiB less the scan scratch: 1,308,672 bits), beyond that
 //           in a global-memory slab of ceil(n / 32) words per workgroup, cleared per list, with a bounded number of slabs.
 //
 //   k_pm_plan     thread per list: offsets checked, class by byte length, bytes of the BITMAP class
-//   k_pm_order    lists in the order the kernels take them: BITMAP lists first, each class in list order
+//   order         lists in the order the kernels take them: BITMAP lists first, each class in list order (fd_order_long_first over every list,
+//                 shared with k_prune.hip and k_split.hip)
 //   k_pm_sort<W>  wavefront per SORT list; W = 0: new byte size and last id, W = 1: the bytes
 //   k_pm_bitmap<W, SLAB>  workgroup per BITMAP list (grid-stride over them); SLAB = 0: LDS bitmap, 1: global slab
 // Both passes run the same code up to the store, so they cannot disagree about a size.  The BITMAP kernels are launched before the SORT kernel in
@@ -30,23 +31,12 @@
 #define PM_SORT_BYTES 2048u                                   // SORT class: lists up to this many bytes, hence ids (8 KiB of LDS per wavefront)
 #define PM_SORT_WAVES 4u                                      // lists per workgroup of k_pm_sort (32 KiB of LDS: five workgroups, 20 wavefronts per CU)
 #define PM_BM_THREADS 512u                                    // k_pm_bitmap: eight wavefronts per list
-#define PM_BM_WAVES (PM_BM_THREADS / 64u)
+#define PM_BM_WAVES (PM_BM_THREADS / FD_WAVE)
 #define PM_BM_SCRATCH 64u                                     // words of k_pm_bitmap's LDS in front of the bitmap (scan partials)
 #define PM_LDS_BITS ((160u * 1024u - PM_BM_SCRATCH * 4u) * 8u)      // ids a workgroup's LDS bitmap covers
 #define PM_SLAB_BYTES (1ull << 30)                            // all global bitmap slabs together
-#define PM_ERR_DAMAGED 1u      // offsets that do not ascend inside the value bytes, or an id outside [first_id, first_id + n_structures)
-#define PM_ERR_LONG 2u         // a list of 4 GiB or more
 
 struct pm_args { const uint64_t *offsets; const uint8_t *value; uint64_t H, value_len, S; const uint32_t *new_id; uint32_t first_id; };
-
-__device__ __forceinline__ uint32_t pm_wave_scan_max(uint32_t v, uint32_t lane) {      // inclusive
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o, 64); if ((int)lane >= o && u > v) v = u; }
-    return v;
-}
-// the varint of v at o
-__device__ __forceinline__ void pm_put(uint8_t *o, uint32_t v, uint32_t ln) {
-    for (uint32_t b = 0; b < ln; ++b) { o[b] = (uint8_t)((v & 0x7fu) | (b + 1 < ln ? 0x80u : 0u)); v >>= 7; }
-}
 
 // ---- plan: thread per list.  A list with bad offsets is flagged and put into the SORT class; the call fails behind this kernel, nothing decodes it
 __global__ __launch_bounds__(256) void k_pm_plan(pm_args A, uint32_t sort_bytes, uint8_t *__restrict__ is_long, unsigned long long *__restrict__ long_bytes,
@@ -55,22 +45,15 @@ __global__ __launch_bounds__(256) void k_pm_plan(pm_args A, uint32_t sort_bytes,
     if (t >= A.H) return;
     const uint64_t b0 = A.offsets[t], b1 = A.offsets[t + 1];
     uint32_t lg = 0;
-    if (b1 <= b0 || b1 > A.value_len) atomicOr(err, PM_ERR_DAMAGED);
-    else if (b1 - b0 > 0xffffffffull) atomicOr(err, PM_ERR_LONG);
+    if (b1 <= b0 || b1 > A.value_len) atomicOr(err, FD_IXERR_DAMAGED);
+    else if (b1 - b0 > 0xffffffffull) atomicOr(err, FD_IXERR_LONG);
     else if (b1 - b0 > sort_bytes) { lg = 1; atomicAdd(long_bytes, (unsigned long long)(b1 - b0)); }
     is_long[t] = (uint8_t)lg;
 }
 
-// ---- order: the BITMAP lists first, each class in list order
-__global__ void k_pm_order(const uint8_t *__restrict__ is_long, const uint64_t *__restrict__ lpre, uint64_t H, uint32_t *__restrict__ order) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= H) return;
-    order[is_long[t] ? lpre[t] : lpre[H] + (t - lpre[t])] = (uint32_t)t;
-}
-
 // ---- SORT class: wavefront per list.  buf holds at most PM_SORT_BYTES ids: every id starts at a byte of its own inside a list of at most that many
 template <bool W>
-__global__ __launch_bounds__(PM_SORT_WAVES * 64) void k_pm_sort(pm_args A, const uint32_t *__restrict__ order, uint64_t n_lists, uint32_t *__restrict__ sizes,
+__global__ __launch_bounds__(PM_SORT_WAVES * FD_WAVE) void k_pm_sort(pm_args A, const uint32_t *__restrict__ order, uint64_t n_lists, uint32_t *__restrict__ sizes,
                                                                 uint32_t *__restrict__ new_last, const uint64_t *__restrict__ out_off,
                                                                 uint8_t *__restrict__ out_value, uint32_t *__restrict__ err) {
     __shared__ uint32_t lds[PM_SORT_WAVES][PM_SORT_BYTES];
@@ -81,37 +64,23 @@ __global__ __launch_bounds__(PM_SORT_WAVES * 64) void k_pm_sort(pm_args A, const
     const uint64_t t = order[g];
     const uint64_t b0 = A.offsets[t], b1 = A.offsets[t + 1];
     // decode and map
-    uint32_t run_id = 0, cnt = 0;
-    bool prev_term = true, bad = false;
-    const uint64_t p0 = b0 + 4u * lane;
-    uint32_t cur = p0 < b1 ? fd_load4(A.value + p0) : 0u;
-    for (uint64_t base = b0; base < b1; base += 256) {
-        const uint64_t p = base + 4u * lane, pn = p + 256;
-        const uint32_t nxt = pn < b1 ? fd_load4(A.value + pn) : 0u;
-        fd_step ds;
-        fd_decode_step(cur, nxt, p, b1, lane, prev_term, &ds);
-        const uint32_t dinc = fd_wave_scan_add(ds.dsum, lane);
+    uint32_t cnt = 0;
+    bool bad = false;
+    fd_wave_walk(A.value, b0, b1, lane, [&](const fd_step &ds, uint32_t id0) {
         const uint32_t ns = (uint32_t)__popc(ds.sb), sinc = fd_wave_scan_add(ns, lane);
-        uint32_t id = run_id + dinc - ds.dsum, pos = cnt + sinc - ns;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            if ((ds.sb >> j) & 1u) {
-                id += ds.d[j];
-                const uint64_t loc = (uint64_t)id - A.first_id;
-                uint32_t m = A.first_id;
-                if (id < A.first_id || loc >= A.S) bad = true;
-                else m = A.first_id + A.new_id[loc];
-                if (pos < PM_SORT_BYTES) buf[pos] = m;
-                ++pos;
-            }
-        }
-        run_id += __shfl(dinc, 63, 64);
-        cnt += __shfl(sinc, 63, 64);
-        prev_term = (__shfl(ds.tb, 63, 64) >> 3) & 1u;
-        cur = nxt;
-    }
+        uint32_t pos = cnt + sinc - ns;
+        fd_lane_starts(ds, id0, [&](uint32_t, uint32_t id) {
+            uint64_t loc;
+            uint32_t m = A.first_id;
+            if (!fd_id_local(id, A.first_id, A.S, &loc)) bad = true;
+            else m = A.first_id + A.new_id[loc];
+            if (pos < PM_SORT_BYTES) buf[pos] = m;
+            ++pos;
+        });
+        cnt += __shfl(sinc, FD_WAVE - 1, FD_WAVE);
+    });
     if (cnt > PM_SORT_BYTES) cnt = PM_SORT_BYTES;      // cannot happen (see above); keeps every LDS index in range whatever the bytes are
-    if (bad) atomicOr(err, PM_ERR_DAMAGED);
+    if (bad) atomicOr(err, FD_IXERR_DAMAGED);
     fd_wave_lds_fence();
     // already ascending?
     bool desc = false;
@@ -143,8 +112,8 @@ __global__ __launch_bounds__(PM_SORT_WAVES * 64) void k_pm_sort(pm_args A, const
             ln = fd_varint_len(d);
         }
         const uint32_t linc = fd_wave_scan_add(ln, lane);
-        if (W) pm_put(dst + out_pos + (linc - ln), d, ln);
-        out_pos += __shfl(linc, 63, 64);
+        if (W) fd_varint_store(dst + out_pos + (linc - ln), d, ln);
+        out_pos += __shfl(linc, FD_WAVE - 1, FD_WAVE);
     }
     if (!W && lane == 0) {
         sizes[t] = out_pos;                           // at most 5 * PM_SORT_BYTES
@@ -175,28 +144,23 @@ __global__ __launch_bounds__(PM_BM_THREADS) void k_pm_bitmap(pm_args A, const ui
         for (uint64_t base = b0; base < b1; base += 256u * PM_BM_WAVES, it ^= 1u) {
             const uint64_t wb = base + 256u * wave, p = wb + 4u * lane, pn = p + 256;
             const uint32_t cur = p < b1 ? fd_load4(A.value + p) : 0u, nxt = pn < b1 ? fd_load4(A.value + pn) : 0u;
-            const bool prev_term = wb == b0 || wb >= b1 || !(A.value[wb - 1] & 0x80u);
+            const bool term_before = wb == b0 || wb >= b1 || !(A.value[wb - 1] & 0x80u);      // this wavefront's step starts a varint: from the byte before it
             fd_step ds;
-            fd_decode_step(cur, nxt, p, b1, lane, prev_term, &ds);
+            fd_decode_step(cur, nxt, p, b1, lane, term_before, &ds);
             const uint32_t dinc = fd_wave_scan_add(ds.dsum, lane);
-            if (lane == 63) s_id[it * 8u + wave] = dinc;
+            if (lane == FD_WAVE - 1) s_id[it * 8u + wave] = dinc;
             __syncthreads();
             uint32_t before = 0, total = 0;
 #pragma unroll
             for (uint32_t k = 0; k < PM_BM_WAVES; ++k) { const uint32_t v = s_id[it * 8u + k]; before += k < wave ? v : 0u; total += v; }
-            uint32_t id = run_id + before + dinc - ds.dsum;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                if ((ds.sb >> j) & 1u) {
-                    id += ds.d[j];
-                    const uint64_t loc = (uint64_t)id - A.first_id;
-                    if (id < A.first_id || loc >= A.S) bad = true;
-                    else { const uint32_t q = A.new_id[loc]; atomicOr(&bm[q >> 5], 1u << (q & 31u)); }
-                }
-            }
+            fd_lane_starts(ds, run_id + before + dinc - ds.dsum, [&](uint32_t, uint32_t id) {
+                uint64_t loc;
+                if (!fd_id_local(id, A.first_id, A.S, &loc)) bad = true;
+                else { const uint32_t q = A.new_id[loc]; atomicOr(&bm[q >> 5], 1u << (q & 31u)); }
+            });
             run_id += total;      // s_id[it] is written again two steps on, behind the next step's barrier
         }
-        if (bad) atomicOr(err, PM_ERR_DAMAGED);
+        if (bad) atomicOr(err, FD_IXERR_DAMAGED);
         __syncthreads();
         // the bitmap in ascending order, 512 words per step
         uint8_t *dst = W ? out_value + out_off[t] : nullptr;
@@ -207,10 +171,10 @@ __global__ __launch_bounds__(PM_BM_THREADS) void k_pm_bitmap(pm_args A, const ui
             uint32_t word = 0;
             if (w < words) word = SLAB ? __hip_atomic_load(&bm[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : bm[w];
             const uint32_t mylast = word ? (w << 5) + (32u - (uint32_t)__clz(word)) : 0u;
-            const uint32_t lmax = pm_wave_scan_max(mylast, lane);
-            if (lane == 63) s_max[wave] = lmax;
+            const uint32_t lmax = fd_wave_scan_max(mylast, lane);
+            if (lane == FD_WAVE - 1) s_max[wave] = lmax;
             __syncthreads();
-            uint32_t pred = __shfl_up(lmax, 1, 64), tile_max = prev1;
+            uint32_t pred = __shfl_up(lmax, 1, FD_WAVE), tile_max = prev1;
             if (lane == 0) pred = 0;
             if (prev1 > pred) pred = prev1;
 #pragma unroll
@@ -226,7 +190,7 @@ __global__ __launch_bounds__(PM_BM_THREADS) void k_pm_bitmap(pm_args A, const ui
                 q1 = pos + 1u;
             }
             const uint32_t linc = fd_wave_scan_add(lsum, lane);
-            if (lane == 63) s_len[wave] = linc;
+            if (lane == FD_WAVE - 1) s_len[wave] = linc;
             __syncthreads();
             uint32_t before = 0, total = 0;
 #pragma unroll
@@ -237,7 +201,7 @@ __global__ __launch_bounds__(PM_BM_THREADS) void k_pm_bitmap(pm_args A, const ui
                 for (uint32_t r = word; r; r &= r - 1u) {
                     const uint32_t pos = (w << 5) + (uint32_t)__ffs(r) - 1u;
                     const uint32_t d = q1 ? pos + 1u - q1 : A.first_id + pos, ln = fd_varint_len(d);
-                    pm_put(o, d, ln);
+                    fd_varint_store(o, d, ln);
                     o += ln;
                     q1 = pos + 1u;
                 }
@@ -246,7 +210,7 @@ __global__ __launch_bounds__(PM_BM_THREADS) void k_pm_bitmap(pm_args A, const ui
             prev1 = tile_max;      // s_max is written again behind the next step's first barrier, s_len behind its second
         }
         if (!W && tid == 0) {
-            if (out_pos > 0xffffffffull) { atomicOr(err, PM_ERR_LONG); out_pos = 0; }
+            if (out_pos > 0xffffffffull) { atomicOr(err, FD_IXERR_LONG); out_pos = 0; }
             sizes[t] = (uint32_t)out_pos;
             new_last[t] = prev1 ? A.first_id + (prev1 - 1u) : 0u;
         }
@@ -306,15 +270,14 @@ static int permute_impl(fdgpu_ctx *c, const fdgpu_index *ix, const uint32_t *new
         HIPCHK(c, hipMemcpyAsync(nid, new_id, S * 4, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(tot, 0, 24, st));
         hipLaunchKernelGGL(k_pm_plan, dim3(fd_grid(H, 256)), dim3(256), 0, st, A, sort_bytes, is_long, (unsigned long long *)(tot + 2), err);
-        fd_exclusive_scan<uint8_t>(is_long, H, lpre, c->ws[WS_SCANTMP].as<uint64_t>(), tot, st);
-        hipLaunchKernelGGL(k_pm_order, dim3(fd_grid(H, 256)), dim3(256), 0, st, is_long, lpre, H, order);
+        fd_order_long_first(nullptr, is_long, H, nullptr, lpre, c->ws[WS_SCANTMP].as<uint64_t>(), tot, order, nullptr, st);
     }
     HIPCHK(c, hipGetLastError());
     uint64_t hv[3] = {0, 0, 0};      // BITMAP lists, error bits, their bytes
     HIPCHK(c, hipMemcpyAsync(hv, tot, sizeof hv, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    if (hv[1] & PM_ERR_DAMAGED) FAIL(c, FDGPU_EINVAL, "index permute: the index is damaged (offsets that do not ascend inside the value bytes)");
-    if (hv[1] & PM_ERR_LONG) FAIL(c, FDGPU_ERANGE, "index permute: a posting list reaches 4 GiB");
+    if (hv[1] & FD_IXERR_DAMAGED) FAIL(c, FDGPU_EINVAL, "index permute: the index is damaged (offsets that do not ascend inside the value bytes)");
+    if (hv[1] & FD_IXERR_LONG) FAIL(c, FDGPU_ERANGE, "index permute: a posting list reaches 4 GiB");
     const uint64_t n_long = hv[0], n_short = H - n_long, long_bytes = hv[2];
     // BITMAP launch shape: a grid-stride loop over the lists; as many workgroups as fit the CUs (LDS) or as there are slabs
     unsigned bm_grid = 0;
@@ -339,7 +302,7 @@ static int permute_impl(fdgpu_ctx *c, const fdgpu_index *ix, const uint32_t *new
     }
     if (n_short) {
         StageTimer t(c, "permute_sizes_sort", ix->value_len - long_bytes + n_short * 24);
-        hipLaunchKernelGGL((k_pm_sort<false>), dim3(fd_grid(n_short, PM_SORT_WAVES)), dim3(PM_SORT_WAVES * 64), 0, st, A, order + n_long, n_short, sizes,
+        hipLaunchKernelGGL((k_pm_sort<false>), dim3(fd_grid(n_short, PM_SORT_WAVES)), dim3(PM_SORT_WAVES * FD_WAVE), 0, st, A, order + n_long, n_short, sizes,
                            nx->last_ids, (const uint64_t *)nullptr, (uint8_t *)nullptr, err);
     }
     {
@@ -350,9 +313,9 @@ static int permute_impl(fdgpu_ctx *c, const fdgpu_index *ix, const uint32_t *new
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(hv, tot, 16, hipMemcpyDeviceToHost, st));      // new value length, error bits
     HIPCHK(c, hipStreamSynchronize(st));
-    if (hv[1] & PM_ERR_DAMAGED)
+    if (hv[1] & FD_IXERR_DAMAGED)
         FAIL(c, FDGPU_EINVAL, "index permute: the index holds ids outside [first_id, first_id + n_structures)");
-    if (hv[1] & PM_ERR_LONG) FAIL(c, FDGPU_ERANGE, "index permute: a posting list reaches 4 GiB");
+    if (hv[1] & FD_IXERR_LONG) FAIL(c, FDGPU_ERANGE, "index permute: a posting list reaches 4 GiB");
     nx->value_len = hv[0];
     HIPCHK(c, fd_index_block(c, hv[0] + FD_VALUE_SLACK, (void **)&nx->value, &nx->cap_value));
     if (n_long) {
@@ -361,7 +324,7 @@ static int permute_impl(fdgpu_ctx *c, const fdgpu_index *ix, const uint32_t *new
     }
     if (n_short) {
         StageTimer t(c, "permute_write_sort", ix->value_len - long_bytes + hv[0] + n_short * 28);
-        hipLaunchKernelGGL((k_pm_sort<true>), dim3(fd_grid(n_short, PM_SORT_WAVES)), dim3(PM_SORT_WAVES * 64), 0, st, A, order + n_long, n_short, sizes,
+        hipLaunchKernelGGL((k_pm_sort<true>), dim3(fd_grid(n_short, PM_SORT_WAVES)), dim3(PM_SORT_WAVES * FD_WAVE), 0, st, A, order + n_long, n_short, sizes,
                            nx->last_ids, nx->offsets, nx->value, err);
     }
     HIPCHK(c, hipGetLastError());
@@ -383,11 +346,7 @@ extern "C" int fdgpu_index_permute(fdgpu_ctx *c, const fdgpu_index *ix, const ui
     }
     fdgpu_index *nx = nullptr;
     const int rc = permute_impl(c, ix, new_id, &nx);
-    if (rc != FDGPU_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        fdgpu_index_destroy(nx);
-        return rc;
-    }
+    if (rc != FDGPU_OK) return fd_index_op_failed(c, rc, &nx);
     *out = nx;
     return FDGPU_OK;
 }

@@ -12,11 +12,11 @@
 // (l - f + 1) - (K[l + 1] - K[f]).  Lists that lose every id get size 0 and drop out of the sparse hash table with their hash.
 //
 //   k_pr_plan       thread per list: head, last id, mode, new size of RE-BASE / VERBATIM lists, long-first order key
-//   k_pr_order      re-encoded lists in the order the decode kernels take them: lists above PR_LONG_BYTES first (a long list is one wavefront's
-//                   serial walk; started first, it overlaps the many short ones instead of trailing them)
-//   k_pr_recode<W>  wavefront per re-encoded list, 256 bytes per step (four per lane; fd_decode_step of fd_postings.h, shared with k_split.hip):
-//                   terminator bits -> varint starts, each start decodes from the lane's and its neighbour's word, wave scans turn deltas into
-//                   ids and place the new deltas; W = 0 sizes, W = 1 writes
+//   order           re-encoded lists in the order the decode kernels take them, lists of FD_LONG_LIST_BYTES and more first (fd_order_long_first,
+//                   shared with k_split.hip and k_permute.hip)
+//   k_pr_recode<W>  wavefront per re-encoded list, 256 bytes per step (four per lane; fd_wave_walk of fd_postings.h, shared with k_split.hip
+//                   and k_permute.hip): terminator bits -> varint starts, each start decodes from the lane's and its neighbour's word, wave
+//                   scans turn deltas into ids and place the new deltas; W = 0 sizes, W = 1 writes
 //   k_pr_copy       eight lanes per RE-BASE / VERBATIM list, 16 bytes per lane and step, new head first
 //   k_pr_compact    hashes / offsets / last ids of the non-empty lists at their new slots
 // HBM-bound byte work: the value bytes are read twice (sizes, write) and written once; 8 bytes per hash of tables.
@@ -24,7 +24,6 @@
 #include "fd_api_common.h"
 #include "fd_postings.h"
 
-#define PR_LONG_BYTES 16384u      // re-encoded lists at least this long are decoded first
 #define PR_MODE_COPY 0u
 #define PR_MODE_REBASE 1u
 #define PR_MODE_RECODE 2u
@@ -44,9 +43,9 @@ __global__ __launch_bounds__(256) void k_pr_plan(pr_args A, uint32_t *__restrict
     const uint32_t f = fd_first_varint(A.value + b0, &nf), l = A.last_ids[t];
     const uint64_t fl = (uint64_t)f - A.first_id, ll = (uint64_t)l - A.first_id;
     uint32_t m = PR_MODE_COPY, sz = (uint32_t)(b1 - b0), nl = l;
-    if (b1 - b0 > 0xffffffffull) atomicOr(err, 2u);                      // a list of 4 GiB or more: FDGPU_ERANGE
+    if (b1 - b0 > 0xffffffffull) atomicOr(err, FD_IXERR_LONG);           // a list of 4 GiB or more: FDGPU_ERANGE
     if (b1 <= b0 || f < A.first_id || l < f || ll >= A.S) {
-        atomicOr(err, 1u);                                               // an id outside [first_id, first_id + S): the index does not match n_keep
+        atomicOr(err, FD_IXERR_DAMAGED);                                 // an id outside [first_id, first_id + S): the index does not match n_keep
         sz = 0;
     } else {
         const uint64_t removed = (ll - fl + 1) - (A.K[ll + 1] - A.K[fl]);
@@ -61,16 +60,7 @@ __global__ __launch_bounds__(256) void k_pr_plan(pr_args A, uint32_t *__restrict
     new_last[t] = nl;
     mode[t] = (uint8_t)m;
     recode[t] = m == PR_MODE_RECODE ? 1u : 0u;
-    is_long[t] = (m == PR_MODE_RECODE && b1 - b0 >= PR_LONG_BYTES) ? 1u : 0u;
-}
-
-// ---- order of the re-encoded lists: the long ones first, each class in list order
-__global__ void k_pr_order(const uint8_t *__restrict__ recode, const uint8_t *__restrict__ is_long, const uint64_t *__restrict__ rpre,
-                           const uint64_t *__restrict__ lpre, uint64_t H, uint32_t *__restrict__ order) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= H || !recode[t]) return;
-    const uint64_t n_long = lpre[H];
-    order[is_long[t] ? lpre[t] : n_long + (rpre[t] - lpre[t])] = (uint32_t)t;
+    is_long[t] = (m == PR_MODE_RECODE && b1 - b0 >= FD_LONG_LIST_BYTES) ? 1u : 0u;
 }
 
 // ---- re-encode: wavefront per list, 64 lanes x 4 bytes per step.  W = false: new byte size, new last id, removed postings; W = true: new bytes.
@@ -84,37 +74,20 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
     const uint64_t t = order[g];
     const uint64_t b0 = A.offsets[t], b1 = A.offsets[t + 1];
     uint8_t *dst = W ? out_value + out_off[t] : nullptr;
-    uint32_t run_id = 0;          // old id of the last element decoded so far (the list's head is absolute: 0 + head)
     uint64_t prev_new = 0;        // new id + 1 of the last KEPT element so far, 0 = none yet
     uint32_t out_pos = 0, removed = 0;
-    bool prev_term = true;        // the byte before the step's first one ends a varint (the list start counts as one)
-    const uint64_t p0 = b0 + 4u * lane;
-    uint32_t cur = p0 < b1 ? fd_load4(A.value + p0) : 0u;
-    for (uint64_t base = b0; base < b1; base += 256) {
-        const uint64_t p = base + 4u * lane, pn = p + 256;
-        const uint32_t nxt = pn < b1 ? fd_load4(A.value + pn) : 0u;      // next step's word, in flight while this one is decoded
-        fd_step ds;
-        fd_decode_step(cur, nxt, p, b1, lane, prev_term, &ds);
-        const uint32_t sb = ds.sb, tb = ds.tb, dsum = ds.dsum;
-        const uint32_t *d = ds.d;
-        const uint32_t dinc = fd_wave_scan_add(dsum, lane);
-        uint32_t id = run_id + dinc - dsum;       // old id before this lane's first element
+    fd_wave_walk(A.value, b0, b1, lane, [&](const fd_step &ds, uint32_t id0) {      // id0: the OLD id before this lane's first element
         // keep / remap; the lane's last kept new id for the predecessor scan
-        uint32_t nid[4];
+        uint32_t nid[4] = {0, 0, 0, 0};
         uint32_t kmask = 0;
         uint64_t lane_last = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            nid[j] = 0;
-            if ((sb >> j) & 1u) {
-                id += d[j];
-                const uint64_t loc = (uint64_t)id - A.first_id;
-                if (id < A.first_id || loc >= A.S) { atomicOr(err, 1u); ++removed; continue; }
-                const uint64_t k0 = A.K[loc], k1 = A.K[loc + 1];      // kept iff the prefix count steps here: no dependent load of the mask
-                if (k1 != k0) { nid[j] = A.first_id + (uint32_t)k0; kmask |= 1u << j; lane_last = (uint64_t)nid[j] + 1u; }
-                else ++removed;
-            }
-        }
+        fd_lane_starts(ds, id0, [&](uint32_t j, uint32_t id) {
+            uint64_t loc;
+            if (!fd_id_local(id, A.first_id, A.S, &loc)) { atomicOr(err, FD_IXERR_DAMAGED); ++removed; return; }
+            const uint64_t k0 = A.K[loc], k1 = A.K[loc + 1];      // kept iff the prefix count steps here: no dependent load of the mask
+            if (k1 != k0) { nid[j] = A.first_id + (uint32_t)k0; kmask |= 1u << j; lane_last = (uint64_t)nid[j] + 1u; }
+            else ++removed;
+        });
         const uint64_t lmax = fd_wave_scan_max(lane_last, lane);
         uint64_t pred = __shfl_up(lmax, 1, FD_WAVE);      // new id + 1 of the last kept element before this lane (0: none)
         if (lane == 0) pred = 0;
@@ -136,25 +109,15 @@ __global__ __launch_bounds__(256) void k_pr_recode(pr_args A, const uint32_t *__
         if (W) {
             uint8_t *o = dst + out_pos + (linc - lsum);
 #pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                uint32_t v = nd[j];
-                for (uint32_t b = 0; b < ln[j]; ++b) {
-                    o[b] = (uint8_t)((v & 0x7fu) | (b + 1 < ln[j] ? 0x80u : 0u));
-                    v >>= 7;
-                }
-                o += ln[j];
-            }
+            for (uint32_t j = 0; j < 4; ++j) { fd_varint_store(o, nd[j], ln[j]); o += ln[j]; }
         }
         // carries into the next step
-        run_id += __shfl(dinc, 63, FD_WAVE);
-        out_pos += __shfl(linc, 63, FD_WAVE);
-        const uint64_t m63 = __shfl(lmax, 63, FD_WAVE);
+        out_pos += __shfl(linc, FD_WAVE - 1, FD_WAVE);
+        const uint64_t m63 = __shfl(lmax, FD_WAVE - 1, FD_WAVE);
         if (m63 > prev_new) prev_new = m63;
-        prev_term = (__shfl(tb, 63, FD_WAVE) >> 3) & 1u;
-        cur = nxt;
-    }
+    });
     if (!W) {
-        for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o, FD_WAVE);
+        removed = fd_wave_sum(removed);
         if (lane == 0) {
             sizes[t] = out_pos;
             new_last[t] = prev_new ? (uint32_t)(prev_new - 1u) : 0u;
@@ -212,10 +175,7 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
     reset_timings(c);
     hipStream_t st = c->stream;
     const uint64_t H = ix->n_hashes, S = n_keep;
-    if (!ix->last_ids && H) {      // a loaded index: last id of every list by one decode pass, kept with the index (as fdgpu_index_merge does)
-        StageTimer t(c, "prune_last_ids", ix->value_len + H * 12);
-        if (int rc = fd_index_last_ids(c, ix)) return rc;
-    }
+    if (int rc = fd_index_last_ids_staged(c, ix, "prune_last_ids")) return rc;
     const uint64_t Hx = std::max<uint64_t>(H, 1);
     HIPCHK(c, c->ws[WS_KEYS_B].ensure((S + 2) * 8 + S + 16));       // K[S + 1] (u64), then keep[S]
     HIPCHK(c, c->ws[WS_MISC0].ensure(Hx * 4));                      // sizes
@@ -244,9 +204,7 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
         fd_exclusive_scan<uint8_t>(kd, S, K, scan_tmp, tot, st);
         if (H) {
             hipLaunchKernelGGL(k_pr_plan, dim3(fd_grid(H, 256)), dim3(256), 0, st, A, sizes, nlast, mode, recode, is_long, err);
-            fd_exclusive_scan<uint8_t>(recode, H, pre_a, scan_tmp, tot, st);
-            fd_exclusive_scan<uint8_t>(is_long, H, pre_b, scan_tmp, tot, st);
-            hipLaunchKernelGGL(k_pr_order, dim3(fd_grid(H, 256)), dim3(256), 0, st, recode, is_long, pre_a, pre_b, H, order);
+            fd_order_long_first(recode, is_long, H, pre_a, pre_b, scan_tmp, tot, order, nullptr, st);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -276,8 +234,8 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
     HIPCHK(c, hipMemcpyAsync(&hv[2], tot + 1, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(&eb, err, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    if (eb & 2u) FAIL(c, FDGPU_ERANGE, "index remove: a posting list reaches 4 GiB");
-    if (eb & 1u) FAIL(c, FDGPU_EINVAL, "index remove: the index holds ids outside [first_id, first_id + n_structures)");
+    if (eb & FD_IXERR_LONG) FAIL(c, FDGPU_ERANGE, "index remove: a posting list reaches 4 GiB");
+    if (eb & FD_IXERR_DAMAGED) FAIL(c, FDGPU_EINVAL, "index remove: the index holds ids outside [first_id, first_id + n_structures)");
     Hn = hv[0]; Vn = hv[1];
     fdgpu_index *r = nullptr;
     if (int rc = fd_index_new(c, true, Hn, Vn, true, &r)) return rc;
@@ -295,7 +253,7 @@ extern "C" int fdgpu_index_remove(fdgpu_ctx *c, const fdgpu_index *ix, const uin
         }
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { c->err = std::string("index remove write: ") + hipGetErrorString(e); fdgpu_index_destroy(r); return FDGPU_EHIP; }
+    if (e != hipSuccess) { c->err = std::string("index remove write: ") + hipGetErrorString(e); return fd_index_op_failed(c, FDGPU_EHIP, &r); }
     *out = r;
     return FDGPU_OK;
 }

@@ -14,9 +14,6 @@
 #include "fd_api_common.h"
 #include "fd_postings.h"
 
-#define RB_ERR_DAMAGED 1u      // offsets that do not ascend inside the value bytes, a first varint that leaves its list, a head outside the id range
-#define RB_ERR_LONG 2u         // a list that would reach 4 GiB
-
 struct rb_args { const uint64_t *offsets; const uint8_t *value; const uint32_t *last_ids; uint64_t H, value_len, S; uint32_t first_id, shift; };
 
 // ---- sizes: thread per list.  Reads offsets[t], offsets[t + 1] and, only for b0 < b1 <= value_len, the 8 bytes at value + b0 (FD_VALUE_SLACK).
@@ -27,16 +24,17 @@ __global__ __launch_bounds__(256) void k_rb_sizes(rb_args A, uint32_t *__restric
     if (t >= A.H) return;
     const uint64_t b0 = A.offsets[t], b1 = A.offsets[t + 1];
     uint32_t sz = 0, head = 0, nf = 0, dl = 0, bad = 0;
-    if (b1 <= b0 || b1 > A.value_len) bad = RB_ERR_DAMAGED;
+    if (b1 <= b0 || b1 > A.value_len) bad = FD_IXERR_DAMAGED;
     else {
         const uint32_t f = fd_first_varint(A.value + b0, &nf);
+        uint64_t loc;
         // nf == 0: no terminator in five bytes.  A head below first_id (the downward shift would wrap) or past the last id (the upward one would)
-        if (nf == 0 || nf > b1 - b0 || f < A.first_id || (uint64_t)f - A.first_id >= A.S) bad = RB_ERR_DAMAGED;
+        if (nf == 0 || nf > b1 - b0 || !fd_id_local(f, A.first_id, A.S, &loc)) bad = FD_IXERR_DAMAGED;
         else {
             head = f + A.shift;      // modulo 2^32: shift = new_first_id - first_id; in range because f is and new_first_id + S <= 2^32
             dl = fd_varint_len(head);
             const uint64_t len = b1 - b0 - nf + dl;
-            if (len > 0xffffffffull) bad = RB_ERR_LONG;
+            if (len > 0xffffffffull) bad = FD_IXERR_LONG;
             else sz = (uint32_t)len;
         }
     }
@@ -91,10 +89,10 @@ static int rebase_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t new_first_i
     uint64_t hv[2] = {0, 0};      // new value length, error bits
     HIPCHK(c, hipMemcpyAsync(hv, tot, sizeof hv, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    if (hv[1] & RB_ERR_DAMAGED)
+    if (hv[1] & FD_IXERR_DAMAGED)
         FAIL(c, FDGPU_EINVAL, "index rebase: the index is damaged (offsets that do not ascend inside the value bytes, or a list whose first id is outside "
                               "[first_id, first_id + n_structures))");
-    if (hv[1] & RB_ERR_LONG) FAIL(c, FDGPU_ERANGE, "index rebase: a posting list reaches 4 GiB");
+    if (hv[1] & FD_IXERR_LONG) FAIL(c, FDGPU_ERANGE, "index rebase: a posting list reaches 4 GiB");
     nx->value_len = hv[0];
     HIPCHK(c, fd_index_block(c, hv[0] + FD_VALUE_SLACK, (void **)&nx->value, &nx->cap_value));
     {
@@ -112,11 +110,7 @@ extern "C" int fdgpu_index_rebase(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t 
     if (new_first_id > 0xffffffffull || new_first_id + ix->n_structures > 0xffffffffull) FAIL(c, FDGPU_ERANGE, "structure ids exceed 32 bits");
     fdgpu_index *nx = nullptr;
     const int rc = rebase_impl(c, ix, new_first_id, &nx);
-    if (rc != FDGPU_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        fdgpu_index_destroy(nx);
-        return rc;
-    }
+    if (rc != FDGPU_OK) return fd_index_op_failed(c, rc, &nx);
     *out = nx;
     return FDGPU_OK;
 }

@@ -9,9 +9,10 @@
 //                          re-base in k_mg_copy)
 //
 //   k_sp_plan         thread per list: head, last id, their parts, class, long-first order key
-//   k_sp_order        crossing lists in the order the decode kernels take them (long ones first, as k_pr_order) and each list's place in it
+//   order             crossing lists in the order the decode kernels take them (long ones first: fd_order_long_first, shared with k_prune.hip
+//                     and k_permute.hip) and each list's place in it
 //   k_sp_count        sizes pass over the VERBATIM lists, eight lanes per list: postings (terminator bytes), bytes and lists per part
-//   k_sp_cross<W>     wavefront per CROSSING list, 256 bytes per step (fd_decode_step): W = 0 bytes / postings / last id of every piece (lane r
+//   k_sp_cross<W>     wavefront per CROSSING list, 256 bytes per step (fd_decode_step; its own copy of the walk, see there): W = 0 bytes / postings / last id of every piece (lane r
 //                     keeps part r), W = 1 writes the pieces
 //   k_sp_cross_totals the crossing pieces' bytes / postings / lists per part
 //   per part:         k_sp_part_sizes -> two scans (slots, value offsets) -> k_sp_place (hashes / offsets / last ids at their slots, and where
@@ -24,7 +25,6 @@
 #include "fd_postings.h"
 
 #define SP_MAX_PARTS 64u
-#define SP_LONG_BYTES 16384u      // crossing lists at least this long are decoded first
 #define SP_PF_BAD 0xffu           // plan: the list holds an id outside the index's range (the call fails before anything is written)
 #define SP_TOT_BLOCKS 2048u       // blocks of the two totals kernels (each flushes its LDS histogram once)
 
@@ -54,23 +54,12 @@ __global__ __launch_bounds__(256) void k_sp_plan(sp_args A, const uint32_t *__re
     uint32_t nf = 0;
     const uint32_t f = fd_first_varint(A.value + b0, &nf), l = A.last_ids[t];
     uint32_t p = SP_PF_BAD, x = 0;
-    if (b1 - b0 > 0xffffffffull) atomicOr(err, 2u);                      // a list of 4 GiB or more: FDGPU_ERANGE
-    if (b1 <= b0 || f < A.first_id || l < f || (uint64_t)l - A.first_id >= A.S) atomicOr(err, 1u);
+    if (b1 - b0 > 0xffffffffull) atomicOr(err, FD_IXERR_LONG);           // a list of 4 GiB or more: FDGPU_ERANGE
+    if (b1 <= b0 || f < A.first_id || l < f || (uint64_t)l - A.first_id >= A.S) atomicOr(err, FD_IXERR_DAMAGED);
     else { p = sp_part(cuts, f); x = sp_part(cuts, l) != p ? 1u : 0u; }
     pf[t] = (uint8_t)p;
     cross[t] = (uint8_t)x;
-    is_long[t] = (x && b1 - b0 >= SP_LONG_BYTES) ? 1u : 0u;
-}
-
-// ---- order of the crossing lists: the long ones first, each class in list order; xidx[t] = the list's place in that order
-__global__ void k_sp_order(const uint8_t *__restrict__ cross, const uint8_t *__restrict__ is_long, const uint64_t *__restrict__ cpre,
-                           const uint64_t *__restrict__ lpre, uint64_t H, uint32_t *__restrict__ order, uint32_t *__restrict__ xidx) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= H || !cross[t]) return;
-    const uint64_t n_long = lpre[H];
-    const uint64_t g = is_long[t] ? lpre[t] : n_long + (cpre[t] - lpre[t]);
-    order[g] = (uint32_t)t;
-    xidx[t] = (uint32_t)g;
+    is_long[t] = (x && b1 - b0 >= FD_LONG_LIST_BYTES) ? 1u : 0u;
 }
 
 // per-part totals of a block: [0] lists, [1] bytes, [2] postings; one global atomic per non-zero entry when the block ends
@@ -117,6 +106,9 @@ __global__ __launch_bounds__(256) void k_sp_count(sp_args A, const uint8_t *__re
 
 // ---- CROSSING lists: wavefront per list, 64 lanes x 4 bytes per step.  W = false: tab[g][r] = {bytes, postings} and clast[g][r] of the list's piece
 // in part r (lane r keeps part r).  W = true: tab[g][r] holds, as one u64, where that piece starts in part r's value bytes; the pieces are written.
+// This kernel keeps its own copy of the walk of fd_wave_walk (fd_postings.h) and its 64-bit max scans: through fd_wave_walk its write pass measured
+// 0.8 % slower at 542,000 structures (profiles/index_ops_refactor_S542000.json; same operations, another branch layout), so it stays instruction
+// for instruction what it was.  A change to fd_wave_walk's carries has to be made here as well.
 template <bool W>
 __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__restrict__ cuts_g, const uint32_t *__restrict__ order, uint64_t n_cross,
                                                   uint2 *__restrict__ tab, uint32_t *__restrict__ clast, const sp_out *__restrict__ outs,
@@ -134,7 +126,7 @@ __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__r
     uint32_t run_id = 0;          // id of the last element decoded so far (the list's head is absolute: 0 + head)
     uint32_t cur_part1 = 0;       // part + 1 of the last element so far, 0 = none yet
     uint32_t piece_pos = 0;       // bytes of that element's piece so far
-    bool prev_term = true;
+    bool prev_term = true;        // the byte before the step's first one ends a varint (the list start counts as one)
     const uint64_t p0 = b0 + 4u * lane;
     uint32_t cur = p0 < b1 ? fd_load4(A.value + p0) : 0u;
     for (uint64_t base = b0; base < b1; base += 256) {
@@ -151,12 +143,12 @@ __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__r
             if ((s.sb >> j) & 1u) {
                 id += s.d[j];
                 idj[j] = id;
-                if (!W && (id < A.first_id || (uint64_t)id - A.first_id >= A.S)) atomicOr(err, 1u);
+                if (!W && (id < A.first_id || (uint64_t)id - A.first_id >= A.S)) atomicOr(err, FD_IXERR_DAMAGED);
                 pj[j] = min(sp_part(cuts, id), NP - 1u);
                 lane_last = pj[j] + 1u;
             }
         }
-        const uint32_t lmax = (uint32_t)fd_wave_scan_max(lane_last, lane);
+        const uint32_t lmax = (uint32_t)fd_wave_scan_max<uint64_t>(lane_last, lane);
         uint32_t pred = __shfl_up(lmax, 1, FD_WAVE);      // part + 1 of the last element before this lane's (0: none)
         if (lane == 0) pred = 0;
         if (cur_part1 > pred) pred = cur_part1;
@@ -166,7 +158,7 @@ __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__r
         for (uint32_t j = 0; j < 4; ++j) {
             ln[j] = 0;
             if ((s.sb >> j) & 1u) {
-                if (!W && pj[j] + 1u < q) atomicOr(err, 1u);      // ids that do not ascend: the write pass relies on ascending parts
+                if (!W && pj[j] + 1u < q) atomicOr(err, FD_IXERR_DAMAGED);      // ids that do not ascend: the write pass relies on ascending parts
                 const bool head = pj[j] + 1u != q;
                 hm |= (head ? 1u : 0u) << j;
                 ln[j] = head ? fd_varint_len(idj[j]) : s.nf[j];
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__r
             }
         }
         const uint32_t linc = fd_wave_scan_add(lsum, lane);
-        const uint32_t m63 = __shfl(lmax, 63, FD_WAVE);      // part + 1 of the step's last element (0: the step starts no varint)
+        const uint32_t m63 = __shfl(lmax, FD_WAVE - 1, FD_WAVE);      // part + 1 of the step's last element (0: the step starts no varint)
         if (!W) {
             // the step's elements lie in parts q_lo .. q_hi (ascending ids): one wave sum per part, lane q keeps it
             const uint32_t q_lo = cur_part1 ? cur_part1 - 1u : __shfl(pj[0], 0, FD_WAVE);
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__r
         uint32_t epfx[4], lane_head = 0, run = linc - lsum;
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) { epfx[j] = run; run += ln[j]; if ((hm >> j) & 1u) lane_head = epfx[j] + 1u; }
-        const uint32_t hmax = (uint32_t)fd_wave_scan_max(lane_head, lane);
+        const uint32_t hmax = (uint32_t)fd_wave_scan_max<uint64_t>(lane_head, lane);
         if (W) {
             uint32_t h1 = __shfl_up(hmax, 1, FD_WAVE);
             if (lane == 0) h1 = 0;
@@ -208,8 +200,7 @@ __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__r
                 uint8_t *o = (uint8_t *)__shfl(dstp, (int)pj[j], FD_WAVE) + (h1 ? epfx[j] - (h1 - 1u) : piece_pos + epfx[j]);
                 if (on) {
                     if ((hm >> j) & 1u) {
-                        uint32_t v = idj[j];
-                        for (uint32_t b = 0; b < ln[j]; ++b) { o[b] = (uint8_t)((v & 0x7fu) | (b + 1 < ln[j] ? 0x80u : 0u)); v >>= 7; }
+                        fd_varint_store(o, idj[j], ln[j]);
                     } else {
                         const unsigned long long src = s.win >> (8 * j);
                         for (uint32_t b = 0; b < ln[j]; ++b) o[b] = (uint8_t)(src >> (8 * b));
@@ -218,11 +209,11 @@ __global__ __launch_bounds__(256) void k_sp_cross(sp_args A, const uint32_t *__r
             }
         }
         // carries into the next step
-        const uint32_t total = __shfl(linc, 63, FD_WAVE), h63 = __shfl(hmax, 63, FD_WAVE);
+        const uint32_t total = __shfl(linc, FD_WAVE - 1, FD_WAVE), h63 = __shfl(hmax, FD_WAVE - 1, FD_WAVE);
         piece_pos = h63 ? total - (h63 - 1u) : piece_pos + total;
         if (m63) cur_part1 = m63;
-        run_id += __shfl(dinc, 63, FD_WAVE);
-        prev_term = (__shfl(s.tb, 63, FD_WAVE) >> 3) & 1u;
+        run_id += __shfl(dinc, FD_WAVE - 1, FD_WAVE);
+        prev_term = (__shfl(s.tb, FD_WAVE - 1, FD_WAVE) >> 3) & 1u;
         cur = nxt;
     }
     if (!W && lane < NP) {
@@ -292,10 +283,7 @@ static int split_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint32_t NP, const ui
     reset_timings(c);
     hipStream_t st = c->stream;
     const uint64_t H = ix->n_hashes;
-    if (!ix->last_ids && H) {      // a loaded index: last id of every list by one decode pass, kept with the index (as merge and remove do)
-        StageTimer t(c, "split_last_ids", ix->value_len + H * 12);
-        if (int rc = fd_index_last_ids(c, ix)) return rc;
-    }
+    if (int rc = fd_index_last_ids_staged(c, ix, "split_last_ids")) return rc;
     const uint64_t Hx = std::max<uint64_t>(H, 1);
     HIPCHK(c, c->ws[WS_MISC4].ensure(256 + SP_MAX_PARTS * sizeof(sp_out)));     // cuts, then the parts' arrays
     HIPCHK(c, c->ws[WS_MISC2].ensure(Hx * 4 + 16));                 // part of the head, crossing flag, long flag, non-empty flag of one part
@@ -326,9 +314,7 @@ static int split_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint32_t NP, const ui
         HIPCHK(c, hipMemsetAsync(tot + 1, 0, 8 + 3 * 64 * 8, st));
         if (H) {
             hipLaunchKernelGGL(k_sp_plan, dim3(fd_grid(H, 256)), dim3(256), 0, st, A, cuts_d, pf, cross, is_long, err);
-            fd_exclusive_scan<uint8_t>(cross, H, pre_a, scan_tmp, tot, st);
-            fd_exclusive_scan<uint8_t>(is_long, H, pre_b, scan_tmp, tot, st);
-            hipLaunchKernelGGL(k_sp_order, dim3(fd_grid(H, 256)), dim3(256), 0, st, cross, is_long, pre_a, pre_b, H, order, xidx);
+            fd_order_long_first(cross, is_long, H, pre_a, pre_b, scan_tmp, tot, order, xidx, st);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -354,8 +340,8 @@ static int split_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint32_t NP, const ui
     HIPCHK(c, hipMemcpyAsync(hv, tot + 1, sizeof hv, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     const uint32_t eb = (uint32_t)hv[0];
-    if (eb & 2u) FAIL(c, FDGPU_ERANGE, "index split: a posting list reaches 4 GiB");
-    if (eb & 1u) FAIL(c, FDGPU_EINVAL, "index split: the index holds ids outside [first_id, first_id + n_structures) or ids that do not ascend");
+    if (eb & FD_IXERR_LONG) FAIL(c, FDGPU_ERANGE, "index split: a posting list reaches 4 GiB");
+    if (eb & FD_IXERR_DAMAGED) FAIL(c, FDGPU_EINVAL, "index split: the index holds ids outside [first_id, first_id + n_structures) or ids that do not ascend");
     std::vector<sp_out> oh(NP);
     uint64_t v_out = 0;
     for (uint32_t r = 0; r < NP; ++r) {
@@ -395,11 +381,7 @@ extern "C" int fdgpu_index_split(fdgpu_ctx *c, const fdgpu_index *ix, uint32_t n
     if (bounds[n_parts] > 0xffffffffull) FAIL(c, FDGPU_ERANGE, "structure ids exceed 32 bits");
     std::vector<fdgpu_index *> parts(n_parts, nullptr);
     const int rc = split_impl(c, ix, n_parts, bounds, parts);
-    if (rc != FDGPU_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        for (auto p : parts) fdgpu_index_destroy(p);
-        return rc;
-    }
+    if (rc != FDGPU_OK) return fd_index_op_failed(c, rc, parts.data(), parts.size());
     for (uint32_t r = 0; r < n_parts; ++r) out[r] = parts[r];
     return FDGPU_OK;
 }

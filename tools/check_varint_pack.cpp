@@ -10,6 +10,7 @@ static inline int __ffsll(long long x) { return __builtin_ffsll(x); }
 template <typename T> static inline T __shfl_up(T v, int, int) { return v; }
 template <typename T> static inline T __shfl_down(T v, int, int) { return v; }
 template <typename T> static inline T __shfl(T v, int, int) { return v; }
+template <typename T> static inline T __shfl_xor(T v, int, int) { return v; }
 #include "../folddisco_amd/csrc/fd_postings.h"
 
 static uint64_t bad = 0, checked = 0;
