@@ -312,23 +312,47 @@ FD_HD void fd_pair_both_tab(const fd_frame &Fi, const fd_frame &Fj, uint32_t aai
 // and the decision is accepted only if |g| exceeds a bound M on how far the speculative (y, x) can be from the
 // operands the reference arithmetic produces.  Otherwise the pair is re-evaluated by the exact routine.
 //
-// Bounds (eps = 2^-24; r1, t1, s2, nv2 are unit vectors; c = v1 x v3 is computed by the SAME operations in both
-// evaluations, only what follows a normalisation differs):
+// The four fields are two dihedrals, each read in both directions: torsion1(i,j) = torsion(N_i, CA_i, CB_i, CB_j) and
+// torsion2(j,i) = torsion(CB_j, CB_i, CA_i, N_i) are one of them, torsion1(j,i) and torsion2(i,j) the other.  Only the
+// FORWARD operands (y, x) = (A.t1_i, r1_i.A) and (B.t1_j, r1_j.B) are formed; one decision serves both fields
+// (k4 = k1, k2 = k3) and is accepted only when it is provably the reference's for the forward AND the reversed chain.
+//
+// Bounds (eps = 2^-24; u = n^(cb-ca); r1, t1, u, A_ref are unit vectors to 4 eps; c = v1 x v3 is computed by the SAME
+// operations in every evaluation, only what follows a normalisation differs; no product underflows):
+//  forward, speculative against reference
 //   A  = c/|c|:           |A_f - A_ref|  <= 5 eps |A_k|                              (rsq 1 ulp + mul  vs  sqrt, div)
-//   y1 = A.t1, x1 = r1.A: |dy|, |dx|     <= 8 eps + 6 eps (product/sum roundings)     -> E1 = 32 eps
-//   X  = (-A) x nv2:      |dX_k|         <= 16 eps                                    (|dX| <= 28 eps)
-//   tA = X/|X|:           |dtA_k|        <= 56 eps/|X| + 10 eps
-//   y4 = s2.tA:           |dy4|          <= 97 eps/|X| + 24 eps                       -> 128 eps/|X| + 32 eps
-//   x4 = (-A).s2:         |dx4|          <= 20 eps                                    -> 32 eps
-//   reference decision:   |RN(y/x)| >= t  <=>  |y| - t|x| >= -eps t|x|  (|y| <= 1)    -> + 2^-20 in M
-// All bounds are multiplied by FD_SPEC_SAFETY = 4.  M = E_y + t E_x; signs must be certain (|y| > E_y, |x| > E_x),
-// which also routes zero / NaN / inf operands to the exact path.
+//   y  = A.t1, x = r1.A:  |dy|, |dx|     <= 8 eps + 6 eps (product/sum roundings)     -> E1 = 32 eps
+//  reversed reference chain against forward reference chain (dihedral of i; the other one alike with B, frame j)
+//   r' = n^((-v3) x (-v1)) = n^(v3 x v1) = -A_ref      bit for bit (the identities of the block above)
+//   s' = n^((ca-cb) x (n-ca)) = n^(v2' x v1') = -r1    bit for bit: this is s2 of fd_make_frame, whose operands are the
+//                                                      negated operands of r1's cross product, taken in the other order
+//   x' = r'.s' = (-A)(-r1): the same three products as x = r1.A, added in the same order      -> x' == x bit for bit
+//   t' = n^(r' x n^(ca-cb)) = n^(A_ref x u)  and  y' = s'.t' = -r1.t'.  As real numbers, with D = det(A_ref, r1, u):
+//        Y = A_ref.(r1 x u)/|r1 x u| = D/|r1 x u|,     Y' = -r1.(A_ref x u)/|A_ref x u| = D/|A_ref x u|
+//      - each chain against its real value: cross of two unit vectors |dX_k| <= 3 eps (|dX| <= 5.2 eps), normalisation
+//        (sum 3 eps, sqrt, div) 4 eps, so |dt| <= 10 eps; dot: 3 eps of its own + |dt|     -> 16 eps per chain
+//      - |Y - Y'| <= |Y| | |r1 x u|/|A_ref x u| - 1 |,  |r1 x u|^2 = |r1|^2 |u|^2 - (r1.u)^2:  8 eps for the norms
+//        (3.5 eps each) + ((r1.u)^2 + (A_ref.u)^2)/2.  Both vectors are perpendicular to u but for rounding, and only
+//        for a well-conditioned cross product: the last term is what the old bound's 1/|X| carried.
+//      - conditioning guard, from values at hand.  sin^2(v1, v3) = |c|^2/(len^2 d_CB^2) >= 2^-16 is required, tested as
+//        (rsA len_i)^2 cb_d2 <= 2^16 (FD_SPEC_COND_SIN2): then |A_ref.u| <= 2 sqrt3 eps/2^-8 + 4 eps < 2^-13.  r1.u is
+//        a property of the frame (N, CA, CB nearly collinear) and is measured: |r1.v1| <= 2^-12 len (FD_SPEC_COND_PERP),
+//        the sum evaluated to 3 eps len, gives |r1.u| < 2^-11.  Together ((r1.u)^2 + (A_ref.u)^2)/2 < 2.2 eps.
+//      so |y_ref - y'_ref| <= 16 + 16 + 8 + 2.2 eps                                          -> EREV = 64 eps
+//      (an f32 emulation of both chains on 2 10^6 random pairs: x bit patterns always equal, max |y - y'| = 6 eps)
+//   |y_f - y_ref| <= E1,  |y_f - y'_ref| <= E1 + EREV,  |x_f - x_ref| = |x_f - x'_ref| <= E1
+//   reference decision:   |RN(y/x)| >= t  <=>  |y| - t|x| >= -eps t|x|  (|y| <= 1)    -> + 2^-20 in M, for either chain
+// All bounds are multiplied by FD_SPEC_SAFETY = 4.  M = E_y + t E_x with E_y = E1 + EREV + slack, E_x = E1; signs must
+// be certain (|y| > E_y, |x| > E_x), which also routes zero / NaN / inf operands to the exact path.  Both guards are
+// tested positively: the v_rsq of a zero or denormal cross product (inf), len = 0 and NaN operands fail them.
+// FD_SPEC_E1 used to be shadowed by the wider margin of the reversed field's own evaluation, which refused every pair
+// the forward test would have; now E1, EREV and the two guards are all that stands between a threshold and a copied key.
 // =============================================================================================
-#define FD_SPEC_E1 7.62939453125e-06f      /* 4 * 32 eps = 2^-17 */
+#define FD_SPEC_E1 7.62939453125e-06f        /* 4 * 32 eps = 2^-17 */
 #define FD_SPEC_EY_SLACK 3.814697265625e-06f /* 4 * 2^-20 */
-#define FD_SPEC_EX4 7.62939453125e-06f     /* 4 * 32 eps */
-#define FD_SPEC_EY4_A 3.0517578125e-05f    /* 4 * 128 eps = 2^-15, times 1/|X| */
-#define FD_SPEC_EY4_B 7.62939453125e-06f   /* 4 * 32 eps */
+#define FD_SPEC_EREV 1.52587890625e-05f      /* 4 * 64 eps = 2^-16 */
+#define FD_SPEC_COND_SIN2 65536.0f           /* 1/sin^2 of the angle between CA->CB and CB_i->CB_j: at most 2^16 */
+#define FD_SPEC_COND_PERP 0.000244140625f    /* |r1.(cb-ca)| <= 2^-12 |cb-ca| */
 
 // tab_f: per quadrant m, 4 float thresholds (padding clamped to FLT_MAX) + packed keys (same layout as the exact table).
 // `margin` accumulates min(decision distance - bound) over everything decided here; the result is trusted iff the final
@@ -393,23 +417,24 @@ __device__ __forceinline__ bool fd_pair_both_spec(const fd_frame &Fi, const fd_f
         q_ca = fd_q(fd_dist(Fi.ca, Fj.ca), 2.0f, q.dist_disc);
         q_cb = fd_q(fd_sqrtf(cb_d2), 2.0f, q.dist_disc);
     }
-    float rsA, rsB, rsXA, rsXB;
+    float rsA, rsB;
     fd_v3 A = fd_normalize_spec(fd_cross(v1, v3), &rsA);
     fd_v3 B = fd_normalize_spec(fd_cross(v3, v2), &rsB);
     float margin = 1.0f;
-    const float E1y = FD_SPEC_E1 + FD_SPEC_EY_SLACK;
-    uint32_t k1 = fd_tor_key_spec(fd_dot(A, Fi.t1), fd_dot(Fi.r1, A), E1y, FD_SPEC_E1, tab_f, margin, fin);
-    uint32_t k3 = fd_tor_key_spec(fd_dot(B, Fj.t1), fd_dot(Fj.r1, B), E1y, FD_SPEC_E1, tab_f, margin, fin);
-    fd_v3 rB = fd_neg(B), rA = fd_neg(A);
-    fd_v3 tB = fd_normalize_spec(fd_cross(rB, Fj.nv2), &rsXB);
-    fd_v3 tA = fd_normalize_spec(fd_cross(rA, Fi.nv2), &rsXA);
-    const float E4c = FD_SPEC_EY4_B + FD_SPEC_EY_SLACK;
-    uint32_t k2 = fd_tor_key_spec(fd_dot(Fj.s2, tB), fd_dot(rB, Fj.s2), __builtin_fmaf(FD_SPEC_EY4_A, rsXB, E4c), FD_SPEC_EX4, tab_f, margin, fin);
-    uint32_t k4 = fd_tor_key_spec(fd_dot(Fi.s2, tA), fd_dot(rA, Fi.s2), __builtin_fmaf(FD_SPEC_EY4_A, rsXA, E4c), FD_SPEC_EX4, tab_f, margin, fin);
+    // one decision per dihedral: the forward operands, a margin that covers the reversed reference chain too (header comment)
+    const float Ey = FD_SPEC_E1 + FD_SPEC_EREV + FD_SPEC_EY_SLACK;
+    uint32_t k1 = fd_tor_key_spec(fd_dot(A, Fi.t1), fd_dot(Fi.r1, A), Ey, FD_SPEC_E1, tab_f, margin, fin);
+    uint32_t k3 = fd_tor_key_spec(fd_dot(B, Fj.t1), fd_dot(Fj.r1, B), Ey, FD_SPEC_E1, tab_f, margin, fin);
+    // conditioning of the two cross products behind each dihedral (not reference arithmetic: fused)
+    const float gA = rsA * Fi.len, gB = rsB * Fj.len;
+    const float pi = __builtin_fmaf(Fi.r1.z, v1.z, __builtin_fmaf(Fi.r1.y, v1.y, Fi.r1.x * v1.x));
+    const float pj = __builtin_fmaf(Fj.r1.z, v2.z, __builtin_fmaf(Fj.r1.y, v2.y, Fj.r1.x * v2.x));
+    const bool cond = (gA * gA * cb_d2 <= FD_SPEC_COND_SIN2) && (gB * gB * cb_d2 <= FD_SPEC_COND_SIN2) &&
+                      (__builtin_fabsf(pi) <= FD_SPEC_COND_PERP * Fi.len) && (__builtin_fabsf(pj) <= FD_SPEC_COND_PERP * Fj.len);
     uint32_t mid = q_ca << 16 | q_cb << 12 | kth << 8;
-    *h_ij = aai << 25 | aaj << 20 | mid | k1 << 4 | k2;
-    *h_ji = aaj << 25 | aai << 20 | mid | k3 << 4 | k4;
-    // rsq of a zero / denormal cross product is inf: margins become NaN or -inf; NaN must fail, so test "> 0" positively
-    return fin && (margin > 0.0f) && (rsXA < 3.0e38f) && (rsXB < 3.0e38f) && (rsA < 3.0e38f) && (rsB < 3.0e38f);
+    *h_ij = aai << 25 | aaj << 20 | mid | k1 << 4 | k3;
+    *h_ji = aaj << 25 | aai << 20 | mid | k3 << 4 | k1;
+    // rsq of a zero / denormal cross product is inf: it fails `cond`; a NaN margin must fail too, so test "> 0" positively
+    return fin && cond && (margin > 0.0f);
 }
 #endif

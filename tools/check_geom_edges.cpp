@@ -74,6 +74,7 @@ int main(int argc, char **argv) {
         for (int k = 0; k < 4; ++k) if (tab_f[7 + 5 * m + k] > 0x7f7fffffu) tab_f[7 + 5 * m + k] = 0x7f7fffffu;
     const bool dist_tab = tab_form && q.dist_disc == 1.0f / ((20.0f - 2.0f) / 15.0f);
     long spec_tried = 0, spec_accepted = 0;
+    long rev_differ = 0, rev_taken = 0;      // tried pairs on which the oracle's two readings of one dihedral give different keys; those the speculation accepted
     std::vector<uint32_t> off32(off.begin(), off.end());
     fd_batch_view B = {N.data(), CA.data(), CB.data(), aa.data(), ok.data(), off32.data(), nullptr, nullptr, S, 0};
     long pairs = 0, accepted = 0, bad = 0;
@@ -118,12 +119,18 @@ int main(int argc, char **argv) {
                         }
                         if (!what && tab_form) {       // speculative torsions: an ACCEPTED result must be the reference's; a refusal takes the table form above
                             ++spec_tried;
+                            // tor1(i,j) / tor2(j,i) and tor1(j,i) / tor2(i,j) are one dihedral each, read in both directions (fd_geom.h): the speculation
+                            // decides each once, so a pair on which the oracle's two readings differ must be refused
+                            const bool differ = ((want >> 4) & 15u) != (want_ji & 15u) || (want & 15u) != ((want_ji >> 4) & 15u);
+                            rev_differ += differ;
                             if (fd_pair_both_spec<false>(F[i], F[j], aa[gi], aa[gj], q, tab, tab_f, &h_ij, &h_ji)) {
                                 ++spec_accepted;
+                                rev_taken += differ;
                                 if ((got = h_ij) != want) what = "speculative";
                                 else if ((got = h_ji) != want_ji) what = "speculative (second orientation)";
                             }
                             if (!what && dist_tab && fd_pair_both_spec<true>(F[i], F[j], aa[gi], aa[gj], q, tab, tab_f, &h_ij, &h_ji, fd_dist_thr_bits)) {
+                                rev_taken += differ;
                                 if ((got = h_ij) != want) what = "speculative + distance table";
                                 else if ((got = h_ji) != want_ji) what = "speculative + distance table (second orientation)";
                             }
@@ -134,7 +141,7 @@ int main(int argc, char **argv) {
             }
         fdo_structure_free(st);
     }
-    printf("type %u bins %u/%u cutoff %g: %u structures, %ld ordered pairs, %ld accepted, speculation %ld of %ld, mismatches: %ld\n", type, nbd, nba, cutoff, S, pairs, accepted,
-           spec_accepted, spec_tried, bad);
+    printf("type %u bins %u/%u cutoff %g: %u structures, %ld ordered pairs, %ld accepted, speculation %ld of %ld, mismatches: %ld; reversed readings differ on %ld, speculation took %ld of them\n", type, nbd, nba, cutoff, S, pairs, accepted,
+           spec_accepted, spec_tried, bad, rev_differ, rev_taken);
     return bad ? 1 : 0;
 }
