@@ -331,8 +331,8 @@ def cmd_update(a):
     from folddisco_amd import indexio, structure
     cfg, keep, add_paths = plan["cfg"], plan["keep"], plan["add_paths"]
     # hash parameters of the existing index, never the command line's defaults
-    a.distance, a.angle, a.grid = int(cfg.get("num_bin_dist", 0)), int(cfg.get("num_bin_angle", 0)), float(cfg.get("grid_width", 20.0))
-    a.hash_type, a.multi = hash_type_index(cfg.get("hash_type", "PDBTrRosetta")), cfg.get("multiple_bin")
+    hp = _type_hash_params(cfg)
+    a.distance, a.angle, a.grid, a.hash_type, a.multi = hp["nbin_dist"], hp["nbin_angle"], hp["dist_cutoff"], hp["hash_type"], cfg.get("multiple_bin")
     a.fc = None
     n_kept = int(keep.sum())
     ctx = fd.Context(a.device)
@@ -424,25 +424,197 @@ def _stop_if_unsound(report, what):
         sys.exit(1)
 
 
+def _type_hash_params(cfg) -> dict:
+    """the hash parameters PREFIX.type records, as the keywords of FolddiscoIndex.build / get_geometric_hash_as_u32 (multiple_bins apart)"""
+    return dict(nbin_dist=int(cfg.get("num_bin_dist", 0)), nbin_angle=int(cfg.get("num_bin_angle", 0)), dist_cutoff=float(cfg.get("grid_width", 20.0)),
+                hash_type=hash_type_index(cfg.get("hash_type", "PDBTrRosetta")))
+
+
+def _windows(ids, width, n):
+    """windows [lo, hi) of at most `width` structures that cover the ascending unique ids: -> (lo, hi, first, end) with ids[first:end] inside"""
+    k = 0
+    while k < len(ids):
+        lo = int(ids[k])
+        hi = min(lo + width, n)
+        end = int(np.searchsorted(ids, hi))
+        yield lo, hi, k, end
+        k = end
+
+
+def _structures_check(a, ctx, ix, store, cfg, n, tids):
+    """`verify --structures`: does the index describe these coordinates?  Per window of structures: the index's rows (fdgpu_index_rows) against
+    the hashes of the store's slice (fdgpu_hash_batch with the parameters of PREFIX.type).  -> (structures, hashes) compared; the first
+    structure that differs ends the command with status 1"""
+    import folddisco_amd as fd
+    hp = _type_hash_params(cfg)
+    raw = hp["hash_type"] in (2, 4, 5, 6)            # encodings the hasher serves in the raw order only: sorted and made unique here
+    total = 0
+    for lo, hi, _, _ in _windows(np.arange(n), a.window, n):
+        got_h, got_off = ix.rows(lo, hi)
+        batch = ctx.upload(store.slice(lo, hi).ps)
+        want_h, want_off = fd.get_geometric_hash_as_u32(ctx, batch, sort_dedup=not raw, **hp)
+        del batch
+        if raw:
+            owner = np.repeat(np.arange(hi - lo, dtype=np.uint64), np.diff(want_off.astype(np.int64)))
+            key = np.unique(owner << np.uint64(32) | want_h.astype(np.uint64))
+            want_h = (key & np.uint64(0xffffffff)).astype(np.uint32)
+            want_off = np.searchsorted(key >> np.uint64(32), np.arange(hi - lo + 1, dtype=np.uint64)).astype(np.uint64)
+        total += len(got_h)
+        if np.array_equal(got_off, want_off) and np.array_equal(got_h, want_h):
+            continue
+        for s in range(hi - lo):
+            g, w = got_h[int(got_off[s]):int(got_off[s + 1])], want_h[int(want_off[s]):int(want_off[s + 1])]
+            if not np.array_equal(g, w):
+                only_ix, only_co = np.setdiff1d(g, w), np.setdiff1d(w, g)
+                show = lambda x: str(int(x[0])) if len(x) else "none"
+                print(f"[FAIL] structure {lo + s} {tids[lo + s]}: index row {len(g)} hashes, coordinates {len(w)}, first hash only in the index / "
+                      f"only in the coordinates: {show(only_ix)} / {show(only_co)}")
+                sys.exit(1)
+    return n, total
+
+
 def cmd_verify(a):
     """`verify`: is the index at PREFIX well formed?  File checks (sizes, .lookup ids, chunk_size), then every posting list decoded once, on the
-    device (fdgpu_index_verify) or with --host on the CPU (fdgpu_verify_host; no device is opened).  Exit status 0 / 1, 2 for unreadable input."""
+    device (fdgpu_index_verify) or with --host on the CPU (fdgpu_verify_host; no device is opened).  With --structures, behind those: does the
+    index describe the coordinates of its store (_structures_check)?  Exit status 0 / 1, 2 for unreadable input."""
     from folddisco_amd import indexio
     v, h, o, n = _verify_files(a.index)
     if os.path.isfile(a.index + ".coords"):      # part of the file checks: header, sections, res_off, stamp
         st = _open_store(a.index + ".coords", a.index, n)
         print(f"[OK] {a.index}.coords: {st.n_struct} structures, {st.n_res} residues, stamp matches the index files")
+    if a.structures:                             # its refusals come before any device is opened
+        if a.host:
+            sys.exit("[FAIL] verify --structures: there is no host hasher in the library; run it without --host")
+        if a.window < 1:
+            sys.exit("[FAIL] verify --structures: --window must be at least 1")
+        cfg = indexio.load_type(a.index + ".type")
+        if cfg.get("multiple_bin"):
+            sys.exit("[FAIL] verify --structures: the index was built with --multiple-bins, which the batch hasher does not serve")
+        cpath = a.coords or a.index + ".coords"
+        if not os.path.isfile(cpath):
+            sys.exit(f"[FAIL] verify --structures: {cpath} not found; run `coords -i {a.index}` first" if not a.coords else
+                     f"[FAIL] verify --structures: {cpath} not found")
+        if a.coords:
+            st = _open_store(cpath, a.index, n)
+        tids = [r.rstrip("\n").split("\t")[1] for r in indexio.read_lookup_rows(a.index + ".lookup")]
     if a.host:
         rep = indexio.verify_host(v, h, o, n, threads=a.threads)
     else:
         import folddisco_amd as fd
         ctx = fd.Context(a.device)
-        rep = fd.FolddiscoIndex.load(ctx, h, o, v, n).verify()
+        ix = fd.FolddiscoIndex.load(ctx, h, o, v, n)
+        rep = ix.verify()
     print(rep)
     if a.verbose:
         print(f"[INFO] {a.index}: {len(h)} hashes, {len(v)} value bytes, {n} structures; checked on the {'host' if a.host else 'device'}"
               + ("" if rep.list_stage else "; the offsets table is damaged, the lists were not decoded"), file=sys.stderr)
+    if a.structures and rep.ok:
+        ns, nh = _structures_check(a, ctx, ix, st, cfg, n, tids)
+        print(f"[OK] {a.index}: the index describes the coordinates of {cpath}: {ns} structures, {nh} hashes compared")
     sys.exit(0 if rep.ok else 1)
+
+
+def _rows_plan(a):
+    """everything `rows` decides before it opens a device: -> (structures of the index, chosen ids in the order asked for, their tids).  Status 2
+    for missing or unreadable files, status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
+    from folddisco_amd import indexio
+    if a.range is not None and a.tids is not None:
+        sys.exit("[FAIL] rows: give at most one of --range LO:HI and --tids FILE")
+    if a.window < 1:
+        sys.exit("[FAIL] rows: --window must be at least 1")
+    for f in [a.index + ext for ext in INDEX_FILES] + ([a.tids] if a.tids is not None else []):
+        if not os.path.isfile(f):
+            print(f"[FAIL] {f} not found", file=sys.stderr)
+            sys.exit(2)
+    try:
+        bad = indexio.check_index_files(a.index)
+        tids = [r.rstrip("\n").split("\t")[1] for r in indexio.read_lookup_rows(a.index + ".lookup")]
+        asked = None
+        if a.tids is not None:
+            with open(a.tids) as f:
+                asked = [line.strip() for line in f if line.strip()]
+    except (OSError, ValueError, UnicodeDecodeError) as e:
+        print(f"[FAIL] rows: unreadable input ({e})", file=sys.stderr)
+        sys.exit(2)
+    if bad:
+        print("[FAIL] index files are inconsistent: " + "; ".join(bad))
+        sys.exit(1)
+    n = len(tids)
+    if asked is not None:
+        where = {}
+        for k, t in enumerate(tids):
+            where.setdefault(t, []).append(k)
+        unknown = [t for t in dict.fromkeys(asked) if t not in where]
+        if unknown:
+            print(f"[FAIL] rows: {len(unknown)} tid(s) of {a.tids} are not in {a.index}.lookup: " + ", ".join(unknown[:10]) + (" ..." if len(unknown) > 10 else ""))
+            sys.exit(1)
+        ids = np.array([k for t in asked for k in where[t]], dtype=np.int64)      # the file's order; every row that carries the tid
+    else:
+        lo, hi = 0, n
+        if a.range is not None:
+            try:
+                lo_s, hi_s = a.range.split(":")
+                lo, hi = int(lo_s) if lo_s else 0, int(hi_s) if hi_s else n
+            except ValueError:
+                sys.exit(f"[FAIL] rows: --range {a.range}: LO:HI expected")
+            if not 0 <= lo <= hi <= n:
+                print(f"[FAIL] rows: --range {a.range} is not inside the index's {n} structures")
+                sys.exit(1)
+        ids = np.arange(lo, hi, dtype=np.int64)
+    return n, ids, tids
+
+
+def cmd_rows(a):
+    """`rows`: the hashes of chosen structures read back from the index at PREFIX (the transposed index), as OUT.npz with hashes, row_off, ids and
+    tids: hashes[row_off[k]: row_off[k + 1]] are the ascending hashes whose posting lists hold structure ids[k].  The index is walked in windows
+    of --window structures that cover the chosen ids, on the device (fdgpu_index_rows) or with --host on the CPU (fdgpu_rows_host; no device is
+    opened); rows that were not asked for are dropped on the host.  No structure file is read."""
+    from folddisco_amd import indexio
+    n, ids, tids = _rows_plan(a)
+    if not a.output:
+        sys.exit("[FAIL] rows: -o OUT.npz is required")
+    try:
+        v, h, o = indexio.read_index_files(a.index)
+        if a.host:
+            if a.verify:
+                _stop_if_unsound(indexio.verify_host(v, h, o, n, threads=a.threads), a.index)
+            window = lambda lo, hi: indexio.rows_host(v, h, o, n, lo=lo, hi=hi, threads=a.threads)
+        else:
+            import folddisco_amd as fd
+            ctx = fd.Context(a.device)
+            ix = fd.FolddiscoIndex.load(ctx, h, o, v, n)
+            del v, h, o
+            if a.verify:                             # before the walk uses its offsets as addresses
+                _stop_if_unsound(ix.verify(), a.index)
+            window = ix.rows
+        uniq = np.unique(ids)
+        piece = [None] * len(uniq)                   # the row of every chosen structure
+        n_windows = 0
+        for lo, hi, k0, k1 in _windows(uniq, a.window, n):
+            wh, woff = window(lo, hi)
+            n_windows += 1
+            for k in range(k0, k1):
+                s = int(uniq[k]) - lo
+                piece[k] = wh[int(woff[s]):int(woff[s + 1])]
+        at = np.searchsorted(uniq, ids)
+        lens = np.array([len(piece[k]) for k in at], dtype=np.uint64)
+        row_off = np.zeros(len(ids) + 1, np.uint64)
+        row_off[1:] = np.cumsum(lens, dtype=np.uint64)
+        hashes = np.concatenate([piece[k] for k in at]).astype(np.uint32, copy=False) if len(ids) else np.zeros(0, np.uint32)
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] rows: {e}", file=sys.stderr)
+        sys.exit(2 if isinstance(e, OSError) else 1)
+    tmp = f"{a.output}.rows-tmp{os.getpid()}"
+    try:
+        with open(tmp, "wb") as f:
+            np.savez(f, hashes=hashes, row_off=row_off, ids=ids.astype(np.uint64), tids=np.array([tids[k] for k in ids], dtype=str))
+        os.replace(tmp, a.output)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    print(f"[OK] {a.output}: {len(ids)} structures, {len(hashes)} hashes, longest row {int(lens.max()) if len(ids) else 0}")
+    if a.verbose:
+        print(f"[INFO] rows of {a.index} on the {'host' if a.host else 'device'}: {n_windows} window(s) of up to {a.window} structures", file=sys.stderr)
 
 
 def _reshard_plan(a):
@@ -1042,6 +1214,21 @@ def main(argv=None):
     pv.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
     pv.add_argument("--device", type=int, default=0)
     pv.add_argument("-v", "--verbose", action="store_true")
+    pv.add_argument("--structures", action="store_true", help="also check that the index describes the coordinate store: every structure's row of the "
+                    "index against the hashes of its coordinates (device only)")
+    pv.add_argument("--coords", default="", help="coordinate store of --structures (default: PREFIX.coords)")
+    pv.add_argument("--window", type=int, default=16384, help="structures compared per step of --structures")
+    pw = sub.add_parser("rows")                                      # the hashes of chosen structures, read back from the index (no counterpart in the reference)
+    pw.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
+    pw.add_argument("-o", "--output", default="", help="the .npz file to write: hashes, row_off, ids, tids")
+    pw.add_argument("--range", default=None, help="LO:HI, the structure ids LO .. HI - 1 (default: every structure)")
+    pw.add_argument("--tids", default=None, help="text file with one tid per line (column 2 of PREFIX.lookup); the rows come out in the file's order")
+    pw.add_argument("--window", type=int, default=16384, help="structures per walk over the index")
+    pw.add_argument("--host", action="store_true", help="walk the index on the CPU (no device is opened)")
+    pw.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    pw.add_argument("--device", type=int, default=0)
+    pw.add_argument("--verify", action="store_true", help="check the loaded index first (see `verify`) and stop with status 1 if it is damaged")
+    pw.add_argument("-v", "--verbose", action="store_true")
     pr = sub.add_parser("reshard")                                   # one index <-> shards by structure id range (no counterpart in the reference)
     pr.add_argument("-i", "--index", required=True)
     pr.add_argument("--to", type=int, required=True, help="shards to write (PREFIX.shard<r>ofW); 1 writes the single index")
@@ -1109,6 +1296,9 @@ def main(argv=None):
         return
     if a.cmd == "verify":
         cmd_verify(a)
+        return
+    if a.cmd == "rows":
+        cmd_rows(a)
         return
     if a.cmd == "reshard":
         cmd_reshard(a)

@@ -206,6 +206,9 @@ SYMBOLS = [
     ("fdgpu_index_permute", C.c_int, [VP, VP, u32p, C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_permute_host", C.c_int, [u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, C.c_uint32, C.POINTER(u8p), u64p,
                                      C.POINTER(u32p), C.POINTER(u64p)]),
+    ("fdgpu_index_rows", C.c_int, [VP, VP, C.c_uint64, C.c_uint64, C.POINTER(u32p), C.POINTER(u64p)]),
+    ("fdgpu_rows_host", C.c_int, [u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(u32p),
+                                  C.POINTER(u64p)]),
     ("fdgpu_index_verify", C.c_int, [VP, VP, C.POINTER(VerifyReportC)]),
     ("fdgpu_verify_host", C.c_int, [u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyReportC)]),
     ("fdgpu_posting_bytes", C.c_int, [VP, VP, u32p, C.c_uint64, u64p]),

@@ -331,6 +331,20 @@ class FolddiscoIndex:
         self.ctx.check(self.ctx.L.fdgpu_index_permute(self.ctx.h, self.h, _ptr(p, u32p), len(p), C.byref(h)))
         return FolddiscoIndex(self.ctx, h, self.n_structures, self.first_id)
 
+    def rows(self, lo=None, hi=None):
+        """rows of the transposed index (fdgpu_index_rows): for the structures lo .. hi - 1 (absolute ids; default: the whole index)
+        -> (hashes u32[...], row_off u64[hi - lo + 1]); hashes[row_off[k]: row_off[k + 1]] are the ascending hashes whose posting lists hold
+        structure lo + k — for an index built over a batch, get_geometric_hash_as_u32(sort_dedup=True) of those structures.  The index is
+        not changed"""
+        lo = self.first_id if lo is None else int(lo)
+        hi = self.first_id + self.n_structures if hi is None else int(hi)
+        if lo < 0 or hi < 0:
+            raise ValueError("rows: lo and hi are absolute structure ids")
+        hp, op = u32p(), u64p()
+        self.ctx.check(self.ctx.L.fdgpu_index_rows(self.ctx.h, self.h, lo, hi, C.byref(hp), C.byref(op)))
+        off = _lib.owned_view(self.ctx.L, op, (hi - lo + 1) * 8, np.uint64)
+        return _lib.owned_view(self.ctx.L, hp, int(off[-1]) * 4, np.uint32), off
+
     # ---- one on-disk index from N ranks (fd_shard_index.hip; SURVEY §8e row 2, Option A)
     def range_bounds(self, n_ranges: int) -> np.ndarray:
         """n_ranges - 1 ascending hash values cutting this index into ranges of about equal posting bytes"""

@@ -1,7 +1,8 @@
 // fd_postings.h — the posting-list byte format, stated once for the encoder (k_index.hip), the device merge (k_merge.hip), the removal
-// (k_prune.hip), the split (k_split.hip), the rebase (k_rebase.hip), the reorder (k_permute.hip), the checker's first varints (k_verify.hip)
-// and the host merge (fdgpu_merge_subindices).  Its host-safe part — the varint writer and reader — is fd_postings_host.h, which the host
-// forms of those operations (fd_split_host.cpp, fd_rebase_host.cpp, fd_permute_host.cpp) take without this header's HIP include.
+// (k_prune.hip), the split (k_split.hip), the rebase (k_rebase.hip), the reorder (k_permute.hip), the rows (k_rows.hip), the checker's first
+// varints (k_verify.hip) and the host merge (fdgpu_merge_subindices).  Its host-safe part — the varint writer and reader — is
+// fd_postings_host.h, which the host forms of those operations (fd_split_host.cpp, fd_rebase_host.cpp, fd_permute_host.cpp, fd_rows_host.cpp)
+// take without this header's HIP include.
 //
 // A posting list is the ascending ids of the structures that hold one hash, as LEB128 varints (7-bit groups, least significant first; bit 7
 // set = another byte follows; 0 is one 0x00 byte; a u32 takes at most five bytes; codec of indextable.rs:93-99, 397-418).  The first varint
@@ -100,8 +101,8 @@ __device__ __forceinline__ T fd_wave_scan_max(T v, uint32_t lane) {
     return v;
 }
 
-// ---- a wavefront's walk over one list, 256 bytes per step (four per lane).  fd_wave_walk: the removal (k_pr_recode) and the reorder's SORT class
-// (k_pm_sort).  fd_decode_step alone, with carries of their own: the reorder's BITMAP class (k_pm_bitmap: eight wavefronts per step, ids through
+// ---- a wavefront's walk over one list, 256 bytes per step (four per lane).  fd_wave_walk: the removal (k_pr_recode), the reorder's SORT class
+// (k_pm_sort) and the rows (k_rw_walk).  fd_decode_step alone, with carries of their own: the reorder's BITMAP class (k_pm_bitmap: eight wavefronts per step, ids through
 // fd_lane_starts) and the split (k_sp_cross, which keeps a copy of fd_wave_walk's loop for its speed — see there)
 __device__ __forceinline__ uint32_t fd_load4(const uint8_t *p) { uint32_t w; __builtin_memcpy(&w, p, 4); return w; }
 // One step: w = the lane's four bytes at p (0 beyond the list's end b1), nxt = its four bytes of the next step, prev_term = the byte before the

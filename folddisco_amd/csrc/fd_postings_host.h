@@ -1,5 +1,5 @@
 // fd_postings_host.h — the part of the posting-list codec (fd_postings.h) that needs no device: the varint writer and a strict reader, and what
-// the host forms of the index operations (fd_split_host.cpp, fd_rebase_host.cpp, fd_permute_host.cpp, fd_verify_host.cpp) share around them —
+// the host forms of the index operations (fd_split_host.cpp, fd_rebase_host.cpp, fd_permute_host.cpp, fd_rows_host.cpp, fd_verify_host.cpp) share around them —
 // the thread fan-out over slot ranges and the packaging of a result.  Plain C++, no HIP include: the host files build with a plain host compiler.
 #pragma once
 #include <stdint.h>

@@ -896,7 +896,7 @@ extern "C" int fdgpu_debug_encode_stream(fdgpu_ctx *c, const uint32_t *hashes, c
 // page faults in parallel (the destination is asked for huge pages).
 #define FD_PIN_SLOTS 16
 #define FD_PIN_BYTES ((size_t)16 << 20)
-static hipError_t fd_d2h_big(fdgpu_ctx *c, void *dst, const void *src, size_t bytes) {
+hipError_t fd_d2h_big(fdgpu_ctx *c, void *dst, const void *src, size_t bytes) {
     if (bytes < 4 * FD_PIN_BYTES) return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
     for (int k = 0; k < FD_PIN_SLOTS; ++k) {
         hipError_t e = hipSuccess;

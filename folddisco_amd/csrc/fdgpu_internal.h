@@ -256,7 +256,7 @@ int fd_index_last_ids(fdgpu_ctx *c, const fdgpu_index *ix);      // k_merge.hip:
 hipError_t fd_count_postings(fdgpu_ctx *c, const uint8_t *value, uint64_t n, uint64_t *out);      // terminators of n value bytes; synchronises
 static inline unsigned fd_grid(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
 
-// ---- what the operations on a resident index share (k_prune.hip, k_split.hip, k_rebase.hip, k_permute.hip)
+// ---- what the operations on a resident index share (k_prune.hip, k_split.hip, k_rebase.hip, k_permute.hip, k_rows.hip)
 // error bits their kernels raise; the message is the operation's own
 #define FD_IXERR_DAMAGED 1u      // offsets that do not ascend inside the value bytes, a varint that leaves its list, an id outside [first_id, first_id + n_structures)
 #define FD_IXERR_LONG 2u         // a list of 4 GiB or more
@@ -314,6 +314,7 @@ int fd_retrieve_batch_dev(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t *re
                           const fd_query_map *const *qms, const fdgpu_batch *qb, const uint32_t *q_struct, const fd_hash_params *p, float ca_distance_cutoff,
                           uint32_t node_count, uint32_t partial_fit, fd_match_rec **matches, uint64_t **match_off, int32_t **residues, uint64_t **res_off, fd_rb_dev_out *dev);
 hipError_t fd_d2h_to_file(fdgpu_ctx *c, int fd, uint64_t file_off, const void *src, size_t bytes, std::atomic<int> *io_err);      // fdgpu_api.hip: device array -> file region through the pinned slots
+hipError_t fd_d2h_big(fdgpu_ctx *c, void *dst, const void *src, size_t bytes);      // fdgpu_api.hip: a large device array -> pageable host memory through the pinned slots (small ones: one asynchronous copy); the caller synchronises
 void *fd_out_alloc(size_t bytes, bool pinned = false);      // result arrays of the hot query paths: recycled blocks (fdgpu_api.hip); released with fdgpu_free like any other output
 
 // kernels / launchers implemented in the k_*.hip files

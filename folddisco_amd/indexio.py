@@ -417,6 +417,31 @@ def permute_host(value, hashes, offsets, new_id, first_id: int = 0, threads: int
     return v, h, o
 
 
+def rows_host(value, hashes, offsets, n_structures: int, first_id: int = 0, lo=None, hi=None, threads: int = 1):
+    """rows of the transposed index from host arrays (fdgpu_rows_host: no context, no device): for the structures lo .. hi - 1 (absolute ids;
+    default: the whole index) -> (hashes u32[...], row_off u64[hi - lo + 1]), hashes[row_off[k]: row_off[k + 1]] = the ascending hashes whose
+    posting lists hold structure lo + k.  The result does not depend on `threads`.  Raises ValueError with the library's code in it: -1
+    (FDGPU_EINVAL) for a window outside the index or a damaged index, -4 (FDGPU_ERANGE) for a list of 4 GiB or 2^32 postings in the window"""
+    value = np.ascontiguousarray(value, dtype=np.uint8)
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(hashes) + 1:
+        raise ValueError(f"offsets: {len(hashes) + 1} entries expected, got {len(offsets)}")
+    lo = int(first_id) if lo is None else int(lo)
+    hi = int(first_id) + int(n_structures) if hi is None else int(hi)
+    if lo < 0 or hi < lo:
+        raise ValueError("fdgpu_rows_host failed (-1): lo <= hi, absolute structure ids, expected")
+    L = _lib.load()
+    oh, oo = u32p(), u64p()
+    rc = L.fdgpu_rows_host(hashes.ctypes.data_as(u32p), offsets.ctypes.data_as(u64p), len(hashes), value.ctypes.data_as(u8p), len(value), int(first_id),
+                           int(n_structures), lo, hi, max(int(threads), 1), C.byref(oh), C.byref(oo))
+    if rc != 0:
+        raise ValueError(f"fdgpu_rows_host failed ({rc}): " + ("a list reaches 4 GiB or the window holds 2^32 postings" if rc == -4 else
+                         "the window is not inside the index, or the index is damaged or holds ids outside [first_id, first_id + n_structures)"))
+    off = _lib.owned_view(L, oo, (hi - lo + 1) * 8, np.uint64)
+    return _lib.owned_view(L, oh, int(off[-1]) * 4, np.uint32), off
+
+
 def permute_lookup_rows(rows, new_id, keep_db_keys: bool):
     """the rows of PREFIX.lookup after a reorder: row k moves to position new_id[k], tid, nres and plddt verbatim, the id renumbered 0 .. n - 1; the
     db_key column renumbered with it for a file-built index (there it equals the id) and kept for a Foldcomp-built one (its database key) -- the

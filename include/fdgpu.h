@@ -578,6 +578,24 @@ int fdgpu_permute_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t
                        const uint32_t *new_id, uint64_t n, uint32_t n_threads, uint8_t **out_value, uint64_t *out_value_len,
                        uint32_t **out_hashes, uint64_t **out_offsets);
 
+/* Rows of the transposed index: for the structures id_lo .. id_hi - 1 (absolute ids, first_id <= id_lo <= id_hi <= first_id + n_structures)
+ * (*row_off)[k] .. [k + 1] delimit, in *hashes, the ascending hashes whose posting lists hold structure id_lo + k.  id_hi - id_lo + 1 offsets,
+ * row_off[0] = 0; id_lo == id_hi: one offset, no hash.  The shape of fdgpu_hash_batch's output, and for an index built over a batch its content:
+ * the rows of the window equal fdgpu_hash_batch(sort_dedup = 1) of the same structures.  Byte-identical from run to run.  Release both with
+ * fdgpu_free.  The index is not changed.  Workspace follows the window, not the index: 16 bytes per posting inside it, 8 per structure of it, 34
+ * per list (csrc/k_rows.hip).  FDGPU_EINVAL for a window outside the index and for a damaged index (offsets that do not ascend inside the value
+ * bytes, a varint that leaves its list, an id outside [first_id, first_id + n_structures)), found before a decoded id is used as an address or a
+ * key; FDGPU_ERANGE for a list of 4 GiB or more or 2^32 or more postings inside the window; FDGPU_EHIP when the workspace does not fit.  On any
+ * error both outputs are NULL.  Lists that hold nothing of the window (head at or above id_hi; last id below id_lo where the index carries last
+ * ids) are not decoded beyond their head, so damage behind it goes unseen there: fdgpu_index_verify is the check of a whole index. */
+int fdgpu_index_rows(fdgpu_ctx *ctx, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, uint32_t **hashes, uint64_t **row_off);
+/* The same rows from host arrays (the payload of PREFIX.offset and PREFIX), n_threads host threads (0 = 1); the result does not depend on their
+ * number.  No device.  Same arrays and same error codes as the device form for an index without last ids (and FDGPU_EINVAL when first_id +
+ * n_structures exceeds 32 bits); both arrays are released with fdgpu_free. */
+int fdgpu_rows_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes, const uint8_t *value, uint64_t value_len,
+                    uint64_t first_id, uint64_t n_structures, uint64_t id_lo, uint64_t id_hi, uint32_t n_threads,
+                    uint32_t **row_hashes, uint64_t **row_off);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
