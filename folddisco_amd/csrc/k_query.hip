@@ -392,27 +392,9 @@ __global__ __launch_bounds__(CQ_FIN_T) void k_cq_rows_finalize(const uint32_t *_
     }
 }
 
-
-__global__ __launch_bounds__(256) void k_cq_compact(const uint32_t *__restrict__ match, const unsigned long long *__restrict__ idf,
-                                                    const uint32_t *__restrict__ node_cnt, const uint32_t *__restrict__ edge_cnt,
-                                                    const uint8_t *__restrict__ flags, const uint64_t *__restrict__ pos,
-                                                    const float *__restrict__ penalty, uint32_t S, uint32_t first_id,
-                                                    fd_count_rec_dev *__restrict__ out) {
-    uint32_t nid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (nid >= S || !flags[nid]) return;
-    fd_count_rec_dev r;
-    r.nid = nid + first_id;
-    const unsigned long long a = idf[nid];
-    r.total_match_count = match ? match[nid] : (uint32_t)(a >> CQ_CNT_SHIFT);
-    r.node_count = node_cnt[nid];
-    r.edge_count = edge_cnt[nid];
-    float sum = (float)((double)(match ? a : a & CQ_SUM_MASK) * (1.0 / IDF_SCALE));
-    r.idf = sum * penalty[nid];  // count_query.rs:200 idf_sum *= nres^(-lp)
-    out[pos[nid]] = r;
-}
-
 // ------------------------------------------------------------------ batched scoring (many queries, one launch each)
-// Same arithmetic as above; the per-structure results are [n_queries][S], the occupancy matrix has one row per query hash of the batch.
+// The touched (query, structure) pairs as records (count_query.rs:200 idf_sum *= nres^(-lp)); the per-structure results are [n_queries][S], the occupancy
+// matrix has one row per query hash of the batch.  One query (fdgpu_count_query) is total == S.
 __global__ __launch_bounds__(256) void k_cq_compact_batch(const uint32_t *__restrict__ match, const unsigned long long *__restrict__ idf,
                                                           const uint32_t *__restrict__ node_cnt, const uint32_t *__restrict__ edge_cnt,
                                                           const uint8_t *__restrict__ flags, const uint64_t *__restrict__ pos,
@@ -856,8 +838,3 @@ void fd_launch_posting_lookup(const uint32_t *hashes, const uint64_t *offsets, c
     if (nq) hipLaunchKernelGGL(k_pl_lookup, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, hashes, offsets, lens, H, q_hash, nq, (unsigned long long *)lengths, nseg, kidx);
 }
 
-void fd_launch_cq_compact(const uint32_t *match, const unsigned long long *idf, const uint32_t *node_cnt, const uint32_t *edge_cnt,
-                          const uint8_t *flags, const uint64_t *pos, const float *penalty, uint32_t S, uint32_t first_id, void *out,
-                          hipStream_t st) {
-    if (S) hipLaunchKernelGGL(k_cq_compact, dim3((S + 255) / 256), dim3(256), 0, st, match, idf, node_cnt, edge_cnt, flags, pos, penalty, S, first_id, (fd_count_rec_dev *)out);
-}

@@ -641,7 +641,8 @@ int fdgpu_spec_fallbacks(fdgpu_ctx *ctx, uint64_t *out);
 /* ---- profiling hooks ------------------------------------------------------------------------------
  * Per-kernel timing of the last fdgpu_index_build / fdgpu_count_query call, measured with
  * HIP events on the context's stream. names[i] is a static string. Returns the number of
- * entries written (<= cap). */
+ * entries written (<= cap).  Every count call, fdgpu_count_query included, reports its scoring as
+ * "cq_batch" and a device selection as "cq_topn". */
 int fdgpu_last_timings(const fdgpu_ctx *ctx, const char **names, float *ms, uint64_t *bytes, int cap);
 int fdgpu_enable_timing(fdgpu_ctx *ctx, int on);
 

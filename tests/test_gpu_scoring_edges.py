@@ -3,13 +3,14 @@ against the integer model of that module BYTE FOR BYTE (no tolerance: the fixed-
 read back through fdgpu_debug_last_count_path after every call.
 
 Per case and first_id (0, 3000, 2^28 - 40,000, 2^32 - 1 - S): the index is loaded, verifies clean where every id is in range, its posting lengths
-equal the model's; count_query_batch with top_n = 0 and with every top_n of the case plus 1, 3072 and 3073; for map cases count_query_maps in the
+equal the model's; count_query_batch with top_n = 0 and with every top_n of the case plus 1, 3072 and 3073; for a case of one query count_query as well
+(the single entry point: the model's full list and the rows form); for map cases count_query_maps in the
 default form and under FDGPU_QT32=0, FDGPU_QT32=0 + FDGPU_QT_STREAM=0 and FDGPU_QTILE=0.  The expected form restates the dispatch's conditions from
 the model's units (no zero-unit row, units below 2^32, rows <= 128 / <= 1024 / >= 4096 in one query, fix < 2^27, top_n + 1024 <= 4096).
 
 Map cases sit on the query map of residues B18 .. B24 of tests/golden/query/4CHA.pdb (scoring_cases.MOTIF: the first of the shortest runs of consecutive
 residues whose map has at least 160 entries; test_scoring_cases_host.py checks that on the CPU) and, for the mixed batches, of B18 .. B19.
-Measured: the module's 69 tests take 11 s on an MI355X, the slowest 0.5 s."""
+Measured: the module's 69 tests take 10 s on an MI355X, the slowest 0.5 s."""
 import ctypes as C
 import functools
 
@@ -115,6 +116,11 @@ def run_case(ctx, motif, c, first_id, monkeypatch):
 
     for n in (0,) + ns:
         check(fd.count_query_batch(ctx, ix, rows, c.penalty, total_structures=c.total, top_n=n), n, "batch", {})
+    if len(rows) == 1:          # the single entry point: the rows form of one query, every touched structure
+        got = fd.count_query(ctx, ix, *rows[0], c.penalty, total_structures=c.total, as_array=True)
+        assert got.tobytes() == mods[0][0].tobytes(), (c, first_id, "single")
+        packed = all(int(x) < 1 << 27 for x in kept_fix[0]) and len(kept_fix[0]) < 1 << 18
+        assert last_path(ctx) == ROWS | (PACKED if packed else 0), (c, first_id, "single", hex(last_path(ctx)))
     if c.via == "maps":
         which = {name: k for k, name in enumerate(dict.fromkeys(c.queries))}
         made = fq.make_query_maps(ctx, motif["qb"], [(0, motif["idx"][name], motif["subs"][name]) for name in which], ix, float(c.total))
