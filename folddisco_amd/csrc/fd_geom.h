@@ -151,11 +151,13 @@ FD_HD uint32_t fd_hash_enc(uint32_t aa1, uint32_t aa2, fd_feature f, fd_quant q)
 // and d_CA, d_CB, theta are symmetric.  8 normalisations per ordered pair become 2.
 // =============================================================================================
 struct fd_frame {     // 20 floats = five 16-byte loads (a sixth load for a stored cb-ca costs more than the three subtractions)
+    // hot: the first four 16-byte words (64 B) hold everything fd_pair_both_spec reads
     fd_v3 ca, cb;
     fd_v3 r1, t1;    // torsion(n, ca, cb, *):  r = n^((ca-n) x (cb-ca)),  t = n^(r x n^(cb-ca))
-    fd_v3 s2, nv2;   // torsion(*, cb, ca, n):  s = n^((ca-cb) x (n-ca)),  n^(ca-cb)
     float len;       // |cb-ca| as evaluated by calc_angle
     float pad;
+    // cold: read by the exact routines only (fd_pair_both, fd_pair_both_tab); s2.x, s2.y share the fourth word, the fifth is all cold
+    fd_v3 s2, nv2;   // torsion(*, cb, ca, n):  s = n^((ca-cb) x (n-ca)),  n^(ca-cb)
 };
 
 FD_HD fd_frame fd_make_frame(fd_v3 n, fd_v3 ca, fd_v3 cb) {

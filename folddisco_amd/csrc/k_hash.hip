@@ -297,7 +297,14 @@ __device__ __forceinline__ fd_frame load_frame(const fd_frame *__restrict__ fram
     float4 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4];
     fd_frame F;
     F.ca = {a.x, a.y, a.z}; F.cb = {a.w, b.x, b.y}; F.r1 = {b.z, b.w, c.x}; F.t1 = {c.y, c.z, c.w};
-    F.s2 = {d.x, d.y, d.z}; F.nv2 = {d.w, e.x, e.y}; F.len = e.z; F.pad = e.w;
+    F.len = d.x; F.pad = d.y; F.s2 = {d.z, d.w, e.x}; F.nv2 = {e.y, e.z, e.w};
+    return F;
+}
+// the hot part of a frame (fd_geom.h) from its four 16-byte words; s2 / nv2 stay zero: fd_pair_both_spec reads neither
+__device__ __forceinline__ fd_frame hot_frame(const float4 &a, const float4 &b, const float4 &c, const float4 &d) {
+    fd_frame F{};
+    F.ca = {a.x, a.y, a.z}; F.cb = {a.w, b.x, b.y}; F.r1 = {b.z, b.w, c.x}; F.t1 = {c.y, c.z, c.w};
+    F.len = d.x; F.pad = d.y;
     return F;
 }
 
@@ -336,7 +343,7 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
         fd_wave_lds_fence();
         if (lane < n) {
             const uint32_t e = q[lane], il = (e >> 16) & 63u, aj = e >> 22;
-            const uint32_t ai = TAB == 2 ? __float_as_uint(s_fi[256 + il].w) : (uint32_t)B.aa[i0 + il];
+            const uint32_t ai = TAB == 2 ? __float_as_uint(s_fi[192 + il].y) : (uint32_t)B.aa[i0 + il];
             const uint32_t bf = ai * 2u + (aj >> 4), br = aj * 2u + (ai >> 4);
             slots = atomicAdd(&s_bc[bf], 1u) | atomicAdd(&s_bc[br], 1u) << 8 | bf << 16 | br << 24;      // one register across the descriptor
         }
@@ -348,13 +355,11 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
         uint32_t e = q[lane];
         uint32_t i = i0 + ((e >> 16) & 63u), j = r0 + (e & 0xffffu);
         if (TAB == 2) {
-            // frame of i from the work item's LDS-staged residue tile ([k][lane] float4 planes), frame of j from L2
+            // hot frame of i from the work item's LDS-staged residue tile ([k][lane] float4 planes), hot frame of j from L2
             const uint32_t il = (e >> 16) & 63u;
-            const float4 a4 = s_fi[il], b4 = s_fi[64 + il], c4 = s_fi[128 + il], d4 = s_fi[192 + il], e4 = s_fi[256 + il];
-            fd_frame Fi;
-            Fi.ca = {a4.x, a4.y, a4.z}; Fi.cb = {a4.w, b4.x, b4.y}; Fi.r1 = {b4.z, b4.w, c4.x}; Fi.t1 = {c4.y, c4.z, c4.w};
-            Fi.s2 = {d4.x, d4.y, d4.z}; Fi.nv2 = {d4.w, e4.x, e4.y}; Fi.len = e4.z; Fi.pad = e4.w;
-            fd_frame Fj = load_frame(frames, j);
+            const fd_frame Fi = hot_frame(s_fi[il], s_fi[64 + il], s_fi[128 + il], s_fi[192 + il]);
+            const float4 *pj = reinterpret_cast<const float4 *>(frames + j);
+            const fd_frame Fj = hot_frame(pj[0], pj[1], pj[2], pj[3]);
             aai = __float_as_uint(Fi.pad); aaj = __float_as_uint(Fj.pad);
 #if defined(FD_EMIT_STUB) && FD_EMIT_STUB == 1
             // measurement build (tools/attrib_emit.sh): the drain without the descriptor — frames loaded, slots claimed, keys stored
@@ -375,6 +380,10 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
         }
     }
     if (MSD) {
+        // the claim's result is first needed HERE.  Without this barrier the compiler widens gb to 64 bits where it is defined: a register copy right
+        // behind global_atomic_add, and in front of it s_waitcnt vmcnt(0) — every drain then sat out the atomic's round trip to L2 (and the stores
+        // of the drain before) ahead of the gather of frame j instead of behind the descriptor
+        asm volatile("" : "+v"(gb));
         if (lane < FD_MSD_BUCKETS) s_bb[lane] = s_boff[lane] + gb;      // first slot of this drain's keys in every bucket (a build call may hold more than 2^32 keys)
         fd_wave_lds_fence();
         if (lane < n) {
@@ -442,13 +451,13 @@ __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_
     const bool vi = i < r1 && B.hash_ok[i];
     fd_v3 cai = {0.f, 0.f, 0.f};
     if (vi) cai = fd_load3(B.ca_xyz, i);
-    // LDS staging of the work item's residue tile: the 64 frames of the i side (5 KB), plane-major so that the fill is
-    // conflict-free; every drain reads its i frames from here instead of gathering them from L2 again
-    __shared__ float4 s_fi[5 * FD_WAVE];
+    // LDS staging of the work item's residue tile: the hot 64 bytes of the 64 frames of the i side (4 KB), plane-major so that the fill
+    // is conflict-free; every drain reads its i frames from here instead of gathering them from L2 again
+    __shared__ float4 s_fi[4 * FD_WAVE];
     if (TAB == 2 && i < r1) {
         const float4 *fp = reinterpret_cast<const float4 *>(frames + i);
 #pragma unroll
-        for (int k = 0; k < 5; ++k) s_fi[k * FD_WAVE + lane] = fp[k];
+        for (int k = 0; k < 4; ++k) s_fi[k * FD_WAVE + lane] = fp[k];
     }
     __shared__ uint32_t s_bc[MSD ? FD_WAVE : 1];
     __shared__ uint64_t s_bb[MSD ? FD_MSD_BUCKETS : 1], s_boff[MSD ? FD_MSD_BUCKETS : 1];      // forty of each: with 64 the workgroup passes 8 KB and the CU holds 19 of them, not 20
