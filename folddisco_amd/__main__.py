@@ -1,4 +1,4 @@
-"""`python -m folddisco_amd index|query|update|verify|reshard|merge|reorder|coords …` — the reference's two hot-path subcommands (and `update`, `verify`, `reshard`, `merge`, `reorder` and `coords`, which it lacks) with its flag names and defaults
+"""`python -m folddisco_amd index|query|update|verify|rows|dups|reshard|merge|reorder|coords …` — the reference's two hot-path subcommands (and `update`, `verify`, `rows`, `dups`, `reshard`, `merge`, `reorder` and `coords`, which it lacks) with its flag names and defaults
 (src/cli/main.rs:26-110, src/cli/workflows/build_index.rs:64-241, src/cli/workflows/query_pdb.rs:144-519), driving the
 GPU path through the C ABI.  Structure order = lexicographic path order (the reference uses readdir order, which is
 filesystem dependent; SURVEY §7 hard part 3).  Only the default PDBTrRosetta encoding is supported; input is PDB or mmCIF, optionally gzip."""
@@ -617,6 +617,152 @@ def cmd_rows(a):
         print(f"[INFO] rows of {a.index} on the {'host' if a.host else 'device'}: {n_windows} window(s) of up to {a.window} structures", file=sys.stderr)
 
 
+def _dups_plan(a):
+    """everything `dups` decides before it opens a device: -> (prefixes, their tids).  Status 2 for missing or unreadable files, status 1 and a
+    [FAIL] line for a refusal; nothing is written in either case."""
+    import glob
+    from folddisco_amd import indexio
+    if not 0.0 < a.min_similarity <= 1.0:            # NaN fails it too
+        sys.exit(f"[FAIL] dups: --min-similarity {a.min_similarity} is outside (0, 1]")
+    if a.window < 1:
+        sys.exit("[FAIL] dups: --window must be at least 1")
+    if a.max_pairs < 0:
+        sys.exit("[FAIL] dups: --max-pairs must not be negative")
+    prefixes = [a.index] + ([a.against] if a.against is not None else [])
+    if len(prefixes) == 2 and os.path.abspath(prefixes[0]) == os.path.abspath(prefixes[1]):
+        sys.exit(f"[FAIL] dups: --against {a.against} is the index itself; leave it out to look for duplicates inside one index")
+    for p in prefixes:
+        if not os.path.isfile(p) and glob.glob(glob.escape(p) + ".shard*of*"):
+            print(f"[FAIL] dups: {p} is a sharded index; write the single index first (`reshard -i {p} --from V --to 1`)")
+            sys.exit(1)
+        for ext in INDEX_FILES:
+            if not os.path.isfile(p + ext):
+                print(f"[FAIL] {p}{ext} not found", file=sys.stderr)
+                sys.exit(2)
+    try:
+        bad = [b for p in prefixes for b in indexio.check_index_files(p)]
+        tids = [[r.rstrip("\n").split("\t")[1] for r in indexio.read_lookup_rows(p + ".lookup")] for p in prefixes]
+        texts = []
+        for p in prefixes:
+            with open(p + ".type") as f:
+                texts.append(f.read())
+    except (OSError, ValueError, UnicodeDecodeError) as e:
+        print(f"[FAIL] dups: unreadable input ({e})", file=sys.stderr)
+        sys.exit(2)
+    if bad:
+        print("[FAIL] index files are inconsistent: " + "; ".join(bad))
+        sys.exit(1)
+    key = indexio.check_joinable(texts)
+    if key is not None:
+        print(f"[FAIL] dups: the two indices' .type files differ in {key}: signatures of indices built with different settings are not comparable")
+        sys.exit(1)
+    return prefixes, tids
+
+
+def _dups_signatures(a, ctx, prefix, n):
+    """the signature table of one index: loaded, checked if --verify, reduced, released"""
+    from folddisco_amd import indexio
+    v, h, o = indexio.read_index_files(prefix)
+    if a.host:
+        if a.verify:
+            _stop_if_unsound(indexio.verify_host(v, h, o, n, threads=a.threads), prefix)
+        return np.array(indexio.signatures_host(v, h, o, n, threads=a.threads))
+    import folddisco_amd as fd
+    ix = fd.FolddiscoIndex.load(ctx, h, o, v, n)
+    del v, h, o
+    if a.verify:
+        _stop_if_unsound(ix.verify(), prefix)
+    return np.array(ix.signatures(window=a.window))
+
+
+def _dups_rows(a, ctx, prefix, n, ids):
+    """the rows of the ascending unique ids of one index, fetched as `rows --tids` does: windows that cover them -> {id: hashes}"""
+    from folddisco_amd import indexio
+    out = {}
+    if not len(ids):
+        return out
+    v, h, o = indexio.read_index_files(prefix)
+    if a.host:
+        window = lambda lo, hi: indexio.rows_host(v, h, o, n, lo=lo, hi=hi, threads=a.threads)
+    else:
+        import folddisco_amd as fd
+        ix = fd.FolddiscoIndex.load(ctx, h, o, v, n)
+        del v, h, o
+        window = ix.rows
+    for lo, hi, k0, k1 in _windows(ids, a.window, n):
+        wh, woff = window(lo, hi)
+        for k in range(k0, k1):
+            s = int(ids[k]) - lo
+            out[int(ids[k])] = np.array(wh[int(woff[s]):int(woff[s + 1])])
+    return out
+
+
+def cmd_dups(a):
+    """`dups`: which structures are already there?  Every structure of the index at PREFIX is reduced to its signature (fdgpu_index_signatures:
+    size, two digests and a 64-bucket MinHash sketch of its row) and the signatures are compared all against all, inside the index or, with
+    --against, with those of a second one, on the device (fdgpu_signature_pairs) or with --host on the CPU (no device is opened).  One TSV row
+    per reported pair, sorted by (id_a, id_b): id_a tid_a n_a id_b tid_b n_b match filled estimate class[ jaccard]; class is `identical` (same
+    size and digests: the same hash set) or `similar` (estimate = match / filled of the sketches reaches --min-similarity); --confirm adds the
+    exact Jaccard similarity from the rows of the reported structures.  It reports and removes nothing.  No structure file is read."""
+    from folddisco_amd import indexio
+    prefixes, tids = _dups_plan(a)
+    two = len(prefixes) == 2
+    thr64 = 64 if a.identical_only else indexio.signature_threshold(a.min_similarity)
+    try:
+        ctx = None
+        if not a.host:
+            import folddisco_amd as fd
+            ctx = fd.Context(a.device)
+        tabs = [_dups_signatures(a, ctx, p, len(t)) for p, t in zip(prefixes, tids)]
+        A, B = tabs[0], (tabs[1] if two else None)
+        try:
+            pairs = indexio.signature_pairs_host(A, B, thr64=thr64, max_pairs=a.max_pairs, threads=a.threads) if a.host else \
+                ctx.signature_pairs(A, B, thr64=thr64, max_pairs=a.max_pairs)
+        except indexio.SignaturePairsOverflow as e:
+            print(f"[FAIL] dups: {e.count} pairs reach the threshold {thr64}/64, more than --max-pairs {a.max_pairs}: raise --min-similarity or --max-pairs")
+            sys.exit(1)
+        if a.identical_only:
+            pairs = pairs[(pairs["flags"] & indexio.SIG_IDENTICAL) != 0]
+        jac = None
+        if a.confirm:
+            ids_a = np.unique(np.concatenate([pairs["a"], pairs["b"]]) if not two else pairs["a"]).astype(np.int64)
+            rows_a = _dups_rows(a, ctx, prefixes[0], len(tids[0]), ids_a)
+            rows_b = _dups_rows(a, ctx, prefixes[1], len(tids[1]), np.unique(pairs["b"]).astype(np.int64)) if two else rows_a
+            jac = []
+            for r in pairs:
+                x, y = rows_a[int(r["a"])], rows_b[int(r["b"])]
+                inter = len(np.intersect1d(x, y))
+                jac.append(inter / max(len(x) + len(y) - inter, 1))
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] dups: {e}", file=sys.stderr)
+        sys.exit(2 if isinstance(e, OSError) else 1)
+    tb = tids[1] if two else tids[0]
+    lines = []
+    for k, r in enumerate(pairs):
+        ia, ib = int(r["a"]), int(r["b"])
+        cols = [str(ia), tids[0][ia], str(int(A["n"][ia])), str(ib), tb[ib], str(int((B if two else A)["n"][ib])), str(int(r["match"])), str(int(r["filled"])),
+                f"{float(r['estimate']):.4f}", "identical" if int(r["flags"]) & indexio.SIG_IDENTICAL else "similar"]
+        if jac is not None:
+            cols.append(f"{jac[k]:.4f}")
+        lines.append("\t".join(cols) + "\n")
+    if a.output:
+        tmp = f"{a.output}.dups-tmp{os.getpid()}"
+        try:
+            with open(tmp, "w") as f:
+                f.writelines(lines)
+            os.replace(tmp, a.output)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+    else:
+        sys.stdout.writelines(lines)
+    n_ident = int(((pairs["flags"] & indexio.SIG_IDENTICAL) != 0).sum())
+    print(f"[OK] {' x '.join(prefixes)}: {' x '.join(str(len(t)) for t in tids)} structures, {len(pairs)} pairs ({n_ident} identical), threshold {thr64}/64")
+    if a.verbose:
+        print(f"[INFO] dups on the {'host' if a.host else 'device'}: signatures of {sum(len(t) for t in tids)} structures ({sum(t.nbytes for t in tabs)} bytes)"
+              + (f", {len(jac)} pairs confirmed from their rows" if jac is not None else ""), file=sys.stderr)
+
+
 def _reshard_plan(a):
     """everything `reshard` decides before it opens a device: -> (source prefixes, structures).  Status 2 for missing or unreadable files,
     status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
@@ -1229,6 +1375,20 @@ def main(argv=None):
     pw.add_argument("--device", type=int, default=0)
     pw.add_argument("--verify", action="store_true", help="check the loaded index first (see `verify`) and stop with status 1 if it is damaged")
     pw.add_argument("-v", "--verbose", action="store_true")
+    pd = sub.add_parser("dups")                                      # which structures are already there? (no counterpart in the reference)
+    pd.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
+    pd.add_argument("--against", default=None, help="a second index prefix: every structure of PREFIX against every structure of it (default: inside PREFIX)")
+    pd.add_argument("--min-similarity", type=float, default=0.9, help="report pairs whose sketches agree in at least this share of their filled buckets, in (0, 1]")
+    pd.add_argument("--identical-only", action="store_true", help="only pairs with the same hash set (same size and digests)")
+    pd.add_argument("--confirm", action="store_true", help="add the exact Jaccard similarity of every reported pair, from the rows of its structures")
+    pd.add_argument("-o", "--output", default="", help="the TSV file to write (default: standard output)")
+    pd.add_argument("--window", type=int, default=16384, help="structures per walk over the index")
+    pd.add_argument("--max-pairs", type=int, default=1 << 24, help="most pairs to report; more end the command with their number")
+    pd.add_argument("--host", action="store_true", help="reduce and compare on the CPU (no device is opened)")
+    pd.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    pd.add_argument("--device", type=int, default=0)
+    pd.add_argument("--verify", action="store_true", help="check every loaded index first (see `verify`) and stop with status 1 if it is damaged")
+    pd.add_argument("-v", "--verbose", action="store_true")
     pr = sub.add_parser("reshard")                                   # one index <-> shards by structure id range (no counterpart in the reference)
     pr.add_argument("-i", "--index", required=True)
     pr.add_argument("--to", type=int, required=True, help="shards to write (PREFIX.shard<r>ofW); 1 writes the single index")
@@ -1299,6 +1459,9 @@ def main(argv=None):
         return
     if a.cmd == "rows":
         cmd_rows(a)
+        return
+    if a.cmd == "dups":
+        cmd_dups(a)
         return
     if a.cmd == "reshard":
         cmd_reshard(a)

@@ -125,6 +125,23 @@ class Context:
         n = self.L.fdgpu_last_timings(self.h, names, ms, by, cap)
         return [(names[i].decode(), float(ms[i]), int(by[i])) for i in range(n)]
 
+    def signature_pairs(self, A, B=None, min_similarity: float = 0.9, max_pairs: int = 1 << 24, thr64=None) -> np.ndarray:
+        """every reported pair of two signature tables, compared on the device (fdgpu_signature_pairs), sorted by (a, b), as
+        indexio.SIGNATURE_PAIRS_DTYPE; the contract of indexio.signature_pairs_host, which it equals record for record"""
+        from . import indexio
+        A = indexio._sig_table(A, "A")
+        B = None if B is None else indexio._sig_table(B, "B")
+        t = indexio.signature_threshold(min_similarity) if thr64 is None else int(thr64)
+        if not 0 <= t <= 0xffffffff:
+            raise ValueError("signature_pairs: thr64 must be 1 .. 64")
+        pp, n = C.c_void_p(), C.c_uint64()
+        rc = self.L.fdgpu_signature_pairs(self.h, A.ctypes.data, len(A), None if B is None else B.ctypes.data, 0 if B is None else len(B), t, int(max_pairs),
+                                          C.byref(pp), C.byref(n))
+        if rc == -4:
+            raise indexio.SignaturePairsOverflow(int(n.value), int(max_pairs))
+        self.check(rc)
+        return indexio.signature_pairs_result(self.L, pp, int(n.value))
+
     # ---- batches
     def upload(self, ps: PackedStructures) -> "Batch":
         d = BatchDesc(ps.n_struct, _ptr(ps.res_off, u64p), _ptr(ps.n_xyz, f32p), _ptr(ps.ca_xyz, f32p), _ptr(ps.cb_xyz, f32p),
@@ -344,6 +361,20 @@ class FolddiscoIndex:
         self.ctx.check(self.ctx.L.fdgpu_index_rows(self.ctx.h, self.h, lo, hi, C.byref(hp), C.byref(op)))
         off = _lib.owned_view(self.ctx.L, op, (hi - lo + 1) * 8, np.uint64)
         return _lib.owned_view(self.ctx.L, hp, int(off[-1]) * 4, np.uint32), off
+
+    def signatures(self, lo=None, hi=None, window: int = 16384) -> np.ndarray:
+        """index signatures (fdgpu_index_signatures): one indexio.SIGNATURE_DTYPE record for each of the structures lo .. hi - 1 (absolute ids;
+        default: the whole index) — the size, two digests and a 64-bucket MinHash sketch of the structure's row, reduced on the device in
+        windows of `window` structures (indexio.signatures_from_rows is the definition).  The result does not depend on `window`; the index is
+        not changed"""
+        from .indexio import SIGNATURE_DTYPE
+        lo = self.first_id if lo is None else int(lo)
+        hi = self.first_id + self.n_structures if hi is None else int(hi)
+        if lo < 0 or hi < 0 or int(window) < 0:
+            raise ValueError("signatures: lo and hi are absolute structure ids, window a count of structures")
+        op = C.c_void_p()
+        self.ctx.check(self.ctx.L.fdgpu_index_signatures(self.ctx.h, self.h, lo, hi, int(window), C.byref(op)))
+        return _lib.owned_view(self.ctx.L, op, (hi - lo) * SIGNATURE_DTYPE.itemsize, np.uint8).view(SIGNATURE_DTYPE)
 
     # ---- one on-disk index from N ranks (fd_shard_index.hip; SURVEY §8e row 2, Option A)
     def range_bounds(self, n_ranges: int) -> np.ndarray:

@@ -1,0 +1,130 @@
+// fd_signatures_host.cpp — fdgpu_signatures_host and fdgpu_signature_pairs_host: the index signatures (k_sig.hip) and their compare on host
+// arrays.  No device and no HIP call: this file also builds with a plain host compiler.
+//
+// Signatures, on purpose by another algorithm than the device's (which transposes the window and reduces every row): ONE pass over the posting
+// lists, m(h) once per list, and every decoded id of the range updates its record in place (n += 1, d0 += m, d1 ^= m, sk[b] = min).  Threads
+// split the structure range and each walks all lists, so no two threads touch the same record and the result does not depend on their number.
+// Every thread makes the checks of fdgpu_rows_host on every list (the same lists are left behind their head: those that start at or above id_hi),
+// so the same input gives the same error code; nothing is handed out unless every list was sound.
+// Pairs: a blocked double loop, threads over the blocks of A, the records sorted by (a, b) at the end.
+#include <cstring>
+#include "fd_signature.h"
+#include "fd_postings_host.h"
+
+namespace {
+struct sg_in { const uint32_t *hashes; const uint64_t *offsets; const uint8_t *value; uint64_t value_len, first_id, S, lo, hi; };
+
+// list k walked for the thread that owns the structures s0 .. s1 - 1 (absolute ids); error bits as rows_list: 1 damaged, 2 a list of 4 GiB
+unsigned sig_list(const sg_in &A, uint64_t k, uint64_t s0, uint64_t s1, fd_signature *tab) {
+    const uint64_t b0 = A.offsets[k], b1 = A.offsets[k + 1];
+    if (b1 <= b0 || b1 > A.value_len) return 1u;
+    if (b1 - b0 > 0xffffffffull) return 2u;
+    if (A.value[b1 - 1] & 0x80) return 1u;
+    const uint64_t m = fd_sig_mix(A.hashes[k]);
+    const uint32_t b = fd_sig_bucket(m), v = fd_sig_value(m);
+    uint64_t run = 0;
+    for (uint64_t q = b0; q < b1;) {
+        const fd_varint_read vr = fd_read_varint(A.value, q, b1);
+        if (vr.st != FD_VR_OK) return 1u;
+        run += vr.v;                               // the head is absolute: 0 + head
+        if (run < A.first_id || run - A.first_id >= A.S) return 1u;
+        if (q == b0 && run >= A.hi) break;
+        if (run >= s0 && run < s1) {
+            fd_signature &g = tab[run - A.lo];
+            g.n += 1; g.d0 += m; g.d1 ^= m;
+            if (v < g.sk[b]) g.sk[b] = v;
+        }
+        q += vr.n;
+    }
+    return 0;
+}
+
+struct sg_stat { uint32_t eq, E; };
+inline sg_stat sig_compare(const fd_signature &a, const fd_signature &b) {
+    sg_stat s = {0, 0};
+    for (unsigned k = 0; k < 64; ++k) {
+        s.eq += a.sk[k] == b.sk[k] ? 1u : 0u;
+        s.E += (a.sk[k] == FD_SIG_EMPTY && b.sk[k] == FD_SIG_EMPTY) ? 1u : 0u;
+    }
+    return s;
+}
+}      // namespace
+
+extern "C" int fdgpu_signatures_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t H, const uint8_t *value, uint64_t value_len, uint64_t first_id,
+                                     uint64_t n_structures, uint64_t id_lo, uint64_t id_hi, uint32_t n_threads, fd_signature **out) {
+    if (!out) return FDGPU_EINVAL;
+    *out = nullptr;
+    if ((H && (!offsets || !hashes)) || (value_len && !value)) return FDGPU_EINVAL;
+    if (first_id > 0xffffffffull || first_id + n_structures > 0xffffffffull) return FDGPU_EINVAL;
+    if (id_lo < first_id || id_lo > id_hi || id_hi > first_id + n_structures) return FDGPU_EINVAL;
+    const uint64_t W = id_hi - id_lo;
+    fd_signature *tab = (fd_signature *)malloc(std::max<uint64_t>(W, 1) * sizeof(fd_signature));
+    if (!tab) return FDGPU_ENOMEM;
+    for (uint64_t s = 0; s < W; ++s) {
+        memset(&tab[s], 0, 24);
+        for (unsigned k = 0; k < 64; ++k) tab[s].sk[k] = FD_SIG_EMPTY;
+    }
+    if (W && H) {
+        const sg_in A{hashes, offsets, value, value_len, first_id, n_structures, id_lo, id_hi};
+        const uint64_t T = fd_host_threads(n_threads, W, 64);
+        std::vector<unsigned> err(T, 0);
+        fd_over_ranges(T, [&](uint64_t t) {
+            const uint64_t s0 = id_lo + W * t / T, s1 = id_lo + W * (t + 1) / T;
+            for (uint64_t k = 0; k < H; ++k) err[t] |= sig_list(A, k, s0, s1, tab);
+        });
+        unsigned eb = 0;
+        for (unsigned e : err) eb |= e;
+        if (eb) { free(tab); return eb & 1u ? FDGPU_EINVAL : FDGPU_ERANGE; }
+    }
+    *out = tab;
+    return FDGPU_OK;
+}
+
+extern "C" int fdgpu_signature_pairs_host(const fd_signature *A, uint64_t nA, const fd_signature *B, uint64_t nB, uint32_t thr64, uint64_t max_pairs,
+                                          uint32_t n_threads, fd_sig_pair **pairs, uint64_t *n_pairs) {
+    if (!pairs || !n_pairs) return FDGPU_EINVAL;
+    *pairs = nullptr; *n_pairs = 0;
+    if (thr64 < 1 || thr64 > 64) return FDGPU_EINVAL;
+    if (nA > 0xffffffffull || (B && nB > 0xffffffffull) || (nA && !A)) return FDGPU_EINVAL;
+    const bool self = B == nullptr;
+    if (self) { B = A; nB = nA; }
+    const uint64_t BLK = 64, n_blk = (nA + BLK - 1) / BLK;
+    const uint64_t T = fd_host_threads(n_threads, n_blk, 1);
+    std::vector<std::vector<fd_sig_pair>> got(T);
+    std::vector<uint64_t> cnt(T, 0);
+    bool oom = false;
+    fd_over_ranges(T, [&](uint64_t t) {
+        try {
+            for (uint64_t ba = n_blk * t / T; ba < n_blk * (t + 1) / T; ++ba) {
+                const uint64_t a0 = ba * BLK, a1 = std::min(nA, a0 + BLK);
+                for (uint64_t b0 = self ? a0 : 0; b0 < nB; b0 += BLK) {      // self mode: the blocks below the diagonal hold no a < b
+                    const uint64_t b1 = std::min(nB, b0 + BLK);
+                    for (uint64_t a = a0; a < a1; ++a) {
+                        if (!A[a].n) continue;
+                        for (uint64_t b = self ? std::max(b0, a + 1) : b0; b < b1; ++b) {
+                            const sg_stat s = sig_compare(A[a], B[b]);
+                            if (!fd_sig_reported(A[a].n, B[b].n, s.eq, s.E, thr64)) continue;
+                            if (++cnt[t] > max_pairs) continue;               // counted, not kept: the call ends with the true count
+                            fd_sig_pair r;
+                            r.a = (uint32_t)a; r.b = (uint32_t)b; r.match = (uint8_t)(s.eq - s.E); r.filled = (uint8_t)(64u - s.E);
+                            r.flags = A[a].n == B[b].n && A[a].d0 == B[b].d0 && A[a].d1 == B[b].d1 ? FD_SIG_IDENTICAL : 0u;
+                            got[t].push_back(r);
+                        }
+                    }
+                }
+            }
+        } catch (...) { oom = true; }
+    });
+    if (oom) return FDGPU_ENOMEM;
+    uint64_t total = 0;
+    for (uint64_t x : cnt) total += x;
+    *n_pairs = total;
+    if (total > max_pairs) return FDGPU_ERANGE;
+    fd_sig_pair *res = (fd_sig_pair *)malloc(std::max<uint64_t>(total, 1) * sizeof(fd_sig_pair));
+    if (!res) return FDGPU_ENOMEM;
+    uint64_t at = 0;
+    for (auto &g : got) { if (!g.empty()) memcpy(res + at, g.data(), g.size() * sizeof(fd_sig_pair)); at += g.size(); }
+    std::sort(res, res + total, [](const fd_sig_pair &x, const fd_sig_pair &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    *pairs = res;
+    return FDGPU_OK;
+}

@@ -94,6 +94,7 @@ enum {
     WS_QT_RANGES, WS_QT_COMPACT, WS_QT_COUNT, WS_QT_AUX, WS_RS_PLAN, WS_RS_REC, WS_RS_RECRES, WS_QT_PARTIAL, WS_QT_SURV, WS_QT_ROWBITS, WS_QT_STREAM, WS_QT_STAB, WS_QT_PIECEP, WS_QT_WIN, WS_QT_HEAD, WS_RS_SPLIT, WS_MP_QSET,
     WS_CA_PERM, WS_OK_PERM, WS_AA_PERM, WS_SEG_TAB,
     WS_RS_TAB, WS_RS_SEG, WS_RS_OUT, WS_RS_RES, WS_RS_KX, WS_RS_KY, WS_RS_KOFF, WS_RS_SOL, WS_RS_CNT, WS_RS_GQ, WS_MP_ACT, WS_MP_Q,
+    WS_SG_TAB /* signatures of a window; table A of a compare */, WS_SG_TAB_B, WS_SG_PAIRS, WS_SG_CURSOR,
     WS_COUNT
 };
 
@@ -273,6 +274,11 @@ static inline int fd_index_last_ids_staged(fdgpu_ctx *c, const fdgpu_index *ix, 
     StageTimer t(c, stage, ix->value_len + ix->n_hashes * 12);
     return fd_index_last_ids(c, ix);
 }
+// k_rows.hip: the device stage of fdgpu_index_rows (plan, count, scan, emit, sort, bounds) without the copy out: the window's rows stay in the
+// context's workspaces (val: the n hashes in (id, hash) order; row_off: id_hi - id_lo + 1 offsets) until its next call that uses the sort buffers.
+// Same checks, codes and messages as the rows, the messages opened by `what`; consumed by the signatures (k_sig.hip)
+struct fd_rows_dev { const uint32_t *val; const uint64_t *row_off; uint64_t n; };
+int fd_rows_device(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, const char *what, fd_rows_dev *out);
 // the failure tail of an operation: the stream's work may still write into the n indexes that were made (null entries: not made), so it ends
 // before their blocks go back to the pool
 static inline int fd_index_op_failed(fdgpu_ctx *c, int rc, fdgpu_index *const *made, size_t n = 1) {

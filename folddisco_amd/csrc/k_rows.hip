@@ -19,6 +19,8 @@
 //   k_rw_bounds    thread per row boundary s = 0 .. W: row_off[s] = the number of sorted keys below s, by a binary search of the sorted keys.
 //                  Empty rows come out right without a histogram and without atomics, and no thread's work depends on the width of a gap
 //                  between two keys (a thread per sorted element would fill such a gap alone: 2^24 stores for one sparse window)
+// Everything up to the bounds is one stage, fd_rows_device, that leaves val, row_off and n in the context's workspaces; the rows copy them out
+// behind it, the signatures (k_sig.hip) reduce them where they are.
 // Byte work: the value bytes of the selected lists are read twice (count, emit); the emit writes 8 bytes per window posting; the sort reads and
 // writes 16 bytes per window posting in each of ceil(key_bits / 8) passes; the bounds gather ceil(log2(n + 1)) keys per row and write 8 bytes.
 // Workspace: 16 bytes per window posting, 34 bytes per list, 8 bytes per window structure — see DESIGN.md §4f.
@@ -104,10 +106,13 @@ __global__ __launch_bounds__(256) void k_rw_bounds(const uint32_t *__restrict__ 
     row_off[s] = lo;
 }
 
-static int rows_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, uint32_t **out_h, uint64_t **out_off) {
-    reset_timings(c);
+// ---- the device stage: plan -> count -> scan -> emit -> sort -> bounds.  Leaves the window's rows in the context's workspaces: out->val (the n
+// hashes in (id, hash) order), out->row_off (W + 1 offsets) — valid until the context's next call that uses its sort workspaces.  `what` opens
+// the messages ("index rows", "index signatures").  The stream is not synchronised behind the last kernel.
+int fd_rows_device(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, const char *what, fd_rows_dev *out) {
     hipStream_t st = c->stream;
     const uint64_t H = ix->n_hashes, W = id_hi - id_lo;
+    const std::string pre = std::string(what) + ": ";
     uint64_t n = 0;               // postings inside the window
     uint32_t *val = nullptr;      // their hashes in (id, hash) order, on the device
     HIPCHK(c, c->ws[WS_MISC5].ensure((W + 1) * 8));
@@ -139,9 +144,9 @@ static int rows_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64
         HIPCHK(c, hipMemcpyAsync(&hv[1], tot + 1, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (hv[1] & FD_IXERR_DAMAGED)
-            FAIL(c, FDGPU_EINVAL, "index rows: the index is damaged (offsets that do not ascend inside the value bytes, or a list whose first id is outside "
-                                  "[first_id, first_id + n_structures))");
-        if (hv[1] & FD_IXERR_LONG) FAIL(c, FDGPU_ERANGE, "index rows: a posting list reaches 4 GiB");
+            FAIL(c, FDGPU_EINVAL, pre + "the index is damaged (offsets that do not ascend inside the value bytes, or a list whose first id is outside "
+                                        "[first_id, first_id + n_structures))");
+        if (hv[1] & FD_IXERR_LONG) FAIL(c, FDGPU_ERANGE, pre + "a posting list reaches 4 GiB");
         if (n_sel) {
             StageTimer t(c, "rows_count", ix->value_len + n_sel * (4 + 16 + 4));      // at most: the selected lists' bytes
             hipLaunchKernelGGL((k_rw_walk<false>), dim3(fd_grid(n_sel, 4)), dim3(256), 0, st, A, order, n_sel, cnt, (const uint64_t *)nullptr,
@@ -155,8 +160,8 @@ static int rows_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64
         HIPCHK(c, hipMemcpyAsync(hv, tot, sizeof hv, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (hv[1] & FD_IXERR_DAMAGED)
-            FAIL(c, FDGPU_EINVAL, "index rows: the index is damaged (a varint that leaves its list, or ids outside [first_id, first_id + n_structures))");
-        if (hv[0] > 0xffffffffull) FAIL(c, FDGPU_ERANGE, "index rows: 2^32 or more postings inside the window; take a narrower window");
+            FAIL(c, FDGPU_EINVAL, pre + "the index is damaged (a varint that leaves its list, or ids outside [first_id, first_id + n_structures))");
+        if (hv[0] > 0xffffffffull) FAIL(c, FDGPU_ERANGE, pre + "2^32 or more postings inside the window; take a narrower window");
         n = hv[0];
         if (n) {
             const size_t kb = n * 4;
@@ -189,6 +194,22 @@ static int rows_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64
             HIPCHK(c, hipGetLastError());
         }
     }
+    if (!n) HIPCHK(c, hipMemsetAsync(row_off, 0, (W + 1) * 8, st));      // no posting in the window: every row is empty
+    out->val = val; out->row_off = row_off; out->n = n;
+    return FDGPU_OK;
+}
+
+// ---- rows = the device stage, then the copy out
+static int rows_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, uint32_t **out_h, uint64_t **out_off) {
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    const uint64_t W = id_hi - id_lo;
+    fd_rows_dev R;
+    const int rc = fd_rows_device(c, ix, id_lo, id_hi, "index rows", &R);
+    if (rc != FDGPU_OK) return rc;
+    const uint64_t n = R.n;
+    const uint32_t *val = R.val;
+    const uint64_t *row_off = R.row_off;
     uint32_t *h = (uint32_t *)fd_out_alloc(std::max<uint64_t>(n, 1) * 4);
     uint64_t *ro = (uint64_t *)fd_out_alloc((W + 1) * 8);
     if (!h || !ro) { fdgpu_free(h); fdgpu_free(ro); FAIL(c, FDGPU_ENOMEM, "index rows: out of host memory"); }

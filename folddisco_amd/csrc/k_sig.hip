@@ -1,0 +1,249 @@
+// k_sig.hip — index signatures (fdgpu_index_signatures) and their all-pairs compare (fdgpu_signature_pairs); the definitions are include/fdgpu.h
+// and fd_signature.h, the host forms fd_signatures_host.cpp.
+//
+// Signatures: the index is walked in windows of structures.  Per window the device stage of the rows (fd_rows_device, k_rows.hip) leaves the
+// window's hashes in (id, hash) order and the row offsets in the context's workspaces, and
+//   k_sg_reduce   wavefront per row: the lanes stride the row's hashes (val[row_off[s] + lane + 64 i], coalesced), each mixes its hash once,
+//                 keeps its share of the sum and the xor in registers and folds the bucket minimum into the wavefront's own 64 words of LDS
+//                 (atomicMin on LDS; no global atomic).  A wave reduction of sum and xor, then the 70 words of the record leave in two
+//                 wave-wide stores.  Sums, xors and minima do not depend on an order, so the table is the same from run to run.
+// Rows are uneven (0 to more than 10^5 hashes); every row keeps one wavefront, no workgroup class for the long ones.
+// The window's table is copied to its place in the page-locked result behind the kernel, in stream order, so the next window may reuse it.
+// Byte work per window, beyond the rows' stages: 4 bytes per posting and 16 per structure read, 280 per structure written and copied out.
+//
+// Pairs: both tables are uploaded (self mode: one), and
+//   k_sg_match    256-thread workgroup: every lane owns one signature of B in registers (64 words + the mask of its empty buckets); the
+//                 workgroup stages tiles of 64 signatures of A in LDS (sk 16 KB, the six header words, a 64-bit empty mask each) and every lane
+//                 compares its signature with the tile's, one signature of A per step — the LDS address is the same for the whole wavefront, a
+//                 broadcast read.  Per pair 64 compares and adds and one popcount.  A wavefront's qualifying pairs of a step take their slots
+//                 from the one global cursor with ONE atomicAdd; a record is written only below max_pairs, the cursor counts on, so the true
+//                 count comes back.  Self mode skips the tiles wholly on or below the diagonal and tests a < b inside the others.
+// The records are sorted by (a, b) on the host (at most max_pairs of them), so the result does not depend on the order the kernel found them in.
+// VALU work: 128 lane-operations per pair.  Workspace: 280 bytes per signature, 12 per pair slot (at most min(max_pairs, every pair)).
+#include <algorithm>
+#include <cstring>
+#include "fdgpu_internal.h"
+#include "fd_api_common.h"
+#include "fd_postings.h"
+#include "fd_signature.h"
+
+#define SG_WINDOW_DEFAULT 16384u
+#define SG_TILE_A 64u           // signatures of A per tile
+#define SG_BLOCK_B 256u         // signatures of B per workgroup: one per lane
+
+__device__ __forceinline__ uint64_t sg_wave_sum64(uint64_t v) {
+    for (int o = FD_WAVE / 2; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o, FD_WAVE);
+    return v;
+}
+__device__ __forceinline__ uint64_t sg_wave_xor64(uint64_t v) {
+    for (int o = FD_WAVE / 2; o > 0; o >>= 1) v ^= (uint64_t)__shfl_xor((unsigned long long)v, o, FD_WAVE);
+    return v;
+}
+
+// ---- reduce: wavefront per row s = 0 .. W - 1.  Reads val[row_off[s] .. row_off[s + 1]) (k_rw_bounds: offsets ascend and end at n), writes the
+// 70 words of record s.  A wavefront's table is its own: the LDS unit takes one wavefront's operations in their order, no workgroup barrier
+__global__ __launch_bounds__(256) void k_sg_reduce(const uint32_t *__restrict__ val, const uint64_t *__restrict__ row_off, uint64_t W, uint32_t *__restrict__ out) {
+    __shared__ uint32_t mins[4][64];
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint64_t s = (uint64_t)blockIdx.x * 4u + wv;
+    if (s >= W) return;
+    uint32_t *mine = mins[wv];
+    mine[lane] = FD_SIG_EMPTY;
+    __builtin_amdgcn_wave_barrier();
+    const uint64_t r0 = row_off[s], r1 = row_off[s + 1];
+    uint64_t d0 = 0, d1 = 0;
+    for (uint64_t i = r0 + lane; i < r1; i += FD_WAVE) {
+        const uint64_t m = fd_sig_mix(val[i]);
+        d0 += m; d1 ^= m;
+        atomicMin(&mine[fd_sig_bucket(m)], fd_sig_value(m));
+    }
+    d0 = sg_wave_sum64(d0); d1 = sg_wave_xor64(d1);
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t sk_lo = mine[lane >= 6u ? lane - 6u : 0u], sk_hi = mine[lane < 6u ? 58u + lane : 0u];
+    const uint32_t head[6] = {(uint32_t)(r1 - r0), 0u, (uint32_t)d0, (uint32_t)(d0 >> 32), (uint32_t)d1, (uint32_t)(d1 >> 32)};
+    uint32_t hw = head[0];
+#pragma unroll
+    for (uint32_t k = 1; k < 6; ++k) if (lane == k) hw = head[k];
+    uint32_t *rec = out + s * FD_SIG_WORDS;
+    rec[lane] = lane < 6u ? hw : sk_lo;               // words 0 .. 63
+    if (lane < 6u) rec[64u + lane] = sk_hi;           // words 64 .. 69
+}
+
+static int signatures_impl(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, uint64_t window, fd_signature **out) {
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    const uint64_t N = id_hi - id_lo;
+    if (!window) window = SG_WINDOW_DEFAULT;
+    fd_signature *res = (fd_signature *)fd_out_alloc(std::max<uint64_t>(N, 1) * sizeof(fd_signature), true);
+    if (!res) FAIL(c, FDGPU_ENOMEM, "index signatures: out of host memory");
+    int rc = FDGPU_OK;
+    hipError_t e = hipSuccess;
+    for (uint64_t lo = id_lo; lo < id_hi && rc == FDGPU_OK && e == hipSuccess; lo += std::min<uint64_t>(window, id_hi - lo)) {
+        const uint64_t W = std::min<uint64_t>(window, id_hi - lo);
+        fd_rows_dev R;
+        rc = fd_rows_device(c, ix, lo, lo + W, "index signatures", &R);
+        if (rc != FDGPU_OK) break;
+        e = c->ws[WS_SG_TAB].ensure(W * sizeof(fd_signature));
+        if (e != hipSuccess) break;
+        uint32_t *tab = c->ws[WS_SG_TAB].as<uint32_t>();
+        {
+            StageTimer t(c, "sig_reduce", R.n * 4 + (W + 1) * 8 + W * sizeof(fd_signature));
+            hipLaunchKernelGGL(k_sg_reduce, dim3(fd_grid(W, 4)), dim3(256), 0, st, R.val, R.row_off, W, tab);
+        }
+        e = hipGetLastError();
+        if (e != hipSuccess) break;
+        {
+            StageTimer t(c, "sig_copy", W * sizeof(fd_signature));
+            e = hipMemcpyAsync(res + (lo - id_lo), tab, W * sizeof(fd_signature), hipMemcpyDeviceToHost, st);
+        }
+    }
+    if (rc == FDGPU_OK && e == hipSuccess) e = hipStreamSynchronize(st);      // the result is complete, and the workspaces free again, when the call returns
+    if (rc != FDGPU_OK || e != hipSuccess) {
+        (void)hipStreamSynchronize(st);                                       // nothing of a failed call still writes into the block
+        fdgpu_free(res);
+        if (rc != FDGPU_OK) return rc;
+        c->err = std::string("index signatures: ") + hipGetErrorString(e);
+        return FDGPU_EHIP;
+    }
+    *out = res;
+    return FDGPU_OK;
+}
+
+extern "C" int fdgpu_index_signatures(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, uint64_t window, fd_signature **out) { FD_LOCK(c);
+    if (!c || !ix || !out) return FDGPU_EINVAL;
+    *out = nullptr;
+    if (id_lo < ix->first_id || id_lo > id_hi || id_hi > ix->first_id + ix->n_structures)
+        FAIL(c, FDGPU_EINVAL, "index signatures: the range is not inside [first_id, first_id + n_structures]");
+    return signatures_impl(c, ix, id_lo, id_hi, window, out);
+}
+
+// ---- match.  Grid: x = workgroups of 256 signatures of B, y = the tiles of A a workgroup takes in turn (tile ta = blockIdx.y, + gridDim.y, ...).
+// Reads A[0 .. nA), B[0 .. nB); writes pairs[slot] for slot < max_pairs only.
+struct sg_match_args { const uint32_t *A; const uint32_t *B; uint32_t nA, nB, thr64, self; fd_sig_pair *pairs; unsigned long long *cursor; unsigned long long max_pairs; };
+
+__global__ __launch_bounds__(256) void k_sg_match(sg_match_args P) {
+    __shared__ uint32_t a_sk[SG_TILE_A][64];
+    __shared__ uint32_t a_head[SG_TILE_A][6];
+    __shared__ unsigned long long a_empty[SG_TILE_A];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint64_t j = (uint64_t)blockIdx.x * SG_BLOCK_B + threadIdx.x;      // the lane's signature of B
+    const bool have = j < P.nB;
+    uint32_t b[64];
+    uint32_t bn = 0, bd0l = 0, bd0h = 0, bd1l = 0, bd1h = 0;
+    unsigned long long b_empty = 0;
+    {
+        const uint32_t *pb = P.B + (have ? j : 0) * FD_SIG_WORDS;
+        if (have) { bn = pb[0]; bd0l = pb[2]; bd0h = pb[3]; bd1l = pb[4]; bd1h = pb[5]; }
+#pragma unroll
+        for (uint32_t k = 0; k < 64; ++k) {
+            b[k] = have ? pb[6 + k] : FD_SIG_EMPTY;
+            b_empty |= (unsigned long long)(b[k] == FD_SIG_EMPTY ? 1u : 0u) << k;
+        }
+    }
+    const uint32_t tiles = (P.nA + SG_TILE_A - 1) / SG_TILE_A;
+    const uint64_t b_last = std::min<uint64_t>((uint64_t)blockIdx.x * SG_BLOCK_B + SG_BLOCK_B, P.nB) - 1;      // the workgroup's last signature of B
+    for (uint32_t ta = blockIdx.y; ta < tiles; ta += gridDim.y) {
+        const uint64_t a0 = (uint64_t)ta * SG_TILE_A;
+        if (P.self && a0 >= b_last) continue;           // no a < b in this tile (the same for the whole workgroup)
+        __syncthreads();                                // the tile before is read to its end
+        const uint32_t n_in = (uint32_t)std::min<uint64_t>(SG_TILE_A, P.nA - a0);
+        for (uint32_t w = threadIdx.x; w < SG_TILE_A * FD_SIG_WORDS; w += 256u) {
+            const uint32_t i = w / FD_SIG_WORDS, f = w % FD_SIG_WORDS;
+            const uint32_t x = i < n_in ? P.A[a0 * FD_SIG_WORDS + w] : (f == 0 ? 0u : FD_SIG_EMPTY);      // beyond the table: n = 0, never reported
+            if (f < 6) a_head[i][f] = x; else a_sk[i][f - 6] = x;
+        }
+        __syncthreads();
+        for (uint32_t i = wv * 16u; i < wv * 16u + 16u; ++i) {      // the empty masks, a wavefront per 16 signatures
+            const unsigned long long em = __ballot(a_sk[i][lane] == FD_SIG_EMPTY);
+            if (lane == 0) a_empty[i] = em;
+        }
+        __syncthreads();
+        for (uint32_t i = 0; i < SG_TILE_A; ++i) {
+            uint32_t eq = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 64; ++k) eq += a_sk[i][k] == b[k] ? 1u : 0u;
+            const uint32_t E = (uint32_t)__popcll(a_empty[i] & b_empty);
+            const uint64_t a = a0 + i;
+            const bool ok = have && fd_sig_reported(a_head[i][0], bn, eq, E, P.thr64) && (!P.self || a < j);
+            const unsigned long long vote = __ballot(ok);
+            if (vote) {                                 // one atomic for the wavefront's pairs of this step
+                unsigned long long base = 0;
+                const uint32_t leader = (uint32_t)__ffsll((long long)vote) - 1u;
+                if (lane == leader) base = atomicAdd(P.cursor, (unsigned long long)__popcll(vote));
+                base = __shfl(base, (int)leader, FD_WAVE);
+                const unsigned long long slot = base + (unsigned long long)__popcll(vote & ((1ull << lane) - 1ull));
+                if (ok && slot < P.max_pairs) {
+                    const bool same = a_head[i][0] == bn && a_head[i][2] == bd0l && a_head[i][3] == bd0h && a_head[i][4] == bd1l && a_head[i][5] == bd1h;
+                    fd_sig_pair r;
+                    r.a = (uint32_t)a; r.b = (uint32_t)j; r.match = (uint8_t)(eq - E); r.filled = (uint8_t)(64u - E); r.flags = same ? FD_SIG_IDENTICAL : 0u;
+                    P.pairs[slot] = r;
+                }
+            }
+        }
+    }
+}
+
+static int pairs_impl(fdgpu_ctx *c, const fd_signature *A, uint64_t nA, const fd_signature *B, uint64_t nB, uint32_t thr64, uint64_t max_pairs,
+                      fd_sig_pair **pairs, uint64_t *n_pairs) {
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    const bool self = B == nullptr;
+    if (self) nB = nA;
+    unsigned long long found = 0;
+    // every pair there is: the slots never need to be more
+    const long double all = self ? (long double)nA * (long double)(nA ? nA - 1 : 0) / 2 : (long double)nA * (long double)nB;
+    const uint64_t cap = all < (long double)max_pairs ? (uint64_t)all : max_pairs;
+    if (nA && nB) {
+        HIPCHK(c, c->ws[WS_SG_TAB].ensure(nA * sizeof(fd_signature)));
+        if (!self) HIPCHK(c, c->ws[WS_SG_TAB_B].ensure(nB * sizeof(fd_signature)));
+        HIPCHK(c, c->ws[WS_SG_PAIRS].ensure(std::max<uint64_t>(cap, 1) * sizeof(fd_sig_pair)));
+        HIPCHK(c, c->ws[WS_SG_CURSOR].ensure(64));
+        uint32_t *dA = c->ws[WS_SG_TAB].as<uint32_t>(), *dB = self ? dA : c->ws[WS_SG_TAB_B].as<uint32_t>();
+        unsigned long long *cursor = c->ws[WS_SG_CURSOR].as<unsigned long long>();
+        {
+            StageTimer t(c, "sigpairs_upload", (nA + (self ? 0 : nB)) * sizeof(fd_signature));
+            HIPCHK(c, hipMemcpyAsync(dA, A, nA * sizeof(fd_signature), hipMemcpyHostToDevice, st));
+            if (!self) HIPCHK(c, hipMemcpyAsync(dB, B, nB * sizeof(fd_signature), hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemsetAsync(cursor, 0, 8, st));
+        }
+        const uint32_t blocks_b = fd_grid(nB, SG_BLOCK_B), tiles = fd_grid(nA, SG_TILE_A);
+        // a workgroup loads its signatures of B once and walks its share of the tiles: enough workgroups to fill the device, no more
+        const uint32_t gy = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(tiles, 65535u), fd_grid(4096, blocks_b)));
+        {
+            StageTimer t(c, "sigpairs_match", (uint64_t)blocks_b * ((uint64_t)SG_BLOCK_B + (uint64_t)(tiles / gy + 1) * SG_TILE_A) * gy * sizeof(fd_signature));
+            const sg_match_args P{dA, dB, (uint32_t)nA, (uint32_t)nB, thr64, self ? 1u : 0u, c->ws[WS_SG_PAIRS].as<fd_sig_pair>(), cursor, cap};
+            hipLaunchKernelGGL(k_sg_match, dim3(blocks_b, gy), dim3(256), 0, st, P);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&found, cursor, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    *n_pairs = found;
+    if (found > max_pairs) FAIL(c, FDGPU_ERANGE, "signature pairs: " + std::to_string(found) + " pairs qualify, more than max_pairs = " + std::to_string(max_pairs));
+    fd_sig_pair *res = (fd_sig_pair *)fd_out_alloc(std::max<uint64_t>(found, 1) * sizeof(fd_sig_pair));
+    if (!res) FAIL(c, FDGPU_ENOMEM, "signature pairs: out of host memory");
+    if (found) {
+        hipError_t e;
+        {
+            StageTimer t(c, "sigpairs_copy", found * sizeof(fd_sig_pair));
+            e = fd_d2h_big(c, res, c->ws[WS_SG_PAIRS].p, found * sizeof(fd_sig_pair));
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { fdgpu_free(res); c->err = std::string("signature pairs: ") + hipGetErrorString(e); return FDGPU_EHIP; }
+        std::sort(res, res + found, [](const fd_sig_pair &x, const fd_sig_pair &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    }
+    *pairs = res;
+    return FDGPU_OK;
+}
+
+extern "C" int fdgpu_signature_pairs(fdgpu_ctx *c, const fd_signature *A, uint64_t nA, const fd_signature *B, uint64_t nB, uint32_t thr64, uint64_t max_pairs,
+                                     fd_sig_pair **pairs, uint64_t *n_pairs) { FD_LOCK(c);
+    if (!c || !pairs || !n_pairs) return FDGPU_EINVAL;
+    *pairs = nullptr; *n_pairs = 0;
+    if (thr64 < 1 || thr64 > 64) FAIL(c, FDGPU_EINVAL, "signature pairs: thr64 must be 1 .. 64");
+    if (nA > 0xffffffffull || (B && nB > 0xffffffffull)) FAIL(c, FDGPU_EINVAL, "signature pairs: a table of 2^32 or more signatures");
+    if (nA && !A) FAIL(c, FDGPU_EINVAL, "signature pairs: table A is NULL");
+    const int rc = pairs_impl(c, A, nA, B, nB, thr64, max_pairs, pairs, n_pairs);
+    if (rc != FDGPU_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}

@@ -442,6 +442,126 @@ def rows_host(value, hashes, offsets, n_structures: int, first_id: int = 0, lo=N
     return _lib.owned_view(L, oh, int(off[-1]) * 4, np.uint32), off
 
 
+# ---- index signatures (include/fdgpu.h: fd_signature, fd_sig_pair) ---------------------------------------------------------------------------
+SIGNATURE_DTYPE = np.dtype([("n", "<u4"), ("reserved", "<u4"), ("d0", "<u8"), ("d1", "<u8"), ("sk", "<u4", (64,))])      # 280 bytes
+SIGNATURE_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("match", "u1"), ("filled", "u1"), ("flags", "<u2")])      # 12 bytes; flags bit 0 = identical
+SIGNATURE_PAIRS_DTYPE = np.dtype(SIGNATURE_PAIR_DTYPE.descr + [("estimate", "<f8")])      # what the pair calls return: the record + match / filled
+SIG_EMPTY = 0xffffffff
+SIG_IDENTICAL = 1
+assert SIGNATURE_DTYPE.itemsize == 280 and SIGNATURE_PAIR_DTYPE.itemsize == 12
+
+
+def signature_mix(h) -> np.ndarray:
+    """m(h): the splitmix64 finaliser of u32 hashes, as a u64 array"""
+    with np.errstate(over="ignore"):
+        z = np.asarray(h, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def signatures_from_rows(hashes, row_off) -> np.ndarray:
+    """THE SPECIFICATION of the index signatures, in plain numpy: rows as CSR (what FolddiscoIndex.rows / rows_host return) -> one
+    SIGNATURE_DTYPE record per row.  With m = signature_mix(h) over the row's distinct hashes: n = their number, d0 = the sum of m mod 2^64,
+    d1 = the xor of m, sk[b] = the smallest (m >> 26) & 0xffffffff among the hashes with m >> 58 == b, 0xffffffff for a bucket without one
+    (so a value of 0xffffffff in a filled bucket reads as empty, in every form alike).  An empty row: n = d0 = d1 = 0, every sk 0xffffffff.
+    The device form (FolddiscoIndex.signatures) and the host form (signatures_host) agree with it bit for bit"""
+    hashes = np.asarray(hashes, dtype=np.uint32)
+    off = np.asarray(row_off).astype(np.int64)
+    out = np.zeros(len(off) - 1, SIGNATURE_DTYPE)
+    out["sk"] = SIG_EMPTY
+    m = signature_mix(hashes)
+    bucket = (m >> np.uint64(58)).astype(np.int64)
+    v = ((m >> np.uint64(26)) & np.uint64(0xffffffff)).astype(np.uint32)
+    for s in range(len(out)):
+        lo, hi = int(off[s]), int(off[s + 1])
+        if hi == lo:
+            continue
+        out["n"][s] = hi - lo
+        with np.errstate(over="ignore"):
+            out["d0"][s] = np.add.reduce(m[lo:hi], dtype=np.uint64)
+        out["d1"][s] = np.bitwise_xor.reduce(m[lo:hi])
+        np.minimum.at(out["sk"][s], bucket[lo:hi], v[lo:hi])
+    return out
+
+
+def _sig_table(t, name):
+    t = np.ascontiguousarray(t)
+    if t.dtype != SIGNATURE_DTYPE or t.ndim != 1:
+        raise ValueError(f"{name}: a 1-d array of indexio.SIGNATURE_DTYPE expected")
+    return t
+
+
+def signature_threshold(min_similarity: float) -> int:
+    """thr64 of a similarity: ceil(min_similarity * 64), clamped to 1 .. 64"""
+    import math
+    return max(1, min(64, int(math.ceil(float(min_similarity) * 64))))
+
+
+def signature_pairs_result(L, pp, n: int) -> np.ndarray:
+    """the library's pair records as SIGNATURE_PAIRS_DTYPE (estimate = match / filled, computed here); releases the block"""
+    raw = _lib.owned_view(L, pp, n * SIGNATURE_PAIR_DTYPE.itemsize, np.uint8).view(SIGNATURE_PAIR_DTYPE) if n else np.zeros(0, SIGNATURE_PAIR_DTYPE)
+    if not n and pp:
+        L.fdgpu_free(pp)
+    out = np.zeros(n, SIGNATURE_PAIRS_DTYPE)
+    for k in SIGNATURE_PAIR_DTYPE.names:
+        out[k] = raw[k]
+    out["estimate"] = raw["match"].astype(np.float64) / np.maximum(raw["filled"], 1)
+    return out
+
+
+class SignaturePairsOverflow(ValueError):
+    """more pairs qualify than max_pairs; .count = how many do"""
+
+    def __init__(self, count: int, max_pairs: int):
+        super().__init__(f"signature pairs failed (-4): {count} pairs qualify, more than max_pairs = {max_pairs}; raise the threshold or the cap")
+        self.count, self.max_pairs = count, max_pairs
+
+
+def signatures_host(value, hashes, offsets, n_structures: int, first_id: int = 0, lo=None, hi=None, threads: int = 1) -> np.ndarray:
+    """index signatures from host arrays (fdgpu_signatures_host: no context, no device): one SIGNATURE_DTYPE record for each of the structures
+    lo .. hi - 1 (absolute ids; default: the whole index), see signatures_from_rows.  The result does not depend on `threads`.  Raises
+    ValueError with the library's code in it, as rows_host does"""
+    value = np.ascontiguousarray(value, dtype=np.uint8)
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(hashes) + 1:
+        raise ValueError(f"offsets: {len(hashes) + 1} entries expected, got {len(offsets)}")
+    lo = int(first_id) if lo is None else int(lo)
+    hi = int(first_id) + int(n_structures) if hi is None else int(hi)
+    if lo < 0 or hi < lo:
+        raise ValueError("fdgpu_signatures_host failed (-1): lo <= hi, absolute structure ids, expected")
+    L = _lib.load()
+    op = C.c_void_p()
+    rc = L.fdgpu_signatures_host(hashes.ctypes.data_as(u32p), offsets.ctypes.data_as(u64p), len(hashes), value.ctypes.data_as(u8p), len(value), int(first_id),
+                                 int(n_structures), lo, hi, max(int(threads), 1), C.byref(op))
+    if rc != 0:
+        raise ValueError(f"fdgpu_signatures_host failed ({rc}): " + ("a list reaches 4 GiB" if rc == -4 else
+                         "the range is not inside the index, or the index is damaged or holds ids outside [first_id, first_id + n_structures)"))
+    return _lib.owned_view(L, op, (hi - lo) * SIGNATURE_DTYPE.itemsize, np.uint8).view(SIGNATURE_DTYPE)
+
+
+def signature_pairs_host(A, B=None, min_similarity: float = 0.9, max_pairs: int = 1 << 24, threads: int = 1, thr64=None) -> np.ndarray:
+    """every reported pair of two signature tables on the CPU (fdgpu_signature_pairs_host: no context, no device), sorted by (a, b), as
+    SIGNATURE_PAIRS_DTYPE.  B = None: A against itself, a < b only.  A pair is reported iff both rows are non-empty and
+    match * 64 >= thr64 * filled with thr64 = signature_threshold(min_similarity) (or the given thr64); estimate = match / filled.  Raises
+    SignaturePairsOverflow (with the true count) when more than max_pairs pairs qualify, ValueError for a thr64 outside 1 .. 64"""
+    A = _sig_table(A, "A")
+    B = None if B is None else _sig_table(B, "B")
+    t = signature_threshold(min_similarity) if thr64 is None else int(thr64)
+    if not 0 <= t <= 0xffffffff:
+        raise ValueError("fdgpu_signature_pairs_host failed (-1): thr64 must be 1 .. 64")
+    L = _lib.load()
+    pp, n = C.c_void_p(), C.c_uint64()
+    rc = L.fdgpu_signature_pairs_host(A.ctypes.data, len(A), None if B is None else B.ctypes.data, 0 if B is None else len(B), t, int(max_pairs),
+                                      max(int(threads), 1), C.byref(pp), C.byref(n))
+    if rc == -4:
+        raise SignaturePairsOverflow(int(n.value), int(max_pairs))
+    if rc != 0:
+        raise ValueError(f"fdgpu_signature_pairs_host failed ({rc}): thr64 must be 1 .. 64 and a table holds fewer than 2^32 signatures")
+    return signature_pairs_result(L, pp, int(n.value))
+
+
 def permute_lookup_rows(rows, new_id, keep_db_keys: bool):
     """the rows of PREFIX.lookup after a reorder: row k moves to position new_id[k], tid, nres and plddt verbatim, the id renumbered 0 .. n - 1; the
     db_key column renumbered with it for a file-built index (there it equals the id) and kept for a Foldcomp-built one (its database key) -- the

@@ -596,6 +596,51 @@ int fdgpu_rows_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_
                     uint64_t first_id, uint64_t n_structures, uint64_t id_lo, uint64_t id_hi, uint32_t n_threads,
                     uint32_t **row_hashes, uint64_t **row_off);
 
+/* ---- index signatures --------------------------------------------------------------------------------------------------------
+ * A fixed-size reduction of a structure's row R (the set of distinct hashes whose posting lists hold it; what fdgpu_index_rows returns).
+ * With m(h) the splitmix64 finaliser of a hash, all arithmetic mod 2^64:
+ *     z = (uint64)h + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  m = z ^ (z >> 31)
+ * the signature holds |R|, the sum and the xor of m over R (equal rows give equal digests) and a one-permutation MinHash of 64 buckets: bucket
+ * b = m >> 58 keeps the smallest v = (uint32_t)(m >> 26) of its hashes, 0xFFFFFFFF when it has none.  A v of 0xFFFFFFFF in a bucket that is not
+ * empty reads as empty; every form (device, host, indexio.signatures_from_rows) does the same by construction.  An empty row: n = 0, d0 = d1 = 0,
+ * every sk 0xFFFFFFFF.  The signature is a function of the row alone, so it moves with the structure under permute, rebase, split, merge and
+ * remove.  280 bytes, little endian. */
+typedef struct fd_signature {
+    uint32_t n;               /* |R| */
+    uint32_t reserved;        /* 0 */
+    uint64_t d0;              /* sum of m(h) over R, mod 2^64 */
+    uint64_t d1;              /* xor of m(h) over R */
+    uint32_t sk[64];          /* bucket minima */
+} fd_signature;
+/* A reported pair of signatures a (of table A) and b (of table B), positions in their tables.  With E = buckets empty in both,
+ * match = buckets that agree - E, filled = 64 - E: the pair is reported iff a.n > 0 && b.n > 0 && filled > 0 && match * 64 >= thr64 * filled
+ * (integers only: the device and the host form agree exactly); match / filled estimates the Jaccard similarity of the two rows.
+ * flags bit 0 (identical): n, d0 and d1 agree.  12 bytes. */
+typedef struct fd_sig_pair { uint32_t a, b; uint8_t match, filled; uint16_t flags; } fd_sig_pair;
+#define FD_SIG_IDENTICAL 1u
+
+/* Signatures of the structures id_lo .. id_hi - 1 of a resident index (absolute ids, the range rule of fdgpu_index_rows): *out holds
+ * id_hi - id_lo records, released with fdgpu_free.  The index is walked in windows of `window` structures (0 = 16384): per window the rows stay
+ * on the device (the stages of fdgpu_index_rows without the copy out) and one wavefront per row reduces them (csrc/k_sig.hip); the result does
+ * not depend on `window` and is byte-identical from run to run.  Workspace follows the window as for the rows, plus 280 bytes per structure of
+ * it.  The refusals and error codes are those of fdgpu_index_rows, with the message prefix "index signatures:"; on any error *out is NULL. */
+int fdgpu_index_signatures(fdgpu_ctx *ctx, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, uint64_t window, fd_signature **out);
+/* The same signatures from host arrays (the payload of PREFIX.offset and PREFIX) by another algorithm: one pass over the lists, m(h) once per
+ * list, every decoded id of the range updates its record.  n_threads host threads (0 = 1); the result does not depend on their number.  No
+ * device.  Same records and same error codes as the device form for an index without last ids (and FDGPU_EINVAL when first_id + n_structures
+ * exceeds 32 bits); released with fdgpu_free. */
+int fdgpu_signatures_host(const uint32_t *hashes, const uint64_t *offsets, uint64_t n_hashes, const uint8_t *value, uint64_t value_len,
+                          uint64_t first_id, uint64_t n_structures, uint64_t id_lo, uint64_t id_hi, uint32_t n_threads, fd_signature **out);
+/* Every pair (a of A, b of B) that is reported at thr64 (1 .. 64), sorted ascending by (a, b): byte-identical from run to run.  A and B are
+ * host tables; B == NULL is self mode: A against itself, only a < b reported (nB is ignored).  More than max_pairs qualifying pairs:
+ * FDGPU_ERANGE, *n_pairs = the true count, *pairs NULL.  thr64 outside 1 .. 64 or nA / nB >= 2^32: FDGPU_EINVAL before any device work.
+ * *pairs (never NULL on success) is released with fdgpu_free. */
+int fdgpu_signature_pairs(fdgpu_ctx *ctx, const fd_signature *A, uint64_t nA, const fd_signature *B, uint64_t nB, uint32_t thr64,
+                          uint64_t max_pairs, fd_sig_pair **pairs, uint64_t *n_pairs);
+/* The same pairs on the CPU (a blocked double loop, n_threads host threads, 0 = 1).  No device. */
+int fdgpu_signature_pairs_host(const fd_signature *A, uint64_t nA, const fd_signature *B, uint64_t nB, uint32_t thr64, uint64_t max_pairs,
+                               uint32_t n_threads, fd_sig_pair **pairs, uint64_t *n_pairs);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
