@@ -514,6 +514,18 @@ def cmd_verify(a):
     sys.exit(0 if rep.ok else 1)
 
 
+def _ids_of_tids(cmd, asked, path, tids, index):
+    """the ids of the tids asked for, in their order, every row that carries the tid; status 1 and a [FAIL] line for a tid the index does not hold"""
+    where = {}
+    for k, t in enumerate(tids):
+        where.setdefault(t, []).append(k)
+    unknown = [t for t in dict.fromkeys(asked) if t not in where]
+    if unknown:
+        print(f"[FAIL] {cmd}: {len(unknown)} tid(s) of {path} are not in {index}.lookup: " + ", ".join(unknown[:10]) + (" ..." if len(unknown) > 10 else ""))
+        sys.exit(1)
+    return np.array([k for t in asked for k in where[t]], dtype=np.int64)
+
+
 def _rows_plan(a):
     """everything `rows` decides before it opens a device: -> (structures of the index, chosen ids in the order asked for, their tids).  Status 2
     for missing or unreadable files, status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
@@ -541,14 +553,7 @@ def _rows_plan(a):
         sys.exit(1)
     n = len(tids)
     if asked is not None:
-        where = {}
-        for k, t in enumerate(tids):
-            where.setdefault(t, []).append(k)
-        unknown = [t for t in dict.fromkeys(asked) if t not in where]
-        if unknown:
-            print(f"[FAIL] rows: {len(unknown)} tid(s) of {a.tids} are not in {a.index}.lookup: " + ", ".join(unknown[:10]) + (" ..." if len(unknown) > 10 else ""))
-            sys.exit(1)
-        ids = np.array([k for t in asked for k in where[t]], dtype=np.int64)      # the file's order; every row that carries the tid
+        ids = _ids_of_tids("rows", asked, a.tids, tids, a.index)
     else:
         lo, hi = 0, n
         if a.range is not None:
@@ -620,20 +625,26 @@ def cmd_rows(a):
 def _dups_plan(a):
     """everything `dups` decides before it opens a device: -> (prefixes, their tids).  Status 2 for missing or unreadable files, status 1 and a
     [FAIL] line for a refusal; nothing is written in either case."""
+    if a.max_pairs < 0:
+        sys.exit("[FAIL] dups: --max-pairs must not be negative")
+    return _sig_plan(a, "dups")
+
+
+def _sig_plan(a, cmd):
+    """what `dups` and `neighbors` check alike before a device is opened: the threshold and the window, that -i (and --against) name single,
+    consistent indices that are not the same one and whose .type files agree -> (prefixes, their tids)"""
     import glob
     from folddisco_amd import indexio
     if not 0.0 < a.min_similarity <= 1.0:            # NaN fails it too
-        sys.exit(f"[FAIL] dups: --min-similarity {a.min_similarity} is outside (0, 1]")
+        sys.exit(f"[FAIL] {cmd}: --min-similarity {a.min_similarity} is outside (0, 1]")
     if a.window < 1:
-        sys.exit("[FAIL] dups: --window must be at least 1")
-    if a.max_pairs < 0:
-        sys.exit("[FAIL] dups: --max-pairs must not be negative")
+        sys.exit(f"[FAIL] {cmd}: --window must be at least 1")
     prefixes = [a.index] + ([a.against] if a.against is not None else [])
     if len(prefixes) == 2 and os.path.abspath(prefixes[0]) == os.path.abspath(prefixes[1]):
-        sys.exit(f"[FAIL] dups: --against {a.against} is the index itself; leave it out to look for duplicates inside one index")
+        sys.exit(f"[FAIL] {cmd}: --against {a.against} is the index itself; leave it out to look for duplicates inside one index")
     for p in prefixes:
         if not os.path.isfile(p) and glob.glob(glob.escape(p) + ".shard*of*"):
-            print(f"[FAIL] dups: {p} is a sharded index; write the single index first (`reshard -i {p} --from V --to 1`)")
+            print(f"[FAIL] {cmd}: {p} is a sharded index; write the single index first (`reshard -i {p} --from V --to 1`)")
             sys.exit(1)
         for ext in INDEX_FILES:
             if not os.path.isfile(p + ext):
@@ -647,14 +658,14 @@ def _dups_plan(a):
             with open(p + ".type") as f:
                 texts.append(f.read())
     except (OSError, ValueError, UnicodeDecodeError) as e:
-        print(f"[FAIL] dups: unreadable input ({e})", file=sys.stderr)
+        print(f"[FAIL] {cmd}: unreadable input ({e})", file=sys.stderr)
         sys.exit(2)
     if bad:
         print("[FAIL] index files are inconsistent: " + "; ".join(bad))
         sys.exit(1)
     key = indexio.check_joinable(texts)
     if key is not None:
-        print(f"[FAIL] dups: the two indices' .type files differ in {key}: signatures of indices built with different settings are not comparable")
+        print(f"[FAIL] {cmd}: the two indices' .type files differ in {key}: signatures of indices built with different settings are not comparable")
         sys.exit(1)
     return prefixes, tids
 
@@ -697,6 +708,36 @@ def _dups_rows(a, ctx, prefix, n, ids):
     return out
 
 
+def _dups_jaccard(a, ctx, prefixes, tids, ia, ib):
+    """the exact Jaccard similarity of the pairs (ia[k] of the first index, ib[k] of the second one, or of the first if there is one only),
+    from the rows of their structures"""
+    two = len(prefixes) == 2
+    ids_a = np.unique(np.concatenate([ia, ib]) if not two else ia).astype(np.int64)
+    rows_a = _dups_rows(a, ctx, prefixes[0], len(tids[0]), ids_a)
+    rows_b = _dups_rows(a, ctx, prefixes[1], len(tids[1]), np.unique(ib).astype(np.int64)) if two else rows_a
+    jac = []
+    for ka, kb in zip(ia, ib):
+        x, y = rows_a[int(ka)], rows_b[int(kb)]
+        inter = len(np.intersect1d(x, y))
+        jac.append(inter / max(len(x) + len(y) - inter, 1))
+    return jac
+
+
+def _write_tsv(output, lines, cmd):
+    """the lines to `output` under a temporary name, then renamed; to standard output without one"""
+    if not output:
+        sys.stdout.writelines(lines)
+        return
+    tmp = f"{output}.{cmd}-tmp{os.getpid()}"
+    try:
+        with open(tmp, "w") as f:
+            f.writelines(lines)
+        os.replace(tmp, output)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
 def cmd_dups(a):
     """`dups`: which structures are already there?  Every structure of the index at PREFIX is reduced to its signature (fdgpu_index_signatures:
     size, two digests and a 64-bucket MinHash sketch of its row) and the signatures are compared all against all, inside the index or, with
@@ -723,16 +764,7 @@ def cmd_dups(a):
             sys.exit(1)
         if a.identical_only:
             pairs = pairs[(pairs["flags"] & indexio.SIG_IDENTICAL) != 0]
-        jac = None
-        if a.confirm:
-            ids_a = np.unique(np.concatenate([pairs["a"], pairs["b"]]) if not two else pairs["a"]).astype(np.int64)
-            rows_a = _dups_rows(a, ctx, prefixes[0], len(tids[0]), ids_a)
-            rows_b = _dups_rows(a, ctx, prefixes[1], len(tids[1]), np.unique(pairs["b"]).astype(np.int64)) if two else rows_a
-            jac = []
-            for r in pairs:
-                x, y = rows_a[int(r["a"])], rows_b[int(r["b"])]
-                inter = len(np.intersect1d(x, y))
-                jac.append(inter / max(len(x) + len(y) - inter, 1))
+        jac = _dups_jaccard(a, ctx, prefixes, tids, pairs["a"], pairs["b"]) if a.confirm else None
     except (OSError, ValueError) as e:
         print(f"[FAIL] dups: {e}", file=sys.stderr)
         sys.exit(2 if isinstance(e, OSError) else 1)
@@ -745,22 +777,77 @@ def cmd_dups(a):
         if jac is not None:
             cols.append(f"{jac[k]:.4f}")
         lines.append("\t".join(cols) + "\n")
-    if a.output:
-        tmp = f"{a.output}.dups-tmp{os.getpid()}"
-        try:
-            with open(tmp, "w") as f:
-                f.writelines(lines)
-            os.replace(tmp, a.output)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-    else:
-        sys.stdout.writelines(lines)
+    _write_tsv(a.output, lines, "dups")
     n_ident = int(((pairs["flags"] & indexio.SIG_IDENTICAL) != 0).sum())
     print(f"[OK] {' x '.join(prefixes)}: {' x '.join(str(len(t)) for t in tids)} structures, {len(pairs)} pairs ({n_ident} identical), threshold {thr64}/64")
     if a.verbose:
         print(f"[INFO] dups on the {'host' if a.host else 'device'}: signatures of {sum(len(t) for t in tids)} structures ({sum(t.nbytes for t in tabs)} bytes)"
               + (f", {len(jac)} pairs confirmed from their rows" if jac is not None else ""), file=sys.stderr)
+
+
+def cmd_neighbors(a):
+    """`neighbors`: for every structure of the index at PREFIX its K nearest structures by signature, among the other structures of PREFIX or,
+    with --against, among those of PREFIX2, selected on the device (fdgpu_signature_neighbors) or with --host on the CPU (no device is opened).
+    --tids FILE restricts the queries to the structures with those tids; --min-similarity is the floor a neighbour must reach (default 1 / 64: one
+    agreeing filled bucket).  One TSV row per neighbour, sorted by (id, rank): id tid n rank nb_id nb_tid nb_n match filled estimate
+    class[ jaccard]; rank counts from 1, nearest first: by match / filled, then by filled, then by nb_id.  A structure without a neighbour gets
+    no row.  This is the order of the sketches, not an exact nearest-neighbour search: --confirm adds the exact Jaccard similarity from the rows
+    but does not reorder.  No structure file is read."""
+    from folddisco_amd import indexio
+    if not 1 <= a.k <= indexio.SIG_MAX_K:
+        sys.exit(f"[FAIL] neighbors: -k {a.k} is outside 1..{indexio.SIG_MAX_K}")
+    if a.tids is not None and not os.path.isfile(a.tids):
+        print(f"[FAIL] {a.tids} not found", file=sys.stderr)
+        sys.exit(2)
+    prefixes, tids = _sig_plan(a, "neighbors")
+    two = len(prefixes) == 2
+    ids = None
+    if a.tids is not None:
+        try:
+            with open(a.tids) as f:
+                asked = [line.strip() for line in f if line.strip()]
+        except (OSError, UnicodeDecodeError) as e:
+            print(f"[FAIL] neighbors: unreadable input ({e})", file=sys.stderr)
+            sys.exit(2)
+        ids = np.unique(_ids_of_tids("neighbors", asked, a.tids, tids[0], a.index))
+    thr64 = indexio.signature_threshold(a.min_similarity)
+    try:
+        ctx = None
+        if not a.host:
+            import folddisco_amd as fd
+            ctx = fd.Context(a.device)
+        tabs = [_dups_signatures(a, ctx, p, len(t)) for p, t in zip(prefixes, tids)]
+        A, D = tabs[0], (tabs[1] if two else tabs[0])
+        if ids is None:
+            ids = np.arange(len(A), dtype=np.int64)
+            Q, cand, excl = A, (D if two else None), None
+        else:                                        # chosen queries: against the whole table, each one's own id excluded inside one index
+            Q, cand, excl = A[ids], D, (None if two else ids.astype(np.uint32))
+        nb = indexio.signature_neighbors_host(Q, cand, k=a.k, thr64=thr64, exclude=excl, threads=a.threads) if a.host else \
+            ctx.signature_neighbors(Q, cand, k=a.k, thr64=thr64, exclude=excl)
+        at_q, at_r = np.nonzero(nb["id"] != indexio.SIG_NO_ID)       # row-major: ascending (id, rank)
+        got = nb[at_q, at_r]
+        jac = _dups_jaccard(a, ctx, prefixes, tids, ids[at_q], got["id"]) if a.confirm else None
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] neighbors: {e}", file=sys.stderr)
+        sys.exit(2 if isinstance(e, OSError) else 1)
+    td = tids[1] if two else tids[0]
+    lines = []
+    for j, (q, rank, r) in enumerate(zip(at_q, at_r, got)):
+        iq, ib = int(ids[q]), int(r["id"])
+        cols = [str(iq), tids[0][iq], str(int(A["n"][iq])), str(int(rank) + 1), str(ib), td[ib], str(int(D["n"][ib])), str(int(r["match"])), str(int(r["filled"])),
+                f"{int(r['match']) / int(r['filled']):.4f}", "identical" if int(r["flags"]) & indexio.SIG_IDENTICAL else "similar"]
+        if jac is not None:
+            cols.append(f"{jac[j]:.4f}")
+        lines.append("\t".join(cols) + "\n")
+    _write_tsv(a.output, lines, "neighbors")
+    n_none = int((nb["id"][:, 0] == indexio.SIG_NO_ID).sum())
+    n_ident = int(((nb["flags"][:, 0] & indexio.SIG_IDENTICAL) != 0).sum())
+    print(f"[OK] {' x '.join(prefixes)}: {' x '.join(str(len(t)) for t in tids)} structures, k = {a.k}, {len(lines)} rows, {n_none} without a neighbour, "
+          f"{n_ident} with an identical nearest, floor {thr64}/64")
+    if a.verbose:
+        print(f"[INFO] neighbors on the {'host' if a.host else 'device'}: {len(ids)} queries, signatures of {sum(len(t) for t in tids)} structures "
+              f"({sum(t.nbytes for t in tabs)} bytes)" + (f", {len(jac)} rows confirmed from their rows" if jac is not None else ""), file=sys.stderr)
 
 
 def _reshard_plan(a):
@@ -1389,6 +1476,20 @@ def main(argv=None):
     pd.add_argument("--device", type=int, default=0)
     pd.add_argument("--verify", action="store_true", help="check every loaded index first (see `verify`) and stop with status 1 if it is damaged")
     pd.add_argument("-v", "--verbose", action="store_true")
+    pn = sub.add_parser("neighbors")                                 # the k nearest structures of every structure, by signature (no counterpart in the reference)
+    pn.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
+    pn.add_argument("--against", default=None, help="a second index prefix: the neighbours are looked for among its structures (default: among the others of PREFIX)")
+    pn.add_argument("-k", type=int, default=8, help="neighbours per structure, 1..32")
+    pn.add_argument("--min-similarity", type=float, default=1.0 / 64, help="the share of agreeing filled buckets a neighbour must reach, in (0, 1]")
+    pn.add_argument("--tids", default=None, help="text file with one tid per line (column 2 of PREFIX.lookup): only these structures are queries")
+    pn.add_argument("--confirm", action="store_true", help="add the exact Jaccard similarity of every row, from the rows of its structures")
+    pn.add_argument("-o", "--output", default="", help="the TSV file to write (default: standard output)")
+    pn.add_argument("--window", type=int, default=16384, help="structures per walk over the index")
+    pn.add_argument("--host", action="store_true", help="reduce and select on the CPU (no device is opened)")
+    pn.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    pn.add_argument("--device", type=int, default=0)
+    pn.add_argument("--verify", action="store_true", help="check every loaded index first (see `verify`) and stop with status 1 if it is damaged")
+    pn.add_argument("-v", "--verbose", action="store_true")
     pr = sub.add_parser("reshard")                                   # one index <-> shards by structure id range (no counterpart in the reference)
     pr.add_argument("-i", "--index", required=True)
     pr.add_argument("--to", type=int, required=True, help="shards to write (PREFIX.shard<r>ofW); 1 writes the single index")
@@ -1462,6 +1563,9 @@ def main(argv=None):
         return
     if a.cmd == "dups":
         cmd_dups(a)
+        return
+    if a.cmd == "neighbors":
+        cmd_neighbors(a)
         return
     if a.cmd == "reshard":
         cmd_reshard(a)

@@ -142,6 +142,16 @@ class Context:
         self.check(rc)
         return indexio.signature_pairs_result(self.L, pp, int(n.value))
 
+    def signature_neighbors(self, Q, D=None, k: int = 8, min_similarity=None, thr64: int = 1, exclude=None) -> np.ndarray:
+        """the k nearest signatures of D for every signature of Q, selected on the device (fdgpu_signature_neighbors): a (len(Q), k) array of
+        indexio.SIGNATURE_NEIGHBOR_DTYPE; the contract of indexio.signature_neighbors_host, which it equals byte for byte"""
+        from . import indexio
+        Q, D, k, t, exclude = indexio._sig_neighbor_args(Q, D, k, min_similarity, thr64, exclude)
+        op = C.c_void_p()
+        self.check(self.L.fdgpu_signature_neighbors(self.h, Q.ctypes.data, len(Q), None if D is None else D.ctypes.data, 0 if D is None else len(D),
+                                                    None if exclude is None else exclude.ctypes.data, k, t, C.byref(op)))
+        return indexio.signature_neighbors_result(self.L, op, len(Q), k)
+
     # ---- batches
     def upload(self, ps: PackedStructures) -> "Batch":
         d = BatchDesc(ps.n_struct, _ptr(ps.res_off, u64p), _ptr(ps.n_xyz, f32p), _ptr(ps.ca_xyz, f32p), _ptr(ps.cb_xyz, f32p),

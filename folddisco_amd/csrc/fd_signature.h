@@ -29,3 +29,12 @@ FD_SIG_HD bool fd_sig_reported(uint32_t na, uint32_t nb, uint32_t eq, uint32_t E
     const uint32_t match = eq - E, filled = 64u - E;
     return na > 0 && nb > 0 && filled > 0 && match * 64u >= thr64 * filled;
 }
+
+// is candidate x nearer than candidate y (include/fdgpu.h: signature neighbours)?  The larger match / filled, then the larger filled, then the
+// smaller id: a total order.  An empty slot (match = filled = 0, id = 0xFFFFFFFF) is farther than every candidate, which has filled > 0
+FD_SIG_HD bool fd_sig_nearer(uint32_t mx, uint32_t fx, uint32_t idx, uint32_t my, uint32_t fy, uint32_t idy) {
+    const uint32_t l = mx * fy, r = my * fx;
+    return l != r ? l > r : fx != fy ? fx > fy : idx < idy;
+}
+static_assert(sizeof(fd_sig_neighbor) == 8, "fd_sig_neighbor layout");
+#define FD_SIG_NO_ID 0xffffffffu

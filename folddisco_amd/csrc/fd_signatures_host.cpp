@@ -7,6 +7,8 @@
 // Every thread makes the checks of fdgpu_rows_host on every list (the same lists are left behind their head: those that start at or above id_hi),
 // so the same input gives the same error code; nothing is handed out unless every list was sound.
 // Pairs: a blocked double loop, threads over the blocks of A, the records sorted by (a, b) at the end.
+// Neighbours: the same blocked loop over (Q blocks x D blocks), threads over the Q blocks; every query's k-list is its row of the result, kept
+// sorted by insertion under fd_sig_nearer, so no two threads touch the same row and the result does not depend on their number.
 #include <cstring>
 #include "fd_signature.h"
 #include "fd_postings_host.h"
@@ -126,5 +128,48 @@ extern "C" int fdgpu_signature_pairs_host(const fd_signature *A, uint64_t nA, co
     for (auto &g : got) { if (!g.empty()) memcpy(res + at, g.data(), g.size() * sizeof(fd_sig_pair)); at += g.size(); }
     std::sort(res, res + total, [](const fd_sig_pair &x, const fd_sig_pair &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
     *pairs = res;
+    return FDGPU_OK;
+}
+
+extern "C" int fdgpu_signature_neighbors_host(const fd_signature *Q, uint64_t nQ, const fd_signature *D, uint64_t nD, const uint32_t *exclude, uint32_t k,
+                                              uint32_t thr64, uint32_t n_threads, fd_sig_neighbor **out) {
+    if (!out) return FDGPU_EINVAL;
+    *out = nullptr;
+    if (k < 1 || k > FD_SIG_MAX_K || thr64 < 1 || thr64 > 64) return FDGPU_EINVAL;
+    if (nQ > 0xffffffffull || (D && nD > 0xffffffffull) || (nQ && !Q) || (!D && exclude)) return FDGPU_EINVAL;
+    const bool self = D == nullptr;
+    if (self) { D = Q; nD = nQ; }
+    fd_sig_neighbor *res = (fd_sig_neighbor *)malloc(std::max<uint64_t>(nQ * k, 1) * sizeof(fd_sig_neighbor));
+    if (!res) return FDGPU_ENOMEM;
+    const fd_sig_neighbor none = {FD_SIG_NO_ID, 0, 0, 0};
+    for (uint64_t i = 0; i < std::max<uint64_t>(nQ * k, 1); ++i) res[i] = none;
+    const uint64_t BLK = 64, n_blk = (nQ + BLK - 1) / BLK;
+    const uint64_t T = fd_host_threads(n_threads, n_blk, 1);
+    fd_over_ranges(T, [&](uint64_t t) {
+        for (uint64_t bq = n_blk * t / T; bq < n_blk * (t + 1) / T; ++bq) {
+            const uint64_t q0 = bq * BLK, q1 = std::min(nQ, q0 + BLK);
+            for (uint64_t d0 = 0; d0 < nD; d0 += BLK) {
+                const uint64_t d1 = std::min(nD, d0 + BLK);
+                for (uint64_t q = q0; q < q1; ++q) {
+                    if (!Q[q].n) continue;
+                    const uint64_t skip = self ? q : exclude ? exclude[q] : FD_SIG_NO_ID;
+                    fd_sig_neighbor *row = res + q * k;
+                    for (uint64_t d = d0; d < d1; ++d) {
+                        if (d == skip) continue;
+                        const sg_stat s = sig_compare(Q[q], D[d]);
+                        if (!fd_sig_reported(Q[q].n, D[d].n, s.eq, s.E, thr64)) continue;
+                        const uint32_t m = s.eq - s.E, f = 64u - s.E;
+                        uint32_t at = k;                                      // the slot it takes: behind everything that is nearer
+                        while (at > 0 && fd_sig_nearer(m, f, (uint32_t)d, row[at - 1].match, row[at - 1].filled, row[at - 1].id)) --at;
+                        if (at == k) continue;
+                        for (uint32_t j = k - 1; j > at; --j) row[j] = row[j - 1];
+                        row[at].id = (uint32_t)d; row[at].match = (uint8_t)m; row[at].filled = (uint8_t)f;
+                        row[at].flags = Q[q].n == D[d].n && Q[q].d0 == D[d].d0 && Q[q].d1 == D[d].d1 ? FD_SIG_IDENTICAL : 0u;
+                    }
+                }
+            }
+        }
+    });
+    *out = res;
     return FDGPU_OK;
 }

@@ -1,5 +1,5 @@
-// k_sig.hip — index signatures (fdgpu_index_signatures) and their all-pairs compare (fdgpu_signature_pairs); the definitions are include/fdgpu.h
-// and fd_signature.h, the host forms fd_signatures_host.cpp.
+// k_sig.hip — index signatures (fdgpu_index_signatures), their all-pairs compare (fdgpu_signature_pairs) and their k nearest neighbours
+// (fdgpu_signature_neighbors); the definitions are include/fdgpu.h and fd_signature.h, the host forms fd_signatures_host.cpp.
 //
 // Signatures: the index is walked in windows of structures.  Per window the device stage of the rows (fd_rows_device, k_rows.hip) leaves the
 // window's hashes in (id, hash) order and the row offsets in the context's workspaces, and
@@ -20,6 +20,15 @@
 //                 count comes back.  Self mode skips the tiles wholly on or below the diagonal and tests a < b inside the others.
 // The records are sorted by (a, b) on the host (at most max_pairs of them), so the result does not depend on the order the kernel found them in.
 // VALU work: 128 lane-operations per pair.  Workspace: 280 bytes per signature, 12 per pair slot (at most min(max_pairs, every pair)).
+//
+// Neighbours: the tables are uploaded as for the pairs, and
+//   k_sg_near        the layout of k_sg_match (a query per lane in registers, tiles of 64 candidates broadcast from LDS, gridDim.y shares the
+//                    tiles), with a selection in place of the cursor: every lane keeps its k nearest so far as a sorted list in LDS
+//                    ([slot][lane], k * 1.5 KB per workgroup, sized by the launch) and the list's last entry in registers.  A candidate that
+//                    passes the predicate is compared with that entry first; only a winner touches the list (a bisection and a shift: about
+//                    k ln(nD / k) of them per query, none in the steady state).  No global atomic, no cursor.  Every tile in self mode too.
+//   k_sg_near_merge  only when gridDim.y > 1: a wavefront per query takes the nearest head of the gridDim.y sorted lists k times.
+// The order (fd_sig_nearer) is total, so the result is the same bytes for every split.  Workspace: 280 bytes per signature, 8 k per query and split.
 #include <algorithm>
 #include <cstring>
 #include "fdgpu_internal.h"
@@ -119,13 +128,32 @@ extern "C" int fdgpu_index_signatures(fdgpu_ctx *c, const fdgpu_index *ix, uint6
 
 // ---- match.  Grid: x = workgroups of 256 signatures of B, y = the tiles of A a workgroup takes in turn (tile ta = blockIdx.y, + gridDim.y, ...).
 // Reads A[0 .. nA), B[0 .. nB); writes pairs[slot] for slot < max_pairs only.
+// the tile A[a0 .. a0 + 64) into LDS for the whole workgroup of 256 (k_sg_match, k_sg_near): sketches, header words, a mask of the empty buckets each
+__device__ __forceinline__ void sg_stage_tile(const uint32_t *__restrict__ A, uint32_t nA, uint64_t a0, uint32_t (*a_sk)[64], uint32_t (*a_head)[6],
+                                              unsigned long long *a_empty) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    __syncthreads();                                // the tile before is read to its end
+    const uint32_t n_in = (uint32_t)std::min<uint64_t>(SG_TILE_A, nA - a0);
+    for (uint32_t w = threadIdx.x; w < SG_TILE_A * FD_SIG_WORDS; w += 256u) {
+        const uint32_t i = w / FD_SIG_WORDS, f = w % FD_SIG_WORDS;
+        const uint32_t x = i < n_in ? A[a0 * FD_SIG_WORDS + w] : (f == 0 ? 0u : FD_SIG_EMPTY);      // beyond the table: n = 0, never reported
+        if (f < 6) a_head[i][f] = x; else a_sk[i][f - 6] = x;
+    }
+    __syncthreads();
+    for (uint32_t i = wv * 16u; i < wv * 16u + 16u; ++i) {      // the empty masks, a wavefront per 16 signatures
+        const unsigned long long em = __ballot(a_sk[i][lane] == FD_SIG_EMPTY);
+        if (lane == 0) a_empty[i] = em;
+    }
+    __syncthreads();
+}
+
 struct sg_match_args { const uint32_t *A; const uint32_t *B; uint32_t nA, nB, thr64, self; fd_sig_pair *pairs; unsigned long long *cursor; unsigned long long max_pairs; };
 
 __global__ __launch_bounds__(256) void k_sg_match(sg_match_args P) {
     __shared__ uint32_t a_sk[SG_TILE_A][64];
     __shared__ uint32_t a_head[SG_TILE_A][6];
     __shared__ unsigned long long a_empty[SG_TILE_A];
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
     const uint64_t j = (uint64_t)blockIdx.x * SG_BLOCK_B + threadIdx.x;      // the lane's signature of B
     const bool have = j < P.nB;
     uint32_t b[64];
@@ -145,19 +173,7 @@ __global__ __launch_bounds__(256) void k_sg_match(sg_match_args P) {
     for (uint32_t ta = blockIdx.y; ta < tiles; ta += gridDim.y) {
         const uint64_t a0 = (uint64_t)ta * SG_TILE_A;
         if (P.self && a0 >= b_last) continue;           // no a < b in this tile (the same for the whole workgroup)
-        __syncthreads();                                // the tile before is read to its end
-        const uint32_t n_in = (uint32_t)std::min<uint64_t>(SG_TILE_A, P.nA - a0);
-        for (uint32_t w = threadIdx.x; w < SG_TILE_A * FD_SIG_WORDS; w += 256u) {
-            const uint32_t i = w / FD_SIG_WORDS, f = w % FD_SIG_WORDS;
-            const uint32_t x = i < n_in ? P.A[a0 * FD_SIG_WORDS + w] : (f == 0 ? 0u : FD_SIG_EMPTY);      // beyond the table: n = 0, never reported
-            if (f < 6) a_head[i][f] = x; else a_sk[i][f - 6] = x;
-        }
-        __syncthreads();
-        for (uint32_t i = wv * 16u; i < wv * 16u + 16u; ++i) {      // the empty masks, a wavefront per 16 signatures
-            const unsigned long long em = __ballot(a_sk[i][lane] == FD_SIG_EMPTY);
-            if (lane == 0) a_empty[i] = em;
-        }
-        __syncthreads();
+        sg_stage_tile(P.A, P.nA, a0, a_sk, a_head, a_empty);
         for (uint32_t i = 0; i < SG_TILE_A; ++i) {
             uint32_t eq = 0;
 #pragma unroll
@@ -246,4 +262,179 @@ extern "C" int fdgpu_signature_pairs(fdgpu_ctx *c, const fd_signature *A, uint64
     const int rc = pairs_impl(c, A, nA, B, nB, thr64, max_pairs, pairs, n_pairs);
     if (rc != FDGPU_OK) (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+// ---- neighbours.  Grid as k_sg_match: x = workgroups of 256 queries (one per lane), y = the tiles of D a workgroup takes in turn.  Reads
+// Q[0 .. nQ), D[0 .. nD), excl[0 .. nQ) if given; writes out[(blockIdx.y * nQ + q) * k + 0 .. k) for its queries q < nQ: the lane's k nearest among
+// the tiles it saw, nearest first, empty slots behind them.  Dynamic LDS: k * 1536 bytes, the lists as [slot][lane]: a word for the id and a
+// halfword for match | filled << 7 | identical << 14 (six bytes a slot: k = 32 leaves room for two workgroups per CU), the lanes of a wavefront
+// on different banks whatever slot each of them is at.
+struct sg_near_args { const uint32_t *Q; const uint32_t *D; const uint32_t *excl; uint32_t nQ, nD, thr64, self, k; uint2 *out; };
+#define SG_NB_LDS_PER_K (SG_BLOCK_B * 6u)
+
+// y as the second word of a fd_sig_neighbor: match | filled << 8 | flags << 16
+__device__ __forceinline__ bool sg_nearer_packed(uint32_t m, uint32_t f, uint32_t id, uint32_t mf, uint32_t id_y) {
+    return fd_sig_nearer(m, f, id, mf & 0xffu, (mf >> 8) & 0xffu, id_y);
+}
+__device__ __forceinline__ uint32_t sg_mf_word(uint32_t h) { return (h & 0x7fu) | ((h >> 7) & 0x7fu) << 8 | (h >> 14) << 16; }      // the LDS halfword -> that word
+
+__global__ __launch_bounds__(256) void k_sg_near(sg_near_args P) {
+    __shared__ uint32_t a_sk[SG_TILE_A][64];
+    __shared__ uint32_t a_head[SG_TILE_A][6];
+    __shared__ unsigned long long a_empty[SG_TILE_A];
+    extern __shared__ uint32_t nb_lds[];
+    const uint32_t t = threadIdx.x, K = P.k;
+    uint32_t *nb_id = nb_lds + t;                                             // slot s at [s * 256]
+    uint16_t *nb_mf = reinterpret_cast<uint16_t *>(nb_lds + K * SG_BLOCK_B) + t;
+    const uint64_t j = (uint64_t)blockIdx.x * SG_BLOCK_B + t;                 // the lane's query
+    const bool have = j < P.nQ;
+    uint32_t b[64];
+    uint32_t bn = 0, bd0l = 0, bd0h = 0, bd1l = 0, bd1h = 0;
+    unsigned long long b_empty = 0;
+    {
+        const uint32_t *pb = P.Q + (have ? j : 0) * FD_SIG_WORDS;
+        if (have) { bn = pb[0]; bd0l = pb[2]; bd0h = pb[3]; bd1l = pb[4]; bd1h = pb[5]; }
+#pragma unroll
+        for (uint32_t k = 0; k < 64; ++k) {
+            b[k] = have ? pb[6 + k] : FD_SIG_EMPTY;
+            b_empty |= (unsigned long long)(b[k] == FD_SIG_EMPTY ? 1u : 0u) << k;
+        }
+    }
+    const uint32_t skip = P.self ? (uint32_t)j : (P.excl && have ? P.excl[j] : FD_SIG_NO_ID);
+    for (uint32_t s = 0; s < K; ++s) { nb_id[s * SG_BLOCK_B] = FD_SIG_NO_ID; nb_mf[s * SG_BLOCK_B] = 0u; }
+    uint32_t kth_id = FD_SIG_NO_ID, kth_mf = 0u;       // the list's last slot: what a candidate has to beat
+    const uint32_t tiles = (P.nD + SG_TILE_A - 1) / SG_TILE_A;
+    for (uint32_t ta = blockIdx.y; ta < tiles; ta += gridDim.y) {
+        const uint64_t a0 = (uint64_t)ta * SG_TILE_A;
+        sg_stage_tile(P.D, P.nD, a0, a_sk, a_head, a_empty);
+        for (uint32_t i = 0; i < SG_TILE_A; ++i) {
+            uint32_t eq = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 64; ++k) eq += a_sk[i][k] == b[k] ? 1u : 0u;
+            const uint32_t E = (uint32_t)__popcll(a_empty[i] & b_empty);
+            const uint32_t a = (uint32_t)(a0 + i), m = eq - E, f = 64u - E;
+            // a lane without a query and a slot beyond the table have n = 0: never a candidate
+            if (fd_sig_reported(bn, a_head[i][0], eq, E, P.thr64) && a != skip && sg_nearer_packed(m, f, a, kth_mf, kth_id)) {
+                const bool same = a_head[i][0] == bn && a_head[i][2] == bd0l && a_head[i][3] == bd0h && a_head[i][4] == bd1l && a_head[i][5] == bd1h;
+                uint32_t lo = 0, hi = K - 1;           // its slot: the first one it is nearer than (the last one at the latest), by bisection
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (sg_nearer_packed(m, f, a, sg_mf_word(nb_mf[mid * SG_BLOCK_B]), nb_id[mid * SG_BLOCK_B])) hi = mid; else lo = mid + 1;
+                }
+                uint32_t s = K - 1;                    // the slots from there on move down by one, the last one leaves
+                for (; s > lo; --s) { nb_id[s * SG_BLOCK_B] = nb_id[(s - 1u) * SG_BLOCK_B]; nb_mf[s * SG_BLOCK_B] = nb_mf[(s - 1u) * SG_BLOCK_B]; }
+                nb_id[lo * SG_BLOCK_B] = a; nb_mf[lo * SG_BLOCK_B] = (uint16_t)(m | f << 7 | (same ? 1u : 0u) << 14);
+                kth_id = nb_id[(K - 1) * SG_BLOCK_B]; kth_mf = sg_mf_word(nb_mf[(K - 1) * SG_BLOCK_B]);
+            }
+        }
+    }
+    if (have) {
+        uint2 *row = P.out + ((uint64_t)blockIdx.y * P.nQ + j) * K;
+        for (uint32_t s = 0; s < K; ++s) row[s] = make_uint2(nb_id[s * SG_BLOCK_B], sg_mf_word(nb_mf[s * SG_BLOCK_B]));
+    }
+}
+
+// ---- merge: a wavefront per query q < nQ; lane l < gy owns the sorted partial list part[(l * nQ + q) * k + 0 .. k) and keeps its head in
+// registers; k times the wavefront takes the nearest head (a butterfly under fd_sig_nearer: the lists hold different candidates, so the order is
+// strict until only empty slots are left) and the lane it came from steps on.  Writes out[q * k + 0 .. k).  A wavefront and not a thread per
+// query: the merge runs when there are few queries and many splits, where a thread per query would leave the device idle and walk gy * k
+// records one after the other.
+__global__ __launch_bounds__(256) void k_sg_near_merge(const uint2 *__restrict__ part, uint32_t gy, uint32_t nQ, uint32_t k, uint2 *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t q = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (q >= nQ) return;
+    const uint2 none = make_uint2(FD_SIG_NO_ID, 0u);
+    const uint2 *src = part + ((uint64_t)(lane < gy ? lane : 0u) * nQ + q) * k;
+    uint32_t pos = 0;
+    uint2 head = lane < gy ? src[0] : none;
+    for (uint32_t r = 0; r < k; ++r) {
+        uint32_t bid = head.x, bmf = head.y, bsrc = lane;
+        for (int o = FD_WAVE / 2; o > 0; o >>= 1) {
+            const uint32_t oid = __shfl_xor(bid, o, FD_WAVE), omf = __shfl_xor(bmf, o, FD_WAVE), osrc = __shfl_xor(bsrc, o, FD_WAVE);
+            if (sg_nearer_packed(omf & 0xffu, (omf >> 8) & 0xffu, oid, bmf, bid)) { bid = oid; bmf = omf; bsrc = osrc; }
+        }
+        if (lane == 0) out[q * k + r] = make_uint2(bid, bmf);
+        if (bsrc == lane && bid != FD_SIG_NO_ID) { ++pos; head = pos < k ? src[pos] : none; }
+    }
+}
+
+#define SG_NB_MAX_SPLIT 64u      // lists a merging wavefront takes, one per lane; bounds WS_SG_NB_PART at 64 * nQ * k * 8 bytes
+
+static int neighbors_impl(fdgpu_ctx *c, const fd_signature *Q, uint64_t nQ, const fd_signature *D, uint64_t nD, const uint32_t *exclude, uint32_t k,
+                          uint32_t thr64, fd_sig_neighbor **out) {
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    const bool self = D == nullptr;
+    if (self) nD = nQ;
+    const uint64_t n_rec = nQ * k;
+    fd_sig_neighbor *res = (fd_sig_neighbor *)fd_out_alloc(std::max<uint64_t>(n_rec, 1) * sizeof(fd_sig_neighbor));
+    if (!res) FAIL(c, FDGPU_ENOMEM, "signature neighbors: out of host memory");
+    const fd_sig_neighbor none = {FD_SIG_NO_ID, 0, 0, 0};
+    if (!nQ || !nD) {                                   // nothing to compare: every slot is empty
+        for (uint64_t i = 0; i < std::max<uint64_t>(n_rec, 1); ++i) res[i] = none;
+        *out = res;
+        return FDGPU_OK;
+    }
+    const uint32_t blocks_q = fd_grid(nQ, SG_BLOCK_B), tiles = fd_grid(nD, SG_TILE_A), most = std::min<uint32_t>(tiles, SG_NB_MAX_SPLIT);
+    // as pairs_impl: enough workgroups to fill the device, no more splits than tiles; FDGPU_SG_NB_SPLIT (tests) moves the boundary
+    uint32_t gy = std::max<uint32_t>(1u, std::min<uint32_t>(most, fd_grid(4096, blocks_q)));
+    if (const char *e = getenv("FDGPU_SG_NB_SPLIT")) {
+        const long long v = atoll(e);
+        if (v > 0) gy = (uint32_t)std::min<long long>(v, most);
+    }
+    const size_t lds = (size_t)k * SG_NB_LDS_PER_K;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = c->ws[WS_SG_TAB].ensure(nD * sizeof(fd_signature))) != hipSuccess) break;
+        if (!self && (e = c->ws[WS_SG_TAB_B].ensure(nQ * sizeof(fd_signature))) != hipSuccess) break;
+        if (exclude && (e = c->ws[WS_MISC0].ensure(nQ * 4)) != hipSuccess) break;
+        if ((e = c->ws[WS_SG_NB_OUT].ensure(n_rec * sizeof(fd_sig_neighbor))) != hipSuccess) break;
+        if (gy > 1 && (e = c->ws[WS_SG_NB_PART].ensure((uint64_t)gy * n_rec * sizeof(fd_sig_neighbor))) != hipSuccess) break;
+        uint32_t *dD = c->ws[WS_SG_TAB].as<uint32_t>(), *dQ = self ? dD : c->ws[WS_SG_TAB_B].as<uint32_t>();
+        uint32_t *dX = exclude ? c->ws[WS_MISC0].as<uint32_t>() : nullptr;
+        uint2 *d_out = c->ws[WS_SG_NB_OUT].as<uint2>(), *d_part = gy > 1 ? c->ws[WS_SG_NB_PART].as<uint2>() : d_out;
+        {
+            StageTimer t(c, "signb_upload", (nQ + (self ? 0 : nD)) * sizeof(fd_signature) + (exclude ? nQ * 4 : 0));
+            if ((e = hipMemcpyAsync(dD, self ? Q : D, nD * sizeof(fd_signature), hipMemcpyHostToDevice, st)) != hipSuccess) break;
+            if (!self && (e = hipMemcpyAsync(dQ, Q, nQ * sizeof(fd_signature), hipMemcpyHostToDevice, st)) != hipSuccess) break;
+            if (exclude && (e = hipMemcpyAsync(dX, exclude, nQ * 4, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        }
+        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sg_near), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) break;
+        {
+            StageTimer t(c, "signb_scan", (uint64_t)blocks_q * ((uint64_t)SG_BLOCK_B + (uint64_t)(tiles / gy + 1) * SG_TILE_A) * gy * sizeof(fd_signature));
+            const sg_near_args P{dQ, dD, dX, (uint32_t)nQ, (uint32_t)nD, thr64, self ? 1u : 0u, k, d_part};
+            hipLaunchKernelGGL(k_sg_near, dim3(blocks_q, gy), dim3(256), lds, st, P);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if (gy > 1) {
+            StageTimer t(c, "signb_merge", ((uint64_t)gy + 1) * n_rec * sizeof(fd_sig_neighbor));
+            hipLaunchKernelGGL(k_sg_near_merge, dim3(fd_grid(nQ, 4)), dim3(256), 0, st, d_part, gy, (uint32_t)nQ, k, d_out);
+            if ((e = hipGetLastError()) != hipSuccess) break;
+        }
+        {
+            StageTimer t(c, "signb_copy", n_rec * sizeof(fd_sig_neighbor));
+            e = fd_d2h_big(c, res, d_out, n_rec * sizeof(fd_sig_neighbor));
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    } while (false);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);                 // nothing of a failed call still writes into the block
+        fdgpu_free(res);
+        c->err = std::string("signature neighbors: ") + hipGetErrorString(e);
+        return FDGPU_EHIP;
+    }
+    *out = res;
+    return FDGPU_OK;
+}
+
+extern "C" int fdgpu_signature_neighbors(fdgpu_ctx *c, const fd_signature *Q, uint64_t nQ, const fd_signature *D, uint64_t nD, const uint32_t *exclude, uint32_t k,
+                                         uint32_t thr64, fd_sig_neighbor **out) { FD_LOCK(c);
+    if (!c || !out) return FDGPU_EINVAL;
+    *out = nullptr;
+    if (k < 1 || k > FD_SIG_MAX_K) FAIL(c, FDGPU_EINVAL, "signature neighbors: k must be 1 .. 32");
+    if (thr64 < 1 || thr64 > 64) FAIL(c, FDGPU_EINVAL, "signature neighbors: thr64 must be 1 .. 64");
+    if (nQ > 0xffffffffull || (D && nD > 0xffffffffull)) FAIL(c, FDGPU_EINVAL, "signature neighbors: a table of 2^32 or more signatures");
+    if (!D && exclude) FAIL(c, FDGPU_EINVAL, "signature neighbors: exclude is implied in self mode (D == NULL); pass none");
+    if (nQ && !Q) FAIL(c, FDGPU_EINVAL, "signature neighbors: table Q is NULL");
+    return neighbors_impl(c, Q, nQ, D, nD, exclude, k, thr64, out);
 }

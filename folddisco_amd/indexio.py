@@ -562,6 +562,80 @@ def signature_pairs_host(A, B=None, min_similarity: float = 0.9, max_pairs: int 
     return signature_pairs_result(L, pp, int(n.value))
 
 
+# ---- signature neighbours (include/fdgpu.h: fd_sig_neighbor)
+SIGNATURE_NEIGHBOR_DTYPE = np.dtype([("id", "<u4"), ("match", "u1"), ("filled", "u1"), ("flags", "<u2")])      # 8 bytes; an empty slot: id = SIG_NO_ID, zeros
+SIG_NO_ID = 0xffffffff
+SIG_MAX_K = 32
+assert SIGNATURE_NEIGHBOR_DTYPE.itemsize == 8
+
+
+def signature_neighbors_from_tables(Q, D=None, k: int = 8, thr64: int = 1, exclude=None) -> np.ndarray:
+    """THE SPECIFICATION of the signature neighbours, in plain numpy: -> (len(Q), k) SIGNATURE_NEIGHBOR_DTYPE records.  d of D is a candidate of
+    q of Q iff both rows are non-empty, filled > 0 and match * 64 >= thr64 * filled (match = agreeing buckets that are not empty in both,
+    filled = 64 - buckets empty in both) and d != exclude[q] (D = None: D is Q and exclude[q] = q).  Row q holds q's candidates by descending
+    match / filled, then descending filled, then ascending id, cut at k; the slots behind them are empty (id = SIG_NO_ID, zeros).  flags bit 0:
+    n, d0 and d1 agree.  The device form (Context.signature_neighbors) and the host form (signature_neighbors_host) agree with it bit for bit"""
+    Q = _sig_table(Q, "Q")
+    self_mode = D is None
+    D = Q if self_mode else _sig_table(D, "D")
+    skip = np.arange(len(Q), dtype=np.int64) if self_mode else np.full(len(Q), SIG_NO_ID, np.int64) if exclude is None else np.asarray(exclude).astype(np.int64)
+    out = np.zeros((len(Q), int(k)), SIGNATURE_NEIGHBOR_DTYPE)
+    out["id"] = SIG_NO_ID
+    d_empty, ids = D["sk"] == SIG_EMPTY, np.arange(len(D), dtype=np.int64)
+    for q0 in range(0, len(Q), 128):                 # blocks of queries: 128 x len(D) x 64 booleans at a time
+        q = Q[q0:q0 + 128]
+        eq = (q["sk"][:, None, :] == D["sk"][None, :, :]).sum(-1)
+        E = ((q["sk"] == SIG_EMPTY)[:, None, :] & d_empty[None, :, :]).sum(-1)
+        match, filled = eq - E, 64 - E
+        ok = (q["n"] > 0)[:, None] & (D["n"] > 0)[None, :] & (filled > 0) & (match * 64 >= int(thr64) * filled) & (ids[None, :] != skip[q0:q0 + 128, None])
+        ratio = (match << 20) // np.maximum(filled, 1)      # distinct fractions with denominators <= 64 -> distinct integers, equal -> equal
+        for r in range(len(q)):
+            c = np.nonzero(ok[r])[0]
+            c = c[np.lexsort((c, -filled[r, c], -ratio[r, c]))][:int(k)]
+            row = out[q0 + r]
+            row["id"][:len(c)], row["match"][:len(c)], row["filled"][:len(c)] = c, match[r, c], filled[r, c]
+            row["flags"][:len(c)] = (D["n"][c] == q["n"][r]) & (D["d0"][c] == q["d0"][r]) & (D["d1"][c] == q["d1"][r])
+    return out
+
+
+def _sig_neighbor_args(Q, D, k, min_similarity, thr64, exclude):
+    Q = _sig_table(Q, "Q")
+    D = None if D is None else _sig_table(D, "D")
+    t = int(thr64) if min_similarity is None else signature_threshold(min_similarity)
+    if not (0 <= int(k) <= 0xffffffff and 0 <= t <= 0xffffffff):
+        raise ValueError("signature neighbors: k must be 1 .. 32 and thr64 1 .. 64")
+    if exclude is not None:
+        exclude = np.ascontiguousarray(exclude, dtype=np.uint32)
+        if exclude.shape != (len(Q),):
+            raise ValueError(f"signature neighbors: exclude needs one position per query ({len(Q)}), got shape {exclude.shape}")
+    return Q, D, int(k), t, exclude
+
+
+def signature_neighbors_result(L, op, nQ: int, k: int) -> np.ndarray:
+    """the library's neighbour records as a (nQ, k) array; releases the block"""
+    if not nQ:
+        if op:
+            L.fdgpu_free(op)
+        return np.zeros((0, k), SIGNATURE_NEIGHBOR_DTYPE)
+    return _lib.owned_view(L, op, nQ * k * SIGNATURE_NEIGHBOR_DTYPE.itemsize, np.uint8).view(SIGNATURE_NEIGHBOR_DTYPE).reshape(nQ, k)
+
+
+def signature_neighbors_host(Q, D=None, k: int = 8, min_similarity=None, thr64: int = 1, exclude=None, threads: int = 1) -> np.ndarray:
+    """the k nearest signatures of D for every signature of Q on the CPU (fdgpu_signature_neighbors_host: no context, no device): a (len(Q), k)
+    array of SIGNATURE_NEIGHBOR_DTYPE, see signature_neighbors_from_tables.  D = None: inside Q, a signature is never its own neighbour.  The
+    floor a neighbour must reach is thr64 / 64, or signature_threshold(min_similarity) if that is given.  The result does not depend on
+    `threads`.  Raises ValueError for k outside 1 .. 32, thr64 outside 1 .. 64 and exclude together with D = None"""
+    Q, D, k, t, exclude = _sig_neighbor_args(Q, D, k, min_similarity, thr64, exclude)
+    L = _lib.load()
+    op = C.c_void_p()
+    rc = L.fdgpu_signature_neighbors_host(Q.ctypes.data, len(Q), None if D is None else D.ctypes.data, 0 if D is None else len(D),
+                                          None if exclude is None else exclude.ctypes.data, k, t, max(int(threads), 1), C.byref(op))
+    if rc != 0:
+        raise ValueError(f"signature neighbors: fdgpu_signature_neighbors_host failed ({rc}): k must be 1 .. 32, thr64 1 .. 64, a table holds fewer "
+                         "than 2^32 signatures and exclude is not given in self mode")
+    return signature_neighbors_result(L, op, len(Q), k)
+
+
 def permute_lookup_rows(rows, new_id, keep_db_keys: bool):
     """the rows of PREFIX.lookup after a reorder: row k moves to position new_id[k], tid, nres and plddt verbatim, the id renumbered 0 .. n - 1; the
     db_key column renumbered with it for a file-built index (there it equals the id) and kept for a Foldcomp-built one (its database key) -- the

@@ -641,6 +641,34 @@ int fdgpu_signature_pairs(fdgpu_ctx *ctx, const fd_signature *A, uint64_t nA, co
 int fdgpu_signature_pairs_host(const fd_signature *A, uint64_t nA, const fd_signature *B, uint64_t nB, uint32_t thr64, uint64_t max_pairs,
                                uint32_t n_threads, fd_sig_pair **pairs, uint64_t *n_pairs);
 
+/* ---- signature neighbours: for every signature q of a table Q its k nearest among the signatures d of a table D.
+ * With eq, E, match = eq - E and filled = 64 - E as for fd_sig_pair:
+ *   candidate  d is a candidate of q iff the pair would be reported at thr64 (q.n > 0 && d.n > 0 && filled > 0 && match * 64 >= thr64 * filled;
+ *              thr64 = 1: at least one agreeing filled bucket) and d is not excluded for q.
+ *   exclusion  exclude[nQ] (optional) names one position of D per query that is never its neighbour, 0xFFFFFFFF = none.  D == NULL is self
+ *              mode: the candidates are Q itself, exclude[q] = q is implied and a passed array is refused.  Both directions are produced:
+ *              every signature gets its own list.
+ *   order      x is nearer to q than y iff match_x * filled_y > match_y * filled_x, or these are equal and filled_x > filled_y (more buckets of
+ *              evidence), or those are equal too and id_x < id_y (csrc/fd_signature.h: fd_sig_nearer).  Integers only and a total order: the
+ *              result is unique and does not depend on the order in which the candidates are met.  The identical flag does not enter the order.
+ *   result     nQ x k records, row q = q's nearest candidates in that order; id is a position in D (in Q in self mode), flags bit 0
+ *              FD_SIG_IDENTICAL as in fd_sig_pair.  A slot beyond q's number of candidates holds id = 0xFFFFFFFF and zeros elsewhere; a query
+ *              with n == 0 has only such slots.  8 bytes. */
+typedef struct fd_sig_neighbor { uint32_t id; uint8_t match, filled; uint16_t flags; } fd_sig_neighbor;
+#define FD_SIG_MAX_K 32u
+/* The neighbours on the device (csrc/k_sig.hip: k_sg_near, one query per lane with its k-list in LDS, k_sg_near_merge when the candidates were
+ * split over several workgroups).  Q and D are host tables; *out holds max(nQ * k, 1) records, released with fdgpu_free, byte-identical from
+ * run to run and for every split.  FDGPU_EINVAL with a message opening "signature neighbors:", before any device work and with *out NULL:
+ * k outside 1 .. FD_SIG_MAX_K, thr64 outside 1 .. 64, a table of 2^32 or more signatures, exclude together with D == NULL, a NULL table with a
+ * non-zero count.  nQ == 0: an empty result; nD == 0: rows of empty slots.  Workspace: 280 bytes per signature, 8 * k per query and per
+ * split.  Test switch, read per call: FDGPU_SG_NB_SPLIT=n sets the number of splits (clamped to 1 .. min(tiles of 64 candidates, 64)). */
+int fdgpu_signature_neighbors(fdgpu_ctx *ctx, const fd_signature *Q, uint64_t nQ, const fd_signature *D, uint64_t nD, const uint32_t *exclude,
+                              uint32_t k, uint32_t thr64, fd_sig_neighbor **out);
+/* The same neighbours on the CPU: blocks of 64 queries against blocks of 64 candidates, n_threads host threads over the query blocks (0 = 1),
+ * every query inserting into its own k-list; the result does not depend on n_threads.  No device.  The same refusals (code only). */
+int fdgpu_signature_neighbors_host(const fd_signature *Q, uint64_t nQ, const fd_signature *D, uint64_t nD, const uint32_t *exclude, uint32_t k,
+                                   uint32_t thr64, uint32_t n_threads, fd_sig_neighbor **out);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
