@@ -10,6 +10,7 @@
 #include "../../include/fdgpu_debug.h"
 #include "fd_device.h"
 #include "fd_geom_other.h"
+#include "fd_retrieve_host.h"
 
 #include <condition_variable>
 #include <thread>
@@ -506,7 +507,6 @@ struct fd_mp_tables {
 void fd_launch_mp_items(const uint32_t *db_res_off, const uint32_t *cand, uint32_t n_cand, const uint32_t *wbase, const uint32_t *cq, uint32_t j_span, uint32_t *wc,
                         uint32_t *wi, uint32_t *wq, uint32_t *wj, hipStream_t st, const uint8_t *aa, const uint8_t *hash_ok, const uint8_t *resname_std, int tert,
                         const struct mp_query_dev *qtab, void *cinfo /* uint4 [n_cand] or null */, uint32_t *act /* [64 x items] */);
-struct fd_vote_row { uint32_t mx, nmx, arg; };
 struct fd_vote_plan {
     const uint8_t *cj_comp; uint64_t n_bits;
     const uint64_t *vt_off; const uint32_t *vt_qs; uint64_t n_counters;

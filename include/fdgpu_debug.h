@@ -44,6 +44,19 @@ int fdgpu_debug_encode_stream(fdgpu_ctx *ctx, const uint32_t *hashes, const uint
 int fdgpu_debug_host_components(const uint32_t *edge_i, const uint32_t *edge_j, uint64_t n_edges, uint32_t node_count, uint32_t **residues,
                                 uint64_t **comp_off, uint64_t *n_comps);
 int fdgpu_debug_hash_is_symmetric(uint32_t hash_type, const uint32_t *hashes, uint64_t n, uint8_t *out);
+/* fdgpu_debug_host_retrieve_slot: what the host path of fdgpu_retrieve_batch computes on its threads for ONE candidate slot (csrc/fd_retrieve_host.cpp:
+ * graph -> components -> votes -> assignment -> rescue -> residue lists), from a pair scan's output given as arrays: the slot's found triples
+ * (found_i, found_j, found_hash)[n_found] in scan order (residues below n_target, else FDGPU_EINVAL) and its candidate pairs (cand_qi, cand_i,
+ * cand_j)[n_pairs] (out-of-range fields are ignored like the glue ignores them), the target's residue count, the query map, hash_type, node_count.
+ * two_pass != 0: the two-scan form of large queries — the plan pass on the found triples alone, then only the candidate pairs the second scan
+ * returns (partner residue cand_j marked by the plan pass), then the full pass on the cached plans.  packed != 0: the candidate pairs reach the slot
+ * in the scan's packed form (16 bits a field: FDGPU_EINVAL beyond), else as records.  Out: *n_recs records in emission order (component order,
+ * graph.rs:43-45): (*idf)[k], (*same)[k], and (*residues)[k * 2 * n_indices ...] = the from-hash list then the processed list (-1 = none).  No
+ * coordinates, no superposition.  The three arrays are released with libc free(). */
+int fdgpu_debug_host_retrieve_slot(const uint32_t *found_i, const uint32_t *found_j, const uint32_t *found_hash, uint64_t n_found, const uint32_t *cand_qi,
+                                   const uint32_t *cand_i, const uint32_t *cand_j, uint64_t n_pairs, uint32_t n_target, const fd_query_map *qm,
+                                   uint32_t hash_type, uint32_t node_count, uint32_t two_pass, uint32_t packed, uint64_t *n_recs, float **idf,
+                                   uint32_t **same, int32_t **residues);
 
 /* Which form the LAST count call on this context took (fdgpu_count_query, fdgpu_count_query_batch[_top], fdgpu_count_query_maps_top): the
  * booleans its dispatch computed, one bit each, so that a test at one of the dispatch's switches can tell which side it landed on.

@@ -10,12 +10,12 @@ are taken from pairs whose hash occurs once in the structure (Struct.uniq), so t
 same-type pairs at a similar distance add (candidate pairs mostly) is counted by the model, and test_retrieval_cases_host.py checks every claim against
 the oracle's own output.
 
-Fields of fd_query_map the retrieval reads (fd_host_query.hip: fd_rb_prepare, fd_rb_device_glue, fd_retrieve_batch_impl): n, hash, qi, qj, idf, n_indices,
+Fields of fd_query_map the retrieval reads (fd_retrieve_host.cpp: fd_rb_prepare, fd_rh_slot; fd_host_query.hip: rs_pack_tables): n, hash, qi, qj, idf, n_indices,
 indices, n_aad, aad_aa1, aad_aa2, aad_dist, aad_qi.  Nothing else: is_primary is never read there, primary_hash is set to `hash` as make_query_map
 does, post_len / post_seg / post_kidx stay NULL and post_index_uid / arena_bytes 0 (they belong to the scoring stage).  library_map() wraps the struct in
 QueryMapResult(None, pointer): with no context the wrapper never hands the hand-made struct to fdgpu_query_map_free.
 
-Every idf is a multiple of 2^-8 below 1/4: the f32 sum over at most 1,025 edges is exact in any order and is compared bit for bit.
+Every idf is a multiple of 2^-8 below 1/4: the f32 sum over at most 4,097 edges is exact in any order and is compared bit for bit.
 
 Thresholds come from the sources' #defines (RS_* of k_retrieve.hip, MP_* of k_match.hip / fdgpu_internal.h); the ones that are literals in the code are
 restated here: 64 graph nodes / query residues (FD_WAVE), 200 hashes (prefilter), 256 hashes held in LDS by k_rs_setup (2 * RS_S_EDGE), 256 sorted keys of
@@ -36,7 +36,8 @@ Case classes (CLASSES; `claims` states as data what a case exists for, `path` wh
           residues in descending order beside an asymmetric one; duplicates in `indices` (the erase-and-reinsert branch, with the erased position
           equal to and different from the first occurrence); 64 / 65 distinct query residues with a vote in one component (65 overflows); a pair voted
           more than 255 times (u8 saturation) where the saturation changes the winner — built as a host-path case (161 nodes: the device glue
-          declines), not with multiple_bins.
+          declines), not with multiple_bins; 4096 / 4097 found triples and hashes in one slot (the host glue's dense vote table and its hash ->
+          entry table, fd_retrieve_host.cpp).
   rescue  largest tally 1 (none); a unique 2 (rescue); two residues tied at 2 (none); the unique largest already assigned (none); a residue of
           `indices` without any observed distance; C = 511 / 512 / 513 candidate pairs in the slot (RS_CAND_LDS) and 511 / 512 / 513 candidate pairs whose
           partner the component assigned (RS_S_FILT), each with a rescue that the last candidate pairs of the slot decide; 511 / 512 / 513 voting pairs of
@@ -61,6 +62,8 @@ import oracle
 SEED = 20261018
 CLASSES = ("nodes", "edges", "comps", "votes", "rescue", "sizes", "window", "long")
 WAVE, PREFILTER, SETUP_HASH_LDS, AAD_SORTED, TWO_PASS_AAD = 64, 200, 256, 256, 4096
+HOST_DENSE = 4096          # fd_retrieve_host.cpp: found triples of a slot above which its votes go through a dense table, hashes of a query above which
+                           # they are looked up in a table
 
 
 def _define(fname, name):
@@ -585,6 +588,16 @@ def _votes_cases():
                     have.add(h)
                     b.edge(u, v, qi=qi, qj=qj)
     out.append(Case("saturation", "votes", T2, b.arrays(_fill_indices(T2, [lo, hi], 40)), dict(max_vote=255, sat_winner=True, winner=(lo, lo)), path="overflow"))
+    # the host glue's own switches (fd_retrieve_host.cpp): more than HOST_DENSE found triples in a slot whose q_size x residues table is small -> the dense
+    # (q, r) vote table instead of the hash map; more than HOST_DENSE hashes -> the hash -> entry table instead of bisection.  The first 4096 / 4097 pairs of
+    # the 200-residue structure with a hash of their own, by identity; every edge brings its observed distance, so 4097 is a two-scan call as well
+    pairs = [(i, j) for i in range(T2.n) for j in range(T2.n) if T2.uniq(i, j)]
+    for F in (HOST_DENSE, HOST_DENSE + 1):
+        b = MapBuilder(T2)
+        for i, j in pairs[:F]:
+            b.edge(i, j)
+        out.append(Case("dense%d" % F, "votes", T2, b.arrays(list(range(8))), dict(F=F, hashes=F, n_aad=F, max_nodes=T2.n),
+                        path="overflow" if F <= TWO_PASS_AAD else "host", targets=[T2]))
     return out
 
 

@@ -141,6 +141,8 @@ THRESHOLDS = (          # class, threshold, the quantity read from the oracle's 
     ("sizes", rc.MP_AAD_LDS, lambda c, R, g: len(c.arrays["aad_dist"])),
     ("sizes", rc.TWO_PASS_AAD, lambda c, R, g: len(c.arrays["aad_dist"])),
     ("long", 64 * rc.MP_SCAN_BLOCKS, lambda c, R, g: c.targets[0].n),
+    ("votes", rc.HOST_DENSE, lambda c, R, g: len(R["found"])),          # the host glue's switches (fd_retrieve_host.cpp): dense vote table, hash -> entry table
+    ("votes", rc.HOST_DENSE, lambda c, R, g: len(np.unique(c.arrays["hash"]))),
 )
 
 
