@@ -688,10 +688,10 @@ extern "C" uint64_t fdgpu_index_num_postings(const fdgpu_index *ix) { return ix 
 extern "C" uint64_t fdgpu_index_num_structures(const fdgpu_index *ix) { return ix ? ix->n_structures : 0; }
 
 #define FDGPU_RETRY_WIDE 1000
-// The encoder on a sorted stream of P elements (codec: k_index.hip; S structures; for codec 2 WS_SEGOFF holds the stream's [40][S] table): sizes
+// The encoder on a sorted stream of P elements (codec: k_index.hip; S structures; for codec 2 WS_SEGOFF holds the stream's [40][seg_stride] table): sizes
 // per tile, their three scans, the totals read back, an index of exactly that size, the write pass.  WS_MISC3 was cleared by the caller (words 0-2
 // receive the totals, 3-4 are the build's wide / overflow flags).  Shared by the build and by fdgpu_debug_encode_stream.
-static int encode_sorted_stream(fdgpu_ctx *c, const uint32_t *ks, const void *is, int codec, uint64_t first_id, uint64_t P, uint64_t S, fdgpu_index **out) {
+static int encode_sorted_stream(fdgpu_ctx *c, const uint32_t *ks, const void *is, int codec, uint64_t first_id, uint64_t P, uint64_t S, uint64_t seg_stride, fdgpu_index **out) {
     hipStream_t st = c->stream;
     const bool el6 = codec != 0;
     int rc;
@@ -711,7 +711,7 @@ static int encode_sorted_stream(fdgpu_ctx *c, const uint32_t *ks, const void *is
         HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_H].p, 0, (size_t)(nt + 1) * 4, st));
         HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_P].p, 0, (size_t)(nt + 1) * 4, st));
         fd_launch_enc_sizes(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_B].as<uint32_t>(), c->ws[WS_TILE_H].as<uint32_t>(), c->ws[WS_TILE_P].as<uint32_t>(),
-                            c->ws[WS_SEGOFF].as<uint64_t>(), S, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
+                            c->ws[WS_SEGOFF].as<uint64_t>(), seg_stride, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
         uint64_t *totd = c->ws[WS_MISC3].as<uint64_t>();
         fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_B].as<uint32_t>(), nt_eff, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 0, st);
         fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_H].as<uint32_t>(), nt_eff, c->ws[WS_TILE_HO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 1, st);
@@ -773,10 +773,12 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
         HIPCHK(c, c->ws[WS_CA_PERM].ensure(std::max<uint64_t>(b->n_res, 1) * 12));
         HIPCHK(c, c->ws[WS_OK_PERM].ensure(std::max<uint64_t>(b->n_res, 1)));
         HIPCHK(c, c->ws[WS_AA_PERM].ensure(std::max<uint64_t>(b->n_res, 1)));
-        StageTimer t(c, "frames", b->n_res * (37 + sizeof(fd_frame) + 14));
-        fd_launch_frames_perm(V, c->ws[WS_FRAMES].p, c->ws[WS_CA_PERM].as<float>(), c->ws[WS_OK_PERM].as<uint8_t>(), c->ws[WS_AA_PERM].as<uint8_t>(), C.wide_flag, st);
+        HIPCHK(c, c->ws[WS_SRC_PERM].ensure(std::max<uint64_t>(b->n_res, 1) * 4));
+        StageTimer t(c, "frames", b->n_res * (2 + 14 + 18));      // the permutation alone: types and flags for the totals, then 14 B read and 18 B written per residue
+        fd_launch_frames_perm(V, c->ws[WS_CA_PERM].as<float>(), c->ws[WS_OK_PERM].as<uint8_t>(), c->ws[WS_AA_PERM].as<uint8_t>(), c->ws[WS_SRC_PERM].as<uint32_t>(),
+                              C.wide_flag, st);
         V.ca_xyz = c->ws[WS_CA_PERM].as<float>(); V.hash_ok = c->ws[WS_OK_PERM].as<uint8_t>(); V.aa = c->ws[WS_AA_PERM].as<uint8_t>();
-        V.n_xyz = nullptr; V.cb_xyz = nullptr;      // the pair kernels read frames, not atoms
+        V.n_xyz = nullptr; V.cb_xyz = nullptr;      // the emit reads frames, not atoms; the count pass, which builds the frames, gets the batch's N / CB beside the view
     } else {
         StageTimer t(c, "frames", b->n_res * (37 + sizeof(fd_frame)));
         fd_launch_frames(b->view(), b->n_res, c->ws[WS_FRAMES].p, st);
@@ -798,18 +800,16 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
         }
         HIPCHK(c, hipGetLastError());
         rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &P1);
-    } else if (msd) {      // counts / cursors / offsets are [bucket][structure] tables: their exclusive scan IS the bucket-major layout
-        const uint64_t NS = NB * S;
+    } else if (msd) {      // counts / offsets are [bucket][work item] tables: their exclusive scan IS the bucket-major layout, and every work item's
+        const uint64_t NS = NB * b->n_work;      // slots in it are its own.  The count pass writes every entry: nothing to clear
         HIPCHK(c, c->ws[WS_COUNTS].ensure((NS + 1) * 4));
-        HIPCHK(c, c->ws[WS_CURSOR].ensure((NS + 1) * 4));
         HIPCHK(c, c->ws[WS_SEGOFF].ensure((NS + 2) * 8));
         HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(NS, b->n_res)) * 8 + 64));
         HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_COUNTS].p, 0, (NS + 1) * 4, st));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_CURSOR].p, 0, (NS + 1) * 4, st));
         {
-            StageTimer t(c, "pair_count", b->n_res * 14);
-            fd_launch_pair_count_msd(V, C, c->ws[WS_COUNTS].as<uint32_t>(), st);
+            // per residue: CA, flag and type of the filter (14 B), the source index, N and CB (28 B) and the frame it stores; + the table
+            StageTimer t(c, "pair_count", b->n_res * (14 + 28 + sizeof(fd_frame)) + NS * 4);
+            fd_launch_pair_count_msd(V, C, b->n_xyz, b->cb_xyz, c->ws[WS_SRC_PERM].as<uint32_t>(), c->ws[WS_FRAMES].p, c->ws[WS_COUNTS].as<uint32_t>(), st);
         }
         {
             StageTimer t(c, "segment_scan", NS * 12);
@@ -836,7 +836,7 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
     {
         StageTimer t(c, "pair_emit", b->n_res * 37 + P * (el6 ? 6 : 8));
         if (own) fd_launch_row_emit(b->view(), C, c->ws[WS_MISC1].as<uint64_t>(), ka, p->dist_cutoff, (uint32_t *)ia, (uint32_t)first_id, st);
-        else if (msd) fd_launch_pair_emit_msd(V, c->ws[WS_FRAMES].p, C, c->ws[WS_SEGOFF].as<uint64_t>(), c->ws[WS_CURSOR].as<uint32_t>(), ka, (uint16_t *)ia, st);
+        else if (msd) fd_launch_pair_emit_msd(V, c->ws[WS_FRAMES].p, C, c->ws[WS_SEGOFF].as<uint64_t>(), ka, (uint16_t *)ia, st);
         else for (uint32_t k = 0; k < n_cfg; ++k) {
             fd_hash_consts Ck = fd_make_consts_cfg(p, k);
             Ck.spec_miss = C.spec_miss; Ck.wide_flag = C.wide_flag; Ck.seg_mul = n_cfg; Ck.seg_cfg = k;
@@ -851,13 +851,13 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
         HIPCHK(c, c->ws[WS_GHIST].ensure((size_t)256 * fd_rs_seg_num_tiles(P, NB) * 4));
         HIPCHK(c, c->ws[WS_TOT].ensure(fd_rs_seg_tot_words(P, NB) * 8));
         HIPCHK(c, c->ws[WS_SEG_TAB].ensure(fd_rs_seg_tab_bytes(P, NB)));
-        cur = fd_radix_sort_pairs16_seg(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, c->ws[WS_SEGOFF].as<uint64_t>(), S, NB, digits, 3, c->ws[WS_GHIST].as<uint32_t>(),
+        cur = fd_radix_sort_pairs16_seg(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, c->ws[WS_SEGOFF].as<uint64_t>(), b->n_work, NB, digits, 3, c->ws[WS_GHIST].as<uint32_t>(),
                                         c->ws[WS_TOT].as<uint64_t>(), c->ws[WS_SEG_TAB].p, st, c, c->ws[WS_MISC3].as<unsigned long long>() + 4);
     } else if (ids16) cur = fd_radix_sort_pairs16(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, 32, c->ws[WS_GHIST].as<uint32_t>(), c->ws[WS_TOT].as<uint64_t>(), st, c);
     else cur = sort_pairs(c, ka, (uint32_t *)ia, kb, (uint32_t *)ib, P, 32);   // all 32 bits: unmasked field overflow can set bits 30-31
     const uint32_t *ks = cur ? kb : ka;
     const void *is = cur ? ib : ia;
-    return encode_sorted_stream(c, ks, is, codec, first_id, P, S, out);
+    return encode_sorted_stream(c, ks, is, codec, first_id, P, S, msd ? b->n_work : 0, out);
 }
 
 extern "C" int fdgpu_index_build(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, uint64_t first_id, fdgpu_index **out) { FD_LOCK(c);
@@ -887,7 +887,7 @@ extern "C" int fdgpu_debug_encode_stream(fdgpu_ctx *c, const uint32_t *hashes, c
         HIPCHK(c, hipMemcpyAsync(c->ws[WS_KEYS_A].p, hashes, n * 4, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(c->ws[WS_IDS_A].p, ids, n * 4, hipMemcpyHostToDevice, st));
     }
-    return encode_sorted_stream(c, c->ws[WS_KEYS_A].as<uint32_t>(), c->ws[WS_IDS_A].p, 0, 0, n, S, out);
+    return encode_sorted_stream(c, c->ws[WS_KEYS_A].as<uint32_t>(), c->ws[WS_IDS_A].p, 0, 0, n, S, 0, out);
 }
 
 // A large device-to-host copy into ordinary (pageable) memory.  The runtime's own path stages through one internal buffer and one

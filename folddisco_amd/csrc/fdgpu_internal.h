@@ -93,7 +93,7 @@ enum {
     retrieval runs — no retrieval stage may ensure() or write this buffer (checked there) */, WS_TILE_PO, WS_MISC0, WS_MISC1, WS_MISC2, WS_MISC3, WS_MISC4, WS_MISC5, WS_FRAMES,
     WS_CQ_KIDX, WS_CQ_NSEG, WS_CQ_WSTART, WS_CQ_SEGSUM, WS_CQ_TOPN,
     WS_QT_RANGES, WS_QT_COMPACT, WS_QT_COUNT, WS_QT_AUX, WS_RS_PLAN, WS_RS_REC, WS_RS_RECRES, WS_QT_PARTIAL, WS_QT_SURV, WS_QT_ROWBITS, WS_QT_STREAM, WS_QT_STAB, WS_QT_PIECEP, WS_QT_WIN, WS_QT_HEAD, WS_RS_SPLIT, WS_MP_QSET,
-    WS_CA_PERM, WS_OK_PERM, WS_AA_PERM, WS_SEG_TAB,
+    WS_CA_PERM, WS_OK_PERM, WS_AA_PERM, WS_SRC_PERM /* MSD build: the residue that landed at every position of the amino-acid order */, WS_SEG_TAB,
     WS_RS_TAB, WS_RS_SEG, WS_RS_OUT, WS_RS_RES, WS_RS_KX, WS_RS_KY, WS_RS_KOFF, WS_RS_SOL, WS_RS_CNT, WS_RS_GQ, WS_MP_ACT, WS_MP_Q,
     WS_SG_TAB /* signatures of a window; table A of a compare */, WS_SG_TAB_B, WS_SG_PAIRS, WS_SG_CURSOR,
     WS_SG_NB_PART /* signature neighbours: the k-lists of every split, [split][query][k] */, WS_SG_NB_OUT /* the merged lists, [query][k] */,
@@ -337,9 +337,10 @@ void fd_launch_pair_emit2(const fd_batch_view &B, const void *frames, const fd_h
                           uint32_t *keys, void *ids, bool ids16, uint32_t first_id, hipStream_t st);
 int fd_radix_sort_pairs16(uint32_t *keys_a, uint16_t *vals_a, uint32_t *keys_b, uint16_t *vals_b, uint64_t n, int key_bits, uint32_t *ghist,
                           uint64_t *tot, hipStream_t st, fdgpu_ctx *timing_ctx = nullptr);
-void fd_launch_frames_perm(const fd_batch_view &B, void *frames, float *ca_perm, uint8_t *ok_perm, uint8_t *aa_perm, unsigned long long *wide_flag, hipStream_t st);
-void fd_launch_pair_count_msd(const fd_batch_view &B, const fd_hash_consts &C, uint32_t *counts, hipStream_t st);
-void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const fd_hash_consts &C, const uint64_t *seg_off, uint32_t *cursor, uint32_t *keys,
+void fd_launch_frames_perm(const fd_batch_view &B, float *ca_perm, uint8_t *ok_perm, uint8_t *aa_perm, uint32_t *src_perm, unsigned long long *wide_flag, hipStream_t st);
+void fd_launch_pair_count_msd(const fd_batch_view &B, const fd_hash_consts &C, const float *n_xyz, const float *cb_xyz, const uint32_t *src_perm, void *frames,
+                              uint32_t *counts, hipStream_t st);
+void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const fd_hash_consts &C, const uint64_t *seg_off, uint32_t *keys,
                              uint16_t *ids, hipStream_t st);
 uint32_t fd_rs_seg_num_tiles(uint64_t n, uint32_t n_seg);
 uint64_t fd_rs_seg_tot_words(uint64_t n, uint32_t n_seg);

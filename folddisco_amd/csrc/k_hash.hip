@@ -217,49 +217,77 @@ __global__ __launch_bounds__(FD_WAVE) void k_pair_count2(fd_batch_view B, fd_has
     if (threadIdx.x == 0 && cnt) atomicAdd(&counts[s], cnt);
 }
 
-// Frames in AMINO-ACID ORDER (MSD build): one workgroup per structure sorts its residues by type (counting sort, hashable residues
-// first; the order inside a type does not matter — the order of keys inside a structure's segment is arbitrary anyway) and writes the
-// frames together with permuted copies of what the pair kernels read per residue (CA, hashable flag, type).  A 64-residue tile then
-// holds ~4 residue types instead of ~15, which is what keeps the bucket runs of a drain long (k_pair_emit2<.., MSD>).
-__global__ __launch_bounds__(256) void k_frames_perm(fd_batch_view B, fd_frame *__restrict__ frames, float *__restrict__ ca_perm, uint8_t *__restrict__ ok_perm,
-                                                     uint8_t *__restrict__ aa_perm, unsigned long long *__restrict__ wide_flag) {
-    __shared__ uint32_t cnt[32], cur[32];
-    const uint32_t s = blockIdx.x;
+// AMINO-ACID ORDER (MSD build): one workgroup per structure sorts its residues by type — a stable counting sort, hashable residues first,
+// unhashable and out-of-range types last — and writes permuted copies of what the pair kernels read per residue (CA, hashable flag, type)
+// plus src_perm[p], the residue that lands at p: the count pass builds the frames through it (k_pair_count_msd).  A 64-residue tile then
+// holds ~4 residue types instead of ~15, which is what keeps the bucket runs of a drain long (k_pair_emit2<.., MSD>).  Inside a type the
+// residues keep residue order: a trip of 256 residues is ranked by one ballot per type and wavefront and the wavefronts' counts, not by
+// LDS atomics on the slot counters, so the order — and with it the emitted stream — is the same in every run.
+__global__ __launch_bounds__(256) void k_frames_perm(fd_batch_view B, float *__restrict__ ca_perm, uint8_t *__restrict__ ok_perm, uint8_t *__restrict__ aa_perm,
+                                                     uint32_t *__restrict__ src_perm, unsigned long long *__restrict__ wide_flag) {
+    __shared__ uint32_t cnt[32], cur[32], wcnt[4][32];
+    const uint32_t s = blockIdx.x, lane = threadIdx.x & (FD_WAVE - 1u), wave = threadIdx.x / FD_WAVE;
     const uint32_t r0 = B.res_off[s], r1 = B.res_off[s + 1];
     if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
     __syncthreads();
-    for (uint32_t r = r0 + threadIdx.x; r < r1; r += 256) {
+    for (uint32_t r = r0 + threadIdx.x; r < r1; r += 256) {      // the totals per type: their order does not matter
         const uint32_t a = B.aa[r];
         atomicAdd(&cnt[(B.hash_ok[r] && a < 20u) ? a : 20u], 1u);
     }
     __syncthreads();
     if (threadIdx.x == 0) { uint32_t run = 0; for (int k = 0; k < 21; ++k) { cur[k] = run; run += cnt[k]; } }
     __syncthreads();
-    for (uint32_t r = r0 + threadIdx.x; r < r1; r += 256) {
-        const uint32_t a = B.aa[r];
-        bool ok = B.hash_ok[r] != 0;
-        if (ok && a >= 20u) {      // a residue type outside map_aa_to_u8's 0..19 marked hashable: forty buckets cannot hold it — the build is redone with the
-            ok = false;            // structure-major 8-byte path, which hashes whatever the caller passed (wide_flag)
-            if (wide_flag) atomicOr(wide_flag, 1ull);
+    for (uint32_t rb = r0; rb < r1; rb += 256) {      // workgroup-uniform trips: the barriers inside are reached by every thread
+        const uint32_t r = rb + threadIdx.x;
+        uint32_t a = 0, cls = 21u;      // 21: no residue
+        bool ok = false;
+        if (r < r1) {
+            a = B.aa[r];
+            ok = B.hash_ok[r] != 0;
+            if (ok && a >= 20u) {      // a residue type outside map_aa_to_u8's 0..19 marked hashable: forty buckets cannot hold it — the build is redone with the
+                ok = false;            // structure-major 8-byte path, which hashes whatever the caller passed (wide_flag)
+                if (wide_flag) atomicOr(wide_flag, 1ull);
+            }
+            cls = ok ? a : 20u;
         }
-        const uint32_t p = r0 + atomicAdd(&cur[(ok && a < 20u) ? a : 20u], 1u);
-        fd_frame F;
-        const fd_v3 ca = fd_load3(B.ca_xyz, r);
-        if (ok) F = fd_make_frame(fd_load3(B.n_xyz, r), ca, fd_load3(B.cb_xyz, r));
-        else { F = fd_frame{}; F.ca = ca; }
-        F.pad = __uint_as_float(a);
-        frames[p] = F;
-        ca_perm[3ull * p] = ca.x; ca_perm[3ull * p + 1] = ca.y; ca_perm[3ull * p + 2] = ca.z;
-        ok_perm[p] = ok ? 1 : 0;
-        aa_perm[p] = (uint8_t)a;
+        uint64_t mine = 0;      // the lanes of this wavefront with this lane's type
+        uint32_t wc = 0;        // lane k: residues of type k in this wavefront
+#pragma unroll 1      // unrolled, the 21 masks are all held in scalar registers at once and some are spilled
+        for (uint32_t k = 0; k < 21u; ++k) {
+            const uint64_t m = __ballot(cls == k);
+            if (cls == k) mine = m;
+            if (lane == k) wc = (uint32_t)__popcll(m);
+        }
+        if (lane < 21u) wcnt[wave][lane] = wc;
+        __syncthreads();
+        if (r < r1) {
+            uint32_t p = r0 + cur[cls] + fd_mbcnt(mine);      // the type's first free slot + the residues of the type in front of this one
+            for (uint32_t v = 0; v < wave; ++v) p += wcnt[v][cls];
+            const fd_v3 ca = fd_load3(B.ca_xyz, r);
+            ca_perm[3ull * p] = ca.x; ca_perm[3ull * p + 1] = ca.y; ca_perm[3ull * p + 2] = ca.z;
+            ok_perm[p] = ok ? 1 : 0;
+            aa_perm[p] = (uint8_t)a;
+            src_perm[p] = r;
+        }
+        __syncthreads();
+        if (threadIdx.x < 21u) cur[threadIdx.x] += wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] + wcnt[3][threadIdx.x];
+        __syncthreads();
     }
 }
 
-// count pass of the MSD build: counts[bucket * S + s] += keys of structure s that fall into the bucket (both orientations of every
-// unordered pair: (aa_i, aa_j >> 4) and (aa_j, aa_i >> 4)).  The partners come in runs of one residue type (fd_filter_block; amino-acid order
-// makes them ~16 long), so ONE per-lane pass counter per run serves both orientations: at the end of the run it goes to the lane's forward
-// counter of the run's half (c_lo / c_hi) and, as the reverse keys of bucket (aa_j, aa_i >> 4), into the forty LDS counters.  B = the permuted view.
-__global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_hash_consts C, uint32_t *__restrict__ counts) {
+// count pass of the MSD build: counts[bucket * n_work + w] = keys of work item w that fall into the bucket (both orientations of every
+// unordered pair: (aa_i, aa_j >> 4) and (aa_j, aa_i >> 4)).  Every work item writes all forty of its entries with plain stores, zeros
+// included, so the table needs no clearing and nothing of an earlier call shows; its exclusive scan gives every work item private,
+// contiguous slots in every bucket (work items are in structure order: the stream stays structure-major inside a bucket).  The partners
+// come in runs of one residue type (fd_filter_block; amino-acid order makes them ~16 long), so ONE per-lane pass counter per run serves
+// both orientations: at the end of the run it goes to the lane's forward counter of the run's half (c_lo / c_hi) and, as the reverse keys
+// of bucket (aa_j, aa_i >> 4), into the forty LDS counters.  B = the permuted view.
+// A work item is exactly one 64-residue tile of the permuted order, so every frame belongs to one work item: in front of the filter loop
+// lane l gathers N and CB of the residue that landed at i0 + l (src_perm; n_xyz / cb_xyz are the batch's arrays in chain order), builds
+// the frame and stores it for the emit pass.  The kernel is bound by the filter loop's scalar instructions; the frames ride in its idle
+// vector and memory slots.
+__global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_hash_consts C, const float *__restrict__ n_xyz, const float *__restrict__ cb_xyz,
+                                                            const uint32_t *__restrict__ src_perm, fd_frame *__restrict__ frames, uint32_t *__restrict__ counts) {
     __shared__ uint32_t s_cnt[FD_WAVE];
     __shared__ float s_cj[3 * FD_WAVE + 1];
     uint32_t w = fd_xcd_remap(blockIdx.x, B.n_work);
@@ -273,6 +301,13 @@ __global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_
     fd_v3 cai = {0.f, 0.f, 0.f};
     uint32_t aai = 0;
     if (vi) { cai = fd_load3(B.ca_xyz, i); aai = B.aa[i]; }
+    if (i < r1) {
+        fd_frame F;
+        if (vi) { const uint32_t src = src_perm[i]; F = fd_make_frame(fd_load3(n_xyz, src), cai, fd_load3(cb_xyz, src)); }
+        else { F = fd_frame{}; F.ca = fd_load3(B.ca_xyz, i); }
+        F.pad = __uint_as_float((uint32_t)B.aa[i]);      // the residue type rides in the frame's spare word (bit pattern, never computed with)
+        frames[i] = F;
+    }
     s_cnt[lane] = 0;
     __syncthreads();
     const uint64_t vim = __ballot(vi);
@@ -289,7 +324,7 @@ __global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_
     if (c_lo) atomicAdd(&s_cnt[aai * 2u], c_lo);
     if (c_hi) atomicAdd(&s_cnt[aai * 2u + 1u], c_hi);
     __syncthreads();
-    if (lane < FD_MSD_BUCKETS && s_cnt[lane]) atomicAdd(&counts[(uint64_t)lane * B.n_struct + s], s_cnt[lane]);
+    if (lane < FD_MSD_BUCKETS) counts[(uint64_t)lane * B.n_work + w] = s_cnt[lane];
 }
 
 __device__ __forceinline__ fd_frame load_frame(const fd_frame *__restrict__ frames, uint32_t r) {
@@ -322,23 +357,25 @@ __device__ __attribute__((noinline)) uint2 pair_both_tab_exact(const fd_frame *_
 
 // MSD (index build, 6-byte elements, default encoding): the keys leave the kernel already partitioned by the top six hash bits — bucket =
 // hash >> 24 = aa_i << 1 | aa_j >> 4, forty of them — into a BUCKET-major stream (inside a bucket structure-major, so the stable sort that
-// follows still leaves ids ascending inside every hash).  seg_off / cursor are then [bucket][structure] tables; a drain counts its keys
-// per bucket in LDS (two ds_add_rtn per lane), claims the slots with one global atomic per touched bucket and stores every key at its
-// own position.  The residues of a structure are visited in amino-acid order (k_frames_perm), so a drain touches a handful of buckets and
-// the partial lines of one bucket's run are completed in L2 by the drains that follow.  The sort then needs three 8-bit passes, not four.
+// follows still leaves ids ascending inside every hash).  seg_off is then a [bucket][work item] table (k_pair_count_msd): a work item owns
+// private, contiguous slots in every bucket, and their forty starts are its running cursor in LDS (s_boff).  A drain counts its keys per
+// bucket in LDS (two ds_add_rtn per lane), stores every key at cursor + its rank inside the drain and advances the cursor by the counts:
+// no global atomic, no memory shared with another workgroup.  The residues of a structure are visited in amino-acid order
+// (k_frames_perm), so a drain touches a handful of buckets and the partial lines of one bucket's run are completed in L2 by the drains
+// that follow.  The sort then needs three 8-bit passes, not four.
 template <int TAB, bool IDS16, bool MSD, bool DT = false>
 __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *__restrict__ frames, const fd_hash_consts &C,
                                        const uint32_t *tab, const uint32_t *q, uint32_t n, uint32_t i0, uint32_t r0, uint32_t s, uint32_t id,
                                        const uint64_t *seg_off, uint32_t *cursor, uint32_t *keys, void *ids, const float4 *s_fi,
-                                       uint32_t *s_bc, uint64_t *s_bb, const uint64_t *s_boff) {
+                                       uint32_t *s_bc, uint64_t *s_boff) {
     const uint32_t lane = threadIdx.x;
-    uint32_t base = 0, gb = 0, slots = 0;
+    uint32_t base = 0, slots = 0;
     if (!MSD) {
         if (lane == 0) base = atomicAdd(&cursor[s], 2u * n);
         base = __shfl(base, 0, FD_WAVE);
     } else {
         // the buckets of a drain's keys are known before any geometry (the queue entry carries the partner's residue type): count per
-        // bucket in LDS, claim the slots with one global atomic per touched bucket — its latency then hides behind the descriptor
+        // bucket in LDS; a lane's two results are its keys' ranks inside the drain
         s_bc[lane] = 0;
         fd_wave_lds_fence();
         if (lane < n) {
@@ -347,8 +384,6 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
             const uint32_t bf = ai * 2u + (aj >> 4), br = aj * 2u + (ai >> 4);
             slots = atomicAdd(&s_bc[bf], 1u) | atomicAdd(&s_bc[br], 1u) << 8 | bf << 16 | br << 24;      // one register across the descriptor
         }
-        fd_wave_lds_fence();
-        if (lane < FD_MSD_BUCKETS) { const uint32_t c = s_bc[lane]; if (c) gb = atomicAdd(&cursor[(uint64_t)lane * B.n_struct + s], c); }
     }
     uint32_t h_ij = 0, h_ji = 0, aai = 0, aaj = 0;
     if (lane < n) {
@@ -380,18 +415,12 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
         }
     }
     if (MSD) {
-        // the claim's result is first needed HERE.  Without this barrier the compiler widens gb to 64 bits where it is defined: a register copy right
-        // behind global_atomic_add, and in front of it s_waitcnt vmcnt(0) — every drain then sat out the atomic's round trip to L2 (and the stores
-        // of the drain before) ahead of the gather of frame j instead of behind the descriptor
-        asm volatile("" : "+v"(gb));
-        if (lane < FD_MSD_BUCKETS) s_bb[lane] = s_boff[lane] + gb;      // first slot of this drain's keys in every bucket (a build call may hold more than 2^32 keys)
-        fd_wave_lds_fence();
         if (lane < n) {
             const uint32_t sf = slots & 255u, sr = (slots >> 8) & 255u, bf = (slots >> 16) & 255u, br = slots >> 24;
             // the bucket comes from the residue types like in the count pass (== hash >> 24 unless a saturated distance field bled into
             // the type bits: such a hash raises wide_flag and the build is redone with 8-byte elements; its key still lands in a counted slot)
             if ((((h_ij | h_ji) >> 30) || (h_ij >> 24) != bf || (h_ji >> 24) != br) && C.wide_flag) atomicOr(C.wide_flag, 1ull);
-            const uint64_t pf = s_bb[bf] + sf, pr = s_bb[br] + sr;
+            const uint64_t pf = s_boff[bf] + sf, pr = s_boff[br] + sr;      // 64 bits: a build call may hold more than 2^32 keys
             // the position says which bucket (the top six hash bits); the other 24 are the three sorted digits: the u32 plane keeps
             // hash[7:0] << 24 | s (s < 2^24), the u16 plane hash[23:8] — a histogram pass of the sort reads only its digit's plane
             keys[pf] = (h_ij << 24) | s;
@@ -399,6 +428,8 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
             ((uint16_t *)ids)[pf] = (uint16_t)(h_ij >> 8);
             ((uint16_t *)ids)[pr] = (uint16_t)(h_ji >> 8);
         }
+        fd_wave_lds_fence();
+        if (lane < FD_MSD_BUCKETS) s_boff[lane] += s_bc[lane];      // the next drain's first slot in every bucket
         return;
     }
     if (lane < n) {
@@ -460,8 +491,8 @@ __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_
         for (int k = 0; k < 4; ++k) s_fi[k * FD_WAVE + lane] = fp[k];
     }
     __shared__ uint32_t s_bc[MSD ? FD_WAVE : 1];
-    __shared__ uint64_t s_bb[MSD ? FD_MSD_BUCKETS : 1], s_boff[MSD ? FD_MSD_BUCKETS : 1];      // forty of each: with 64 the workgroup passes 8 KB and the CU holds 19 of them, not 20
-    if (MSD && lane < FD_MSD_BUCKETS) s_boff[lane] = seg_off[(uint64_t)lane * B.n_struct + s];      // where the structure's keys of every bucket start
+    __shared__ uint64_t s_boff[MSD ? FD_MSD_BUCKETS : 1];      // forty, not 64: the workgroup stays below 8 KB, 20 of them on a CU
+    if (MSD && lane < FD_MSD_BUCKETS) s_boff[lane] = seg_off[(uint64_t)lane * B.n_work + w];      // where the work item's keys of every bucket start: its cursor
     __syncthreads();
     const uint64_t vim = __ballot(vi);
     const uint32_t lane16 = lane << 16;
@@ -486,7 +517,7 @@ __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_
                     fd_wave_lds_fence();
                     uint32_t n = qn < FD_WAVE ? qn : FD_WAVE;
                     qn -= n;
-                    drain2<TAB, IDS16, MSD, DT>(B, frames, C, tab, q + qn, n, i0, r0, s, first_id + s, seg_off, cursor, keys, ids, s_fi, s_bc, s_bb, s_boff);
+                    drain2<TAB, IDS16, MSD, DT>(B, frames, C, tab, q + qn, n, i0, r0, s, first_id + s, seg_off, cursor, keys, ids, s_fi, s_bc, s_boff);
                     fd_wave_lds_fence();
                 }
             },
@@ -641,24 +672,26 @@ void fd_launch_pair_emit2(const fd_batch_view &B, const void *frames, const fd_h
     else if (ids16) hipLaunchKernelGGL((k_pair_emit2<0, true, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
     else hipLaunchKernelGGL((k_pair_emit2<0, false, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
 }
-// the MSD build (6-byte elements): B = the permuted view (ca_xyz / hash_ok / aa = the arrays k_frames_perm wrote), seg_off / cursor = [40][S]
-void fd_launch_frames_perm(const fd_batch_view &B, void *frames, float *ca_perm, uint8_t *ok_perm, uint8_t *aa_perm, unsigned long long *wide_flag, hipStream_t st) {
+// the MSD build (6-byte elements): B = the permuted view (ca_xyz / hash_ok / aa = the arrays k_frames_perm wrote), counts / seg_off = [40][n_work]
+void fd_launch_frames_perm(const fd_batch_view &B, float *ca_perm, uint8_t *ok_perm, uint8_t *aa_perm, uint32_t *src_perm, unsigned long long *wide_flag, hipStream_t st) {
     if (!B.n_struct) return;
-    hipLaunchKernelGGL(k_frames_perm, dim3(B.n_struct), dim3(256), 0, st, B, (fd_frame *)frames, ca_perm, ok_perm, aa_perm, wide_flag);
+    hipLaunchKernelGGL(k_frames_perm, dim3(B.n_struct), dim3(256), 0, st, B, ca_perm, ok_perm, aa_perm, src_perm, wide_flag);
 }
-void fd_launch_pair_count_msd(const fd_batch_view &B, const fd_hash_consts &C, uint32_t *counts, hipStream_t st) {
+// n_xyz / cb_xyz: the batch's own arrays (chain order), src_perm: what k_frames_perm wrote; the kernel fills frames (permuted order)
+void fd_launch_pair_count_msd(const fd_batch_view &B, const fd_hash_consts &C, const float *n_xyz, const float *cb_xyz, const uint32_t *src_perm, void *frames,
+                              uint32_t *counts, hipStream_t st) {
     if (!B.n_work) return;
-    hipLaunchKernelGGL(k_pair_count_msd, dim3(grid_for(B.n_work)), dim3(FD_WAVE), 0, st, B, C, counts);
+    hipLaunchKernelGGL(k_pair_count_msd, dim3(grid_for(B.n_work)), dim3(FD_WAVE), 0, st, B, C, n_xyz, cb_xyz, src_perm, (fd_frame *)frames, counts);
 }
-void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const fd_hash_consts &C, const uint64_t *seg_off, uint32_t *cursor, uint32_t *keys,
+void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const fd_hash_consts &C, const uint64_t *seg_off, uint32_t *keys,
                              uint16_t *ids, hipStream_t st) {
     if (!B.n_work) return;
     dim3 g(grid_for(B.n_work)), b(FD_WAVE);
     const fd_frame *F = (const fd_frame *)frames;
-    if (C.use_tab == 3) hipLaunchKernelGGL((k_pair_emit2<2, true, true, true>), g, b, 0, st, B, F, C, seg_off, cursor, keys, (void *)ids, 0u);      // + squared-distance table
-    else if (C.use_tab == 2) hipLaunchKernelGGL((k_pair_emit2<2, true, true>), g, b, 0, st, B, F, C, seg_off, cursor, keys, (void *)ids, 0u);
-    else if (C.use_tab) hipLaunchKernelGGL((k_pair_emit2<1, true, true>), g, b, 0, st, B, F, C, seg_off, cursor, keys, (void *)ids, 0u);
-    else hipLaunchKernelGGL((k_pair_emit2<0, true, true>), g, b, 0, st, B, F, C, seg_off, cursor, keys, (void *)ids, 0u);
+    if (C.use_tab == 3) hipLaunchKernelGGL((k_pair_emit2<2, true, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);      // + squared-distance table
+    else if (C.use_tab == 2) hipLaunchKernelGGL((k_pair_emit2<2, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);
+    else if (C.use_tab) hipLaunchKernelGGL((k_pair_emit2<1, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);
+    else hipLaunchKernelGGL((k_pair_emit2<0, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);
 }
 void fd_launch_row_count(const fd_batch_view &B, const fd_hash_consts &C, uint32_t *row_cnt, float cutoff, hipStream_t st) {
     if (!B.n_work) return;

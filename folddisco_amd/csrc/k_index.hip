@@ -21,7 +21,7 @@ struct enc_item { uint32_t len; uint32_t head; uint32_t delta; uint32_t hash; };
 //   V = uint32_t      : keys[p] = hash,                      vals[p] = structure id
 //   V = uint16_t      : keys[p] = hash << 2 | (local >> 16), vals[p] = local & 0xffff, id = first_id + local  (6-byte elements, 2^18 structures)
 //   V = uint16_t, B24 : keys[p] = hash[7:0] << 24 | local, vals[p] = hash[23:8]  — the MSD build's stream (digit planes: k_sort.hip): the top six
-//                       hash bits ARE the bucket the position p lies in (bucket b = [seg_off[b * S], seg_off[(b + 1) * S])), the two planes keep
+//                       hash bits ARE the bucket the position p lies in (bucket b = [seg_off[b * stride], seg_off[(b + 1) * stride]), stride = the build's work items), the two planes keep
 //                       the other 24 and the whole local id (2^24 structures): hash = bucket << 24 | val << 8 | key >> 24, id = first_id + (key & 0xffffff)
 template <typename V> struct enc_codec;
 template <> struct enc_codec<uint32_t> {
@@ -34,7 +34,7 @@ template <> struct enc_codec<uint16_t> {
 };
 
 #define ENC_BUCKETS 40u
-struct enc_b24 {              // B24: where the forty buckets start (bo[0..40], compact copy of seg_off[b * S]) and the tile's first / last bucket
+struct enc_b24 {              // B24: where the forty buckets start (bo[0..40], compact copy of seg_off[b * stride]) and the tile's first / last bucket
     const uint64_t *bo;
     uint32_t b0, b1;
     __device__ __forceinline__ uint32_t at(uint64_t p) const { uint32_t b = b0; while (b < b1 && p >= bo[b + 1]) ++b; return b; }      // tiles on a boundary only
@@ -282,7 +282,7 @@ __global__ void k_set_u64(uint64_t *dst, uint64_t idx, const uint64_t *src) { ds
 
 uint32_t fd_enc_num_tiles(uint64_t n) { return (uint32_t)((n + ENC_TILE - 1) / ENC_TILE); }
 // codec: 0 = (u32 hash, u32 id), 1 = 6-byte elements of the structure-major stream, 2 = 6-byte elements of the MSD stream (seg_off = its [40][S]
-// table, bo = 41 words of scratch that receive the bucket starts; fd_launch_enc_write reads them again)
+// table, S here = the table's stride: the build's work items, bo = 41 words of scratch that receive the bucket starts; fd_launch_enc_write reads them again)
 void fd_launch_enc_sizes(const uint32_t *keys, const void *ids, int codec, uint32_t first_id, uint64_t n, uint32_t *tb, uint32_t *th, uint32_t *tp,
                          const uint64_t *seg_off, uint64_t S, uint64_t *bo, hipStream_t st) {
     if (!n) return;
