@@ -250,6 +250,7 @@ SYMBOLS = [
     ("fdgpu_debug_last_count_path", C.c_int, [VP, u32p]),
     ("fdgpu_debug_last_retrieve_path", C.c_int, [VP, u32p]),
     ("fdgpu_debug_encode_stream", C.c_int, [VP, u32p, u32p, C.c_uint64, C.POINTER(VP)]),
+    ("fdgpu_debug_encode_stream_b24", C.c_int, [VP, u32p, u32p, C.c_uint64, C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_ingest_stats", None, [C.POINTER(C.c_double), C.c_int]),
     ("fdgpu_debug_gunzip", C.c_int, [u8p, C.c_uint64, C.POINTER(u8p), u64p]),
     ("fdgpu_debug_host_components", C.c_int, [u32p, u32p, C.c_uint64, C.c_uint32, C.POINTER(u32p), C.POINTER(u64p), u64p]),

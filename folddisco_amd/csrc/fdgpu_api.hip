@@ -889,6 +889,49 @@ extern "C" int fdgpu_debug_encode_stream(fdgpu_ctx *c, const uint32_t *hashes, c
     }
     return encode_sorted_stream(c, c->ws[WS_KEYS_A].as<uint32_t>(), c->ws[WS_IDS_A].p, 0, 0, n, S, 0, out);
 }
+// Test-only: the same on the 6-byte elements of the MSD build's stream (codec 2), packed here on the host; the 41 bucket starts go to WS_SEGOFF at stride 1.
+// The stream is checked before the context is looked at: without one (ctx NULL) the call is those checks alone, which a test without a device can reach.
+extern "C" int fdgpu_debug_encode_stream_b24(fdgpu_ctx *c, const uint32_t *hashes, const uint32_t *local_ids, uint64_t n, uint64_t first_id, fdgpu_index **out) { FD_LOCK(c);
+    if (!out || (n && (!hashes || !local_ids))) return FDGPU_EINVAL;
+    *out = nullptr;
+    const uint32_t NB = 40;
+    uint64_t S = 0;
+    const char *why = n >= 0xffffffffull ? "encode_stream_b24: 2^32 elements or more" : nullptr;
+    for (uint64_t p = 0; p < n && !why; ++p) {
+        const uint32_t h = hashes[p], id = local_ids[p];
+        if (h >= (1u << 30) || (h >> 24) >= NB) why = "encode_stream_b24: a hash of 2^30 or more, or in a bucket (hash >> 24) of 40 or more";
+        else if (id >= (1u << 24)) why = "encode_stream_b24: a local id of 2^24 or more";
+        else if (p && (hashes[p - 1] > h || (hashes[p - 1] == h && local_ids[p - 1] > id))) why = "encode_stream_b24: the stream is not sorted by (hash, id)";
+        S = std::max<uint64_t>(S, (uint64_t)id + 1);
+    }
+    if (!why && first_id + S > 0xffffffffull) why = "encode_stream_b24: structure ids exceed 32 bits";
+    if (why) { if (c) c->err = why; return FDGPU_EINVAL; }
+    if (!c) return FDGPU_OK;
+    std::vector<uint32_t> k32(std::max<uint64_t>(n, 1));
+    std::vector<uint16_t> v16(std::max<uint64_t>(n, 1));
+    std::vector<uint64_t> seg(NB + 2, 0);      // seg[b + 1] counts bucket b, then the running sum: seg[b] = where bucket b starts, seg[40] = n
+    for (uint64_t p = 0; p < n; ++p) {
+        const uint32_t h = hashes[p];
+        k32[p] = (h & 0xffu) << 24 | local_ids[p];
+        v16[p] = (uint16_t)(h >> 8);
+        ++seg[(h >> 24) + 1];
+    }
+    for (uint32_t b = 0; b < NB; ++b) seg[b + 1] += seg[b];
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->ws[WS_MISC3].ensure(512));
+    HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC3].p, 0, 64, st));
+    HIPCHK(c, c->ws[WS_KEYS_A].ensure(k32.size() * 4));
+    HIPCHK(c, c->ws[WS_IDS_A].ensure(v16.size() * 2));
+    HIPCHK(c, c->ws[WS_SEGOFF].ensure((NB + 2) * 8));
+    HIPCHK(c, hipMemcpyAsync(c->ws[WS_SEGOFF].p, seg.data(), (NB + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(c->ws[WS_KEYS_A].p, k32.data(), n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ws[WS_IDS_A].p, v16.data(), n * 2, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));      // the host vectors go out of scope with this call
+    return encode_sorted_stream(c, c->ws[WS_KEYS_A].as<uint32_t>(), c->ws[WS_IDS_A].p, 2, first_id, n, S, 1, out);
+}
 
 // A large device-to-host copy into ordinary (pageable) memory.  The runtime's own path stages through one internal buffer and one
 // host thread (~12 GB/s: 2.2 s for the 26 GB of a Swiss-Prot-scale index); here FD_PIN_SLOTS pinned buffers are filled by

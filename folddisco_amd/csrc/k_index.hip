@@ -8,6 +8,13 @@
 //   * lists are laid out in ascending hash order; only non-empty hashes are kept (sparse form):
 //     hashes[H], offsets[H+1] with offsets[k] = first byte of list k, offsets[H] = total bytes.
 // Two streaming passes over the sorted pairs (sizes, then write), HBM-bound.
+//
+// Precondition of the MSD stream (codec 2, B24 below): inside every one of the forty buckets the u16 plane (hash[23:8]) is non-decreasing.  The
+// segmented sort guarantees it (fd_radix_sort_pairs16_seg, k_sort.hip, with the digit order of the build, fdgpu_api.hip: hash[7:0], then the u16
+// plane's low byte, then its high byte LAST, each pass stable), and fdgpu_debug_encode_stream_b24 checks it of a caller's stream.  Both passes
+// rely on it: a tile of ENC_TILE elements that lies in one bucket, predecessor element included, and whose two end elements carry the same u16
+// value holds that value everywhere, so such a tile reads two elements of the plane and not its 4 KB (enc_b24::cst).  The two passes take the
+// same decision for a tile: same predicate, same inputs.  Codecs 0 and 1 have no such path: their second plane is the id.
 #include "fd_device.h"
 #include "fd_postings.h"
 
@@ -37,65 +44,107 @@ template <> struct enc_codec<uint16_t> {
 struct enc_b24 {              // B24: where the forty buckets start (bo[0..40], compact copy of seg_off[b * stride]) and the tile's first / last bucket
     const uint64_t *bo;
     uint32_t b0, b1;
+    bool cst;                 // the tile and its predecessor element hold ONE u16 value, `ev` (workgroup-uniform; see the precondition above)
+    uint32_t ev;
     __device__ __forceinline__ uint32_t at(uint64_t p) const { uint32_t b = b0; while (b < b1 && p >= bo[b + 1]) ++b; return b; }      // tiles on a boundary only
 };
-// per wave, no LDS and no barrier: lane l holds bo[l]; called AFTER the tile's key loads are in flight
-__device__ __forceinline__ enc_b24 enc_b24_setup(const uint64_t *__restrict__ bo, uint64_t n) {
+// What a wave reads to classify its tile, per wave, no LDS and no barrier: lane l holds bo[l], every lane the u16 values at the tile's two ends (tp =
+// the predecessor of its first element, t1 = its last valid one).  Issued BEFORE the tile's key loads: the memory counter retires loads in issue
+// order, so enc_b24_setup's wait for these three leaves the key loads in flight, where behind them it would be the wait for the keys as well.
+struct enc_b24_raw { uint64_t o; uint32_t e0, e1; };
+__device__ __forceinline__ enc_b24_raw enc_b24_fetch(const uint64_t *__restrict__ bo, const uint16_t *__restrict__ vals, uint64_t n) {
+    const uint64_t t0 = (uint64_t)blockIdx.x * (256 * 8);
+    const uint64_t t1 = (t0 + 256 * 8 < n ? t0 + 256 * 8 : n) - 1;
+    const uint64_t tp = t0 ? t0 - 1 : 0;
+    const uint32_t lane = threadIdx.x & 63;
+    enc_b24_raw R;
+    R.o = lane >= 1 && lane <= ENC_BUCKETS ? bo[lane] : ~0ull;
+    R.e0 = vals[tp];
+    R.e1 = vals[t1];
+    return R;
+}
+__device__ __forceinline__ enc_b24 enc_b24_setup(const uint64_t *__restrict__ bo, uint64_t n, const enc_b24_raw &R) {
     const uint64_t t0 = (uint64_t)blockIdx.x * (256 * 8);
     const uint64_t t1 = (t0 + 256 * 8 < n ? t0 + 256 * 8 : n) - 1;
     const uint64_t tp = t0 ? t0 - 1 : 0;      // the predecessor of the tile's first element is classified too
     const uint32_t lane = threadIdx.x & 63;
     const bool in = lane >= 1 && lane <= ENC_BUCKETS;
-    const uint64_t o = in ? bo[lane] : ~0ull;
     enc_b24 K;
     K.bo = bo;
-    K.b0 = (uint32_t)__popcll(__ballot(in && o <= tp));      // buckets 1..40 that start at or before p: the bucket p lies in
-    K.b1 = (uint32_t)__popcll(__ballot(in && o <= t1));
+    K.b0 = (uint32_t)__popcll(__ballot(in && R.o <= tp));      // buckets 1..40 that start at or before p: the bucket p lies in
+    K.b1 = (uint32_t)__popcll(__ballot(in && R.o <= t1));
     if (K.b0 >= ENC_BUCKETS) K.b0 = ENC_BUCKETS - 1;
     if (K.b1 >= ENC_BUCKETS) K.b1 = ENC_BUCKETS - 1;
+    // every lane loaded the same two elements: as scalars, so that the branches on `cst` are uniform branches and not exec masks
+    // (both read before the comparison: behind a short-circuit the compiler moves the load of e0 there too, one more round trip)
+    const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)R.e0);
+    K.ev = (uint32_t)__builtin_amdgcn_readfirstlane((int)R.e1);
+    K.cst = (K.b0 == K.b1) & (e0 == K.ev);
     return K;
 }
 __global__ void k_enc_bucket_starts(const uint64_t *__restrict__ seg_off, uint64_t S, uint64_t *__restrict__ bo) {
     if (threadIdx.x <= ENC_BUCKETS) bo[threadIdx.x] = seg_off[(uint64_t)threadIdx.x * S];
 }
 
-// Loads the ENC_ITEMS (= 8) consecutive elements owned by this thread with 16-byte loads (full tiles) and
-// classifies them; the predecessor of the thread's first element comes from the neighbouring lane (shuffle)
-// or, for lane 0 of a wave, from memory.
+// The two ways a thread gets its ENC_ITEMS (= 8) consecutive elements: 16-byte loads, or guarded loads per element at the stream's end.  B24: each
+// is ONE straight run — edge loads, key loads, the decision, the u16 plane if the tile is not constant — and enc_load_classify branches between
+// the two whole runs.  With the branch around the key loads alone, both sides met again before the decision, and there the compiler counts
+// the loads behind the edge loads by the side with the fewest (the guarded ones count as none): it waited for the keys before it looked at the
+// tile's ends.
+template <typename V, bool B24>
+__device__ __forceinline__ enc_b24 enc_load_full(const uint32_t *__restrict__ keys, const V *__restrict__ ids, uint64_t n, uint64_t base,
+                                                 const uint64_t *__restrict__ bo, uint32_t *k, uint32_t *v) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    enc_b24_raw R = {};
+    if (B24) R = enc_b24_fetch(bo, (const uint16_t *)ids, n);
+    const u32x4 *kp = reinterpret_cast<const u32x4 *>(keys + base);
+    u32x4 a = __builtin_nontemporal_load(&kp[0]), b = __builtin_nontemporal_load(&kp[1]);
+    k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w; k[4] = b.x; k[5] = b.y; k[6] = b.z; k[7] = b.w;
+    enc_b24 K = {};
+    if (B24) K = enc_b24_setup(bo, n, R);
+    if (B24 && K.cst) {      // workgroup-uniform
+#pragma unroll
+        for (int j = 0; j < ENC_ITEMS; ++j) v[j] = K.ev;
+    } else if (sizeof(V) == 2) {
+        u32x4 w = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ids + base));
+        v[0] = w.x & 0xffffu; v[1] = w.x >> 16; v[2] = w.y & 0xffffu; v[3] = w.y >> 16;
+        v[4] = w.z & 0xffffu; v[5] = w.z >> 16; v[6] = w.w & 0xffffu; v[7] = w.w >> 16;
+    } else {
+        const u32x4 *vp = reinterpret_cast<const u32x4 *>(ids + base);
+        u32x4 c = __builtin_nontemporal_load(&vp[0]), d = __builtin_nontemporal_load(&vp[1]);
+        v[0] = c.x; v[1] = c.y; v[2] = c.z; v[3] = c.w; v[4] = d.x; v[5] = d.y; v[6] = d.z; v[7] = d.w;
+    }
+    return K;
+}
+template <typename V, bool B24>
+__device__ __forceinline__ enc_b24 enc_load_tail(const uint32_t *__restrict__ keys, const V *__restrict__ ids, uint64_t n, uint64_t base,
+                                                 const uint64_t *__restrict__ bo, uint32_t *k, uint32_t *v) {
+    enc_b24 K = {};
+    if (B24) K = enc_b24_setup(bo, n, enc_b24_fetch(bo, (const uint16_t *)ids, n));
+#pragma unroll
+    for (int j = 0; j < ENC_ITEMS; ++j) {
+        uint64_t p = base + j;
+        k[j] = p < n ? keys[p] : 0u;
+        v[j] = B24 && K.cst ? K.ev : p < n ? (uint32_t)ids[p] : 0u;
+    }
+    return K;
+}
+
+// Loads the thread's elements and classifies them; the predecessor of the thread's first element comes from the neighbouring lane (shuffle)
+// or, for lane 0 of a wave, from memory.  B24: a constant tile (enc_b24::cst) reads nothing of the u16 plane but its two end elements.
 template <typename V, bool B24>
 __device__ __forceinline__ void enc_load_classify(const uint32_t *__restrict__ keys, const V *__restrict__ ids, uint64_t n, uint64_t base,
                                                   uint32_t first_id, enc_item *it, const uint64_t *__restrict__ bo, uint32_t *pred_id = nullptr) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     uint32_t k[ENC_ITEMS], v[ENC_ITEMS];
-    const bool full = base + ENC_ITEMS <= n;
-    if (full) {
-        const u32x4 *kp = reinterpret_cast<const u32x4 *>(keys + base);
-        u32x4 a = __builtin_nontemporal_load(&kp[0]), b = __builtin_nontemporal_load(&kp[1]);
-        k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w; k[4] = b.x; k[5] = b.y; k[6] = b.z; k[7] = b.w;
-        if (sizeof(V) == 2) {
-            u32x4 w = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ids + base));
-            v[0] = w.x & 0xffffu; v[1] = w.x >> 16; v[2] = w.y & 0xffffu; v[3] = w.y >> 16;
-            v[4] = w.z & 0xffffu; v[5] = w.z >> 16; v[6] = w.w & 0xffffu; v[7] = w.w >> 16;
-        } else {
-            const u32x4 *vp = reinterpret_cast<const u32x4 *>(ids + base);
-            u32x4 c = __builtin_nontemporal_load(&vp[0]), d = __builtin_nontemporal_load(&vp[1]);
-            v[0] = c.x; v[1] = c.y; v[2] = c.z; v[3] = c.w; v[4] = d.x; v[5] = d.y; v[6] = d.z; v[7] = d.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < ENC_ITEMS; ++j) {
-            uint64_t p = base + j;
-            k[j] = p < n ? keys[p] : 0u;
-            v[j] = p < n ? (uint32_t)ids[p] : 0u;
-        }
-    }
+    // B24: by the tile and not by the thread, so that the whole workgroup goes one way (enc_b24_setup holds wave-wide ballots)
+    const bool full = B24 ? ((uint64_t)blockIdx.x + 1) * ENC_TILE <= n : base + ENC_ITEMS <= n;
+    const enc_b24 K = full ? enc_load_full<V, B24>(keys, ids, n, base, bo, k, v) : enc_load_tail<V, B24>(keys, ids, n, base, bo, k, v);
     // predecessor of element 0
     uint32_t pk = __shfl_up(k[ENC_ITEMS - 1], 1, FD_WAVE), pv = __shfl_up(v[ENC_ITEMS - 1], 1, FD_WAVE);
-    if ((threadIdx.x & 63) == 0 && base > 0 && base < n) { pk = keys[base - 1]; pv = (uint32_t)ids[base - 1]; }
+    if ((threadIdx.x & 63) == 0 && base > 0 && base < n) { pk = keys[base - 1]; pv = B24 && K.cst ? K.ev : (uint32_t)ids[base - 1]; }
     uint32_t ph, pid;
     uint32_t hb[ENC_ITEMS];      // B24: the items' bucket << 24 — one value for the whole tile unless it lies on one of the 40 boundaries
     if (B24) {
-        const enc_b24 K = enc_b24_setup(bo, n);
         uint32_t pb = K.b0;
 #pragma unroll
         for (int j = 0; j < ENC_ITEMS; ++j) hb[j] = K.b0 << 24;

@@ -33,6 +33,13 @@ int fdgpu_debug_libm(fdgpu_ctx *ctx, int op, const float *a, const float *b, flo
  * the build (u32 hash, u32 id; first_id 0).  *out: a resident index of max(ids) + 1 structures, released with fdgpu_index_destroy.  Lets a test
  * place list heads, varint lengths, duplicates and byte alignments where proteins never put them.  FDGPU_EINVAL for an unsorted stream. */
 int fdgpu_debug_encode_stream(fdgpu_ctx *ctx, const uint32_t *hashes, const uint32_t *ids, uint64_t n, fdgpu_index **out);
+/* The same on the 6-byte elements of the default build's stream (codec 2 of csrc/k_index.hip), which the entry above does not reach: the stream
+ * (hashes[p], first_id + local_ids[p]), sorted by (hash, local id), is packed on the host into the two planes (u32 = hash[7:0] << 24 | local id,
+ * u16 = hash[23:8]) and the 41 starts of the buckets hash >> 24.  Requires hash < 2^30, hash >> 24 < 40 and local id < 2^24; FDGPU_EINVAL for
+ * anything else and for an unsorted stream.  *out: a resident index of max(local_ids) + 1 structures with that first_id.  The stream is checked
+ * before the context is used: with ctx NULL the call is the checks alone (FDGPU_OK for a stream it would encode, *out stays NULL), which a test
+ * without a device can reach. */
+int fdgpu_debug_encode_stream_b24(fdgpu_ctx *ctx, const uint32_t *hashes, const uint32_t *local_ids, uint64_t n, uint64_t first_id, fdgpu_index **out);
 
 /* Host-only pieces of the retrieval glue for graphs of more than 64 nodes (csrc/fd_host_query.hip), callable without a GPU.
  * fdgpu_debug_host_components: the graph of the found residue pairs (edge_i[e] -> edge_j[e], nodes numbered by first appearance,
