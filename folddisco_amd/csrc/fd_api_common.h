@@ -1,5 +1,6 @@
-// fd_api_common.h — what the files of the C ABI share (fdgpu_api.hip: context, batches, S1, S2; fd_api_count.hip: S3; fd_api_match.hip: S4): the
-// error macros (every entry point returns a code, the message goes to the context) and a few helpers defined in fdgpu_api.hip.
+// fd_api_common.h — what the files of the C ABI share (fdgpu_api.hip: context, batches, hash constants, the index object; fd_api_build.hip: S1 and the
+// build of S2; fd_api_count.hip: S3; fd_api_match.hip: S4): the error macros (every entry point returns a code, the message goes to the context) and a
+// few helpers defined in fdgpu_api.hip.
 #pragma once
 #include "fdgpu_internal.h"
 

@@ -1,6 +1,6 @@
-// fdgpu_api.hip — C ABI of libfdgpu.so (include/fdgpu.h): context, HBM residency, and the
-// orchestration of the kernels in k_hash.hip / k_sort.hip / k_index.hip / k_query.hip / k_match.hip.
-// No CPU fallback exists: every entry point fails with FDGPU_EHIP if no gfx950 device answers.
+// fdgpu_api.hip — C ABI of libfdgpu.so (include/fdgpu.h): the context, the result pool, batches, the hash constants, the index object (the other half of S2:
+// fd_index_new, destroy, accessors), export / load / save and the pinned copy paths.  The hashers and the build are in fd_api_build.hip, S3 in
+// fd_api_count.hip, S4 in fd_api_match.hip.  No CPU fallback exists: every entry point fails with FDGPU_EHIP if no gfx950 device answers.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -466,169 +466,12 @@ int d2h_u64(fdgpu_ctx *c, const uint64_t *dev, uint64_t *host) {
     return FDGPU_OK;
 }
 
-// pair count -> segment offsets; returns total pairs
-static int count_and_scan(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_consts &C, uint64_t *P, bool unordered = false) {
-    uint64_t S = b->n_struct;
-    HIPCHK(c, c->ws[WS_COUNTS].ensure((S + 1) * 4));
-    HIPCHK(c, c->ws[WS_CURSOR].ensure((S + 1) * 4));
-    HIPCHK(c, c->ws[WS_SEGOFF].ensure((S + 2) * 8));
-    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(S, b->n_res)) * 8 + 64));
-    HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-    HIPCHK(c, hipMemsetAsync(c->ws[WS_COUNTS].p, 0, (S + 1) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ws[WS_CURSOR].p, 0, (S + 1) * 4, c->stream));
-    {
-        StageTimer t(c, "pair_count", b->n_res * 13);
-        if (unordered) fd_launch_pair_count2(b->view(), C, c->ws[WS_COUNTS].as<uint32_t>(), c->stream);
-        else fd_launch_pair_count(b->view(), C, c->ws[WS_COUNTS].as<uint32_t>(), c->stream);
-    }
-    {
-        StageTimer t(c, "segment_scan", S * 12);
-        fd_exclusive_scan<uint32_t>(c->ws[WS_COUNTS].as<uint32_t>(), S, c->ws[WS_SEGOFF].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(),
-                                    c->ws[WS_TOTAL].as<uint64_t>(), c->stream);
-    }
-    HIPCHK(c, hipGetLastError());
-    return d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), P);
-}
-
-static int ensure_sort_ws(fdgpu_ctx *c, uint64_t P, size_t id_bytes = 4) {
-    size_t kb = std::max<uint64_t>(P, 1) * 4, ib = std::max<uint64_t>(P, 1) * id_bytes + 16;
-    // a call that grows the sort buffers by gigabytes first returns the cached blocks of destroyed indices to the device
-    if (kb > c->ws[WS_KEYS_A].cap + ((size_t)1 << 30) || kb > c->ws[WS_KEYS_B].cap + ((size_t)1 << 30)) c->pool_drop();
-    HIPCHK(c, c->ws[WS_KEYS_A].ensure(kb));
-    HIPCHK(c, c->ws[WS_IDS_A].ensure(ib));
-    HIPCHK(c, c->ws[WS_KEYS_B].ensure(kb));
-    HIPCHK(c, c->ws[WS_IDS_B].ensure(ib));
-    HIPCHK(c, c->ws[WS_GHIST].ensure((size_t)256 * std::max<uint32_t>(fd_rs_num_tiles(P), 1) * 4));
-    // 256 digit totals + the chunk sums of the tile-major histogram scan ([tiles / 128][256] u64)
-    HIPCHK(c, c->ws[WS_TOT].ensure((256 + (size_t)(fd_rs_num_tiles(P) / 128 + 2) * 256) * 8));
-    return FDGPU_OK;
-}
-
 // stable sort of (keys, vals) by the low key_bits of keys
 int sort_pairs(fdgpu_ctx *c, uint32_t *ka, uint32_t *va, uint32_t *kb, uint32_t *vb, uint64_t n, int key_bits) {
     return fd_radix_sort_pairs(ka, va, kb, vb, n, key_bits, c->ws[WS_GHIST].as<uint32_t>(), c->ws[WS_TOT].as<uint64_t>(), c->stream, c);
 }
 
-// ---- S1 ---------------------------------------------------------------------------------------------------------------
-extern "C" int fdgpu_hash_batch(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, int sort_dedup, uint32_t **hashes,
-                                uint64_t **hash_off) { FD_LOCK(c);
-    if (!c || !b || !p || !hashes || !hash_off) return FDGPU_EINVAL;
-    *hashes = nullptr; *hash_off = nullptr;
-    if (p->n_multiple_bins) FAIL(c, FDGPU_EINVAL, "hash_batch: multiple_bins is honoured by the index build and the query calls only");
-    if (!fd_hash_type_supported(p->hash_type)) FAIL(c, FDGPU_EINVAL, "hash_type: only the encodings over the (d_CA, d_CB, theta, tau1, tau2) descriptor are built (0, 1, 3, 7, 8)");
-    reset_timings(c);
-    fd_hash_consts C = make_consts(p);
-    uint64_t S = b->n_struct, R = b->n_res;
-    uint64_t *h_off = (uint64_t *)malloc((S + 1) * 8);
-    if (!h_off) return FDGPU_ENOMEM;
-    hipStream_t st = c->stream;
-    if (!sort_dedup) {
-        // row-major raw list: per-residue row counts -> row offsets -> ordered emit
-        HIPCHK(c, c->ws[WS_MISC0].ensure((R + 1) * 4));
-        HIPCHK(c, c->ws[WS_MISC1].ensure((R + 2) * 8));
-        HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(S, R)) * 8 + 64));
-        HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC0].p, 0, (R + 1) * 4, st));
-        fd_launch_row_count(b->view(), C, c->ws[WS_MISC0].as<uint32_t>(), p->dist_cutoff, st);
-        fd_exclusive_scan<uint32_t>(c->ws[WS_MISC0].as<uint32_t>(), R, c->ws[WS_MISC1].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(),
-                                    c->ws[WS_TOTAL].as<uint64_t>(), st);
-        HIPCHK(c, hipGetLastError());
-        uint64_t P = 0;
-        int rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &P);
-        if (rc) { free(h_off); return rc; }
-        HIPCHK(c, c->ws[WS_KEYS_A].ensure(std::max<uint64_t>(P, 1) * 4));
-        fd_launch_row_emit(b->view(), C, c->ws[WS_MISC1].as<uint64_t>(), c->ws[WS_KEYS_A].as<uint32_t>(), p->dist_cutoff, nullptr, 0u, st);
-        HIPCHK(c, hipGetLastError());
-        uint32_t *h = (uint32_t *)malloc(std::max<uint64_t>(P, 1) * 4);
-        std::vector<uint64_t> row_off(R + 1);
-        if (!h) { free(h_off); return FDGPU_ENOMEM; }
-        HIPCHK(c, hipMemcpyAsync(h, c->ws[WS_KEYS_A].p, P * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(row_off.data(), c->ws[WS_MISC1].p, (R + 1) * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        for (uint64_t s = 0; s <= S; ++s) h_off[s] = row_off[b->h_res_off[s]];
-        *hashes = h; *hash_off = h_off;
-        return FDGPU_OK;
-    }
-    if (fd_own_descriptor(p->hash_type)) { free(h_off); FAIL(c, FDGPU_EINVAL, "hash_batch: this encoding is served in the reference's raw order only (sort_dedup = 0)"); }
-    uint64_t P = 0;
-    int rc = count_and_scan(c, b, C, &P);
-    if (rc) { free(h_off); return rc; }
-    if (P >= 0xffffffffull) { free(h_off); FAIL(c, FDGPU_ERANGE, "more than 2^32 residue pairs in one batch; split the batch"); }
-    if ((rc = ensure_sort_ws(c, P))) { free(h_off); return rc; }
-    uint32_t *ka = c->ws[WS_KEYS_A].as<uint32_t>(), *ia = c->ws[WS_IDS_A].as<uint32_t>();
-    uint32_t *kb = c->ws[WS_KEYS_B].as<uint32_t>(), *ib = c->ws[WS_IDS_B].as<uint32_t>();
-    fd_launch_pair_emit(b->view(), C, c->ws[WS_SEGOFF].as<uint64_t>(), c->ws[WS_CURSOR].as<uint32_t>(), ka, ia, 0u, st);
-    // sort by hash, then (stable) by structure -> (structure, hash) order
-    int cur = sort_pairs(c, ka, ia, kb, ib, P, 32);   // all 32 bits: unmasked field overflow can set bits 30-31
-    uint32_t *k1 = cur ? kb : ka, *i1 = cur ? ib : ia, *k2 = cur ? ka : kb, *i2 = cur ? ia : ib;
-    int id_bits = 1;
-    while (id_bits < 32 && (1ull << id_bits) < std::max<uint64_t>(S, 2)) ++id_bits;
-    int cur2 = sort_pairs(c, i1, k1, i2, k2, P, id_bits);
-    uint32_t *ids_s = cur2 ? i2 : i1, *keys_s = cur2 ? k2 : k1, *spare = cur2 ? k1 : k2;
-    // adjacent-unique compaction
-    HIPCHK(c, c->ws[WS_MISC0].ensure(std::max<uint64_t>(P, 1)));
-    HIPCHK(c, c->ws[WS_MISC1].ensure((P + 2) * 8));
-    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(P, S)) * 8 + 64));
-    fd_launch_uniq_flags(keys_s, ids_s, P, c->ws[WS_MISC0].as<uint8_t>(), st);
-    fd_exclusive_scan<uint8_t>(c->ws[WS_MISC0].as<uint8_t>(), P, c->ws[WS_MISC1].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(),
-                               c->ws[WS_TOTAL].as<uint64_t>(), st);
-    fd_launch_compact(keys_s, c->ws[WS_MISC0].as<uint8_t>(), c->ws[WS_MISC1].as<uint64_t>(), P, spare, st);
-    // hash_off[s] = unique position at the first raw element of structure s (segments survive the stable sort by id)
-    HIPCHK(c, c->ws[WS_MISC2].ensure((S + 2) * 8));
-    fd_launch_gather_u64(c->ws[WS_MISC1].as<uint64_t>(), c->ws[WS_SEGOFF].as<uint64_t>(), S + 1, c->ws[WS_MISC2].as<uint64_t>(), st);
-    HIPCHK(c, hipGetLastError());
-    uint64_t U = 0;
-    if ((rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &U))) { free(h_off); return rc; }
-    uint32_t *h = (uint32_t *)malloc(std::max<uint64_t>(U, 1) * 4);
-    if (!h) { free(h_off); return FDGPU_ENOMEM; }
-    HIPCHK(c, hipMemcpyAsync(h, spare, U * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(h_off, c->ws[WS_MISC2].p, (S + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    *hashes = h; *hash_off = h_off;
-    return FDGPU_OK;
-}
-
-// Raw hash list with positions: every ordered residue pair that has a feature, in the reference's row-major order, as
-// (hash, partner residue j); entries [row_off[i], row_off[i + 1]) belong to residue i (batch residue indices).  This is the inner loop of
-// collect_hash_id_pos (src/controller/summary.rs:632-690: get_single_feature + perfect_hash for every (i, j)) for a whole batch.
-extern "C" int fdgpu_hash_batch_rows(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, uint32_t **hashes, uint32_t **partner, uint64_t **row_off) { FD_LOCK(c);
-    if (!c || !b || !p || !hashes || !partner || !row_off) return FDGPU_EINVAL;
-    *hashes = nullptr; *partner = nullptr; *row_off = nullptr;
-    if (p->n_multiple_bins) FAIL(c, FDGPU_EINVAL, "hash_batch_rows: multiple_bins is honoured by the index build and the query calls only");
-    if (!fd_hash_type_supported(p->hash_type)) FAIL(c, FDGPU_EINVAL, "hash_type: unknown encoding");
-    reset_timings(c);
-    const fd_hash_consts C = make_consts(p);
-    const uint64_t R = b->n_res;
-    hipStream_t st = c->stream;
-    HIPCHK(c, c->ws[WS_MISC0].ensure((R + 1) * 4));
-    HIPCHK(c, c->ws[WS_MISC1].ensure((R + 2) * 8));
-    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(b->n_struct, R)) * 8 + 64));
-    HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-    HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC0].p, 0, (R + 1) * 4, st));
-    fd_launch_row_count(b->view(), C, c->ws[WS_MISC0].as<uint32_t>(), p->dist_cutoff, st);
-    fd_exclusive_scan<uint32_t>(c->ws[WS_MISC0].as<uint32_t>(), R, c->ws[WS_MISC1].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(),
-                                c->ws[WS_TOTAL].as<uint64_t>(), st);
-    HIPCHK(c, hipGetLastError());
-    uint64_t P = 0;
-    int rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &P);
-    if (rc) return rc;
-    HIPCHK(c, c->ws[WS_KEYS_A].ensure(std::max<uint64_t>(P, 1) * 4));
-    HIPCHK(c, c->ws[WS_IDS_A].ensure(std::max<uint64_t>(P, 1) * 4));
-    fd_launch_row_emit(b->view(), C, c->ws[WS_MISC1].as<uint64_t>(), c->ws[WS_KEYS_A].as<uint32_t>(), p->dist_cutoff, c->ws[WS_IDS_A].as<uint32_t>(), 0u, st, 1);
-    HIPCHK(c, hipGetLastError());
-    uint32_t *h = (uint32_t *)malloc(std::max<uint64_t>(P, 1) * 4), *pj = (uint32_t *)malloc(std::max<uint64_t>(P, 1) * 4);
-    uint64_t *ro = (uint64_t *)malloc((R + 1) * 8);
-    if (!h || !pj || !ro) { free(h); free(pj); free(ro); return FDGPU_ENOMEM; }
-    hipError_t e = hipMemcpyAsync(h, c->ws[WS_KEYS_A].p, P * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(pj, c->ws[WS_IDS_A].p, P * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ro, c->ws[WS_MISC1].p, (R + 1) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { free(h); free(pj); free(ro); c->err = std::string("hash_batch_rows: ") + hipGetErrorString(e); return FDGPU_EHIP; }
-    *hashes = h; *partner = pj; *row_off = ro;
-    return FDGPU_OK;
-}
-
-// ---- S2 ---------------------------------------------------------------------------------------------------------------
+// ---- S2: the index object (the build that fills it: fd_api_build.hip) --------------------------------------------------
 // An index's blocks come from the pool of the context that owns it (steady-state builds then call neither hipMalloc nor hipFree, which would
 // serialise the stream), or from hipMalloc for an index without one (fdgpu_index_load); fdgpu_index_destroy releases them the same way.
 hipError_t fd_index_block(fdgpu_ctx *pool, size_t bytes, void **p, size_t *cap) {
@@ -686,252 +529,6 @@ extern "C" uint64_t fdgpu_index_num_hashes(const fdgpu_index *ix) { return ix ? 
 extern "C" uint64_t fdgpu_index_value_len(const fdgpu_index *ix) { return ix ? ix->value_len : 0; }
 extern "C" uint64_t fdgpu_index_num_postings(const fdgpu_index *ix) { return ix ? ix->n_postings : 0; }
 extern "C" uint64_t fdgpu_index_num_structures(const fdgpu_index *ix) { return ix ? ix->n_structures : 0; }
-
-#define FDGPU_RETRY_WIDE 1000
-// The encoder on a sorted stream of P elements (codec: k_index.hip; S structures; for codec 2 WS_SEGOFF holds the stream's [40][seg_stride] table): sizes
-// per tile, their three scans, the totals read back, an index of exactly that size, the write pass.  WS_MISC3 was cleared by the caller (words 0-2
-// receive the totals, 3-4 are the build's wide / overflow flags).  Shared by the build and by fdgpu_debug_encode_stream.
-static int encode_sorted_stream(fdgpu_ctx *c, const uint32_t *ks, const void *is, int codec, uint64_t first_id, uint64_t P, uint64_t S, uint64_t seg_stride, fdgpu_index **out) {
-    hipStream_t st = c->stream;
-    const bool el6 = codec != 0;
-    int rc;
-    uint32_t nt = std::max<uint32_t>(fd_enc_num_tiles(P), 1);
-    HIPCHK(c, c->ws[WS_TILE_B].ensure((size_t)(nt + 1) * 4));
-    HIPCHK(c, c->ws[WS_TILE_H].ensure((size_t)(nt + 1) * 4));
-    HIPCHK(c, c->ws[WS_TILE_P].ensure((size_t)(nt + 1) * 4));
-    HIPCHK(c, c->ws[WS_TILE_BO].ensure((size_t)(nt + 2) * 8));
-    HIPCHK(c, c->ws[WS_TILE_HO].ensure((size_t)(nt + 2) * 8));
-    HIPCHK(c, c->ws[WS_TILE_PO].ensure((size_t)(nt + 2) * 8));
-    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(nt, S)) * 8 + 64));
-    uint64_t tot[5] = {0, 0, 0, 0, 0};
-    uint64_t nt_eff = P ? fd_enc_num_tiles(P) : 0;
-    {
-        StageTimer t(c, "encode_sizes", P * (el6 ? 6 : 8));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_B].p, 0, (size_t)(nt + 1) * 4, st));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_H].p, 0, (size_t)(nt + 1) * 4, st));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_TILE_P].p, 0, (size_t)(nt + 1) * 4, st));
-        fd_launch_enc_sizes(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_B].as<uint32_t>(), c->ws[WS_TILE_H].as<uint32_t>(), c->ws[WS_TILE_P].as<uint32_t>(),
-                            c->ws[WS_SEGOFF].as<uint64_t>(), seg_stride, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
-        uint64_t *totd = c->ws[WS_MISC3].as<uint64_t>();
-        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_B].as<uint32_t>(), nt_eff, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 0, st);
-        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_H].as<uint32_t>(), nt_eff, c->ws[WS_TILE_HO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 1, st);
-        fd_exclusive_scan<uint32_t>(c->ws[WS_TILE_P].as<uint32_t>(), nt_eff, c->ws[WS_TILE_PO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), totd + 2, st);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(tot, c->ws[WS_MISC3].p, 40, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (tot[4]) FAIL(c, FDGPU_ERANGE, "index build: one (residue-pair bucket, key digit) group holds 2^32 keys or more; build the shard in several calls and merge");
-    if (el6 && tot[3]) return FDGPU_RETRY_WIDE;
-    fdgpu_index *ix = nullptr;
-    if ((rc = fd_index_new(c, true, tot[1], tot[0], true, &ix))) return rc;
-    ix->n_postings = tot[2]; ix->n_structures = S; ix->first_id = first_id;
-    {
-        StageTimer t(c, "encode_write", P * (el6 ? 6 : 8) + ix->value_len + ix->n_hashes * 12);
-        fd_launch_enc_write(ks, is, codec, (uint32_t)first_id, P, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_TILE_HO].as<uint64_t>(), ix->value, ix->hashes, ix->offsets,
-                            ix->last_ids, c->ws[WS_MISC3].as<uint64_t>(), ix->n_hashes, c->ws[WS_MISC3].as<uint64_t>() + 8, st);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { c->err = std::string("encode launch: ") + hipGetErrorString(e); fdgpu_index_destroy(ix); return FDGPU_EHIP; }
-    *out = ix;
-    return FDGPU_OK;
-}
-
-// force32: 8-byte sort elements.  Returns FDGPU_RETRY_WIDE (internal) when the 6-byte form met a hash beyond 30 bits.
-static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, uint64_t first_id, fdgpu_index **out, bool force32) {
-    if (!c || !b || !p || !out) return FDGPU_EINVAL;
-    *out = nullptr;
-    if (!fd_hash_type_supported(p->hash_type)) FAIL(c, FDGPU_EINVAL, "hash_type: only the encodings over the (d_CA, d_CB, theta, tau1, tau2) descriptor are built (0, 1, 3, 7, 8)");
-    reset_timings(c);
-    if (first_id + b->n_struct > 0xffffffffull) FAIL(c, FDGPU_ERANGE, "structure ids exceed 32 bits");
-    if (!fd_multiple_bins_valid(p)) FAIL(c, FDGPU_EINVAL, "multiple_bins: at most 8 (dist, angle) bin pairs, no zero counts");
-    const uint32_t n_cfg = fd_num_bin_configs(p);
-    fd_hash_consts C = fd_make_consts_cfg(p, 0);
-    C.spec_miss = c->spec_miss;
-    hipStream_t st = c->stream;
-    uint64_t S = b->n_struct, P = 0;
-    HIPCHK(c, c->ws[WS_FRAMES].ensure(std::max<uint64_t>(b->n_res, 1) * sizeof(fd_frame)));
-    // the encodings with their own descriptor go one ordered pair at a time through the row kernels (reference order), 8-byte elements
-    const bool own = fd_own_descriptor(p->hash_type);
-    if (own && n_cfg > 1) FAIL(c, FDGPU_EINVAL, "multiple_bins is built for the encodings over the PDBTrRosetta descriptor only");
-    // shards of <= 2^18 structures use 6-byte sort elements (key = hash << 2 | local id bits 17:16, u16 payload) as long as
-    // every hash fits 30 bits; the 8-byte form (u32 hash, u32 id) otherwise
-    const bool ids16 = !own && !force32 && S <= (1ull << 18);
-    // MSD build (default encoding, 6-byte elements): the pair kernel writes the keys partitioned by the top six hash bits (forty buckets,
-    // residues visited in amino-acid order) and every bucket is sorted by the remaining 24 bits — three 8-bit passes instead of four.
-    // FDGPU_MSD=0 selects the structure-major stream + four passes (A/B measurements, tests).
-    const bool msd_env = [] { const char *e = getenv("FDGPU_MSD"); return !(e && e[0] == '0'); }();      // read per call: tests flip it
-    // its elements are 6 bytes too, but the bucket carries the top six hash bits: u32 plane = hash[7:0] << 24 | local id, u16 plane = hash[23:8] — 2^24 structures
-    const bool msd = msd_env && !own && !force32 && S <= (1ull << 24) && n_cfg == 1 && p->hash_type == FDGPU_HASH_PDBTR && S > 0;
-    const bool el6 = ids16 || msd;                       // 6-byte sort elements
-    const int codec = msd ? 2 : ids16 ? 1 : 0;           // of the sorted stream (k_index.hip)
-    const uint32_t NB = 40;
-    fd_batch_view V = b->view();
-    HIPCHK(c, c->ws[WS_MISC3].ensure(512));     // words 0-2: encode totals, 3: wide flag, 4: sort overflow flag, 8-48: the MSD stream's bucket starts for the encoder
-    HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC3].p, 0, 64, st));
-    C.wide_flag = c->ws[WS_MISC3].as<unsigned long long>() + 3;
-    if (msd) {
-        HIPCHK(c, c->ws[WS_CA_PERM].ensure(std::max<uint64_t>(b->n_res, 1) * 12));
-        HIPCHK(c, c->ws[WS_OK_PERM].ensure(std::max<uint64_t>(b->n_res, 1)));
-        HIPCHK(c, c->ws[WS_AA_PERM].ensure(std::max<uint64_t>(b->n_res, 1)));
-        HIPCHK(c, c->ws[WS_SRC_PERM].ensure(std::max<uint64_t>(b->n_res, 1) * 4));
-        StageTimer t(c, "frames", b->n_res * (2 + 14 + 18));      // the permutation alone: types and flags for the totals, then 14 B read and 18 B written per residue
-        fd_launch_frames_perm(V, c->ws[WS_CA_PERM].as<float>(), c->ws[WS_OK_PERM].as<uint8_t>(), c->ws[WS_AA_PERM].as<uint8_t>(), c->ws[WS_SRC_PERM].as<uint32_t>(),
-                              C.wide_flag, st);
-        V.ca_xyz = c->ws[WS_CA_PERM].as<float>(); V.hash_ok = c->ws[WS_OK_PERM].as<uint8_t>(); V.aa = c->ws[WS_AA_PERM].as<uint8_t>();
-        V.n_xyz = nullptr; V.cb_xyz = nullptr;      // the emit reads frames, not atoms; the count pass, which builds the frames, gets the batch's N / CB beside the view
-    } else {
-        StageTimer t(c, "frames", b->n_res * (37 + sizeof(fd_frame)));
-        fd_launch_frames(b->view(), b->n_res, c->ws[WS_FRAMES].p, st);
-    }
-    uint64_t P1 = 0;
-    int rc;
-    if (own) {
-        const uint64_t R = b->n_res;
-        HIPCHK(c, c->ws[WS_MISC0].ensure((R + 1) * 4));
-        HIPCHK(c, c->ws[WS_MISC1].ensure((R + 2) * 8));
-        HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(R, S)) * 8 + 64));
-        HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-        HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC0].p, 0, (R + 1) * 4, st));
-        {
-            StageTimer t(c, "pair_count", R * 37);
-            fd_launch_row_count(b->view(), C, c->ws[WS_MISC0].as<uint32_t>(), p->dist_cutoff, st);
-            fd_exclusive_scan<uint32_t>(c->ws[WS_MISC0].as<uint32_t>(), R, c->ws[WS_MISC1].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(),
-                                        c->ws[WS_TOTAL].as<uint64_t>(), st);
-        }
-        HIPCHK(c, hipGetLastError());
-        rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &P1);
-    } else if (msd) {      // counts / offsets are [bucket][work item] tables: their exclusive scan IS the bucket-major layout, and every work item's
-        const uint64_t NS = NB * b->n_work;      // slots in it are its own.  The count pass writes every entry: nothing to clear
-        HIPCHK(c, c->ws[WS_COUNTS].ensure((NS + 1) * 4));
-        HIPCHK(c, c->ws[WS_SEGOFF].ensure((NS + 2) * 8));
-        HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(NS, b->n_res)) * 8 + 64));
-        HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-        {
-            // per residue: CA, flag and type of the filter (14 B), the source index, N and CB (28 B) and the frame it stores; + the table
-            StageTimer t(c, "pair_count", b->n_res * (14 + 28 + sizeof(fd_frame)) + NS * 4);
-            fd_launch_pair_count_msd(V, C, b->n_xyz, b->cb_xyz, c->ws[WS_SRC_PERM].as<uint32_t>(), c->ws[WS_FRAMES].p, c->ws[WS_COUNTS].as<uint32_t>(), st);
-        }
-        {
-            StageTimer t(c, "segment_scan", NS * 12);
-            fd_exclusive_scan<uint32_t>(c->ws[WS_COUNTS].as<uint32_t>(), NS, c->ws[WS_SEGOFF].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(),
-                                        c->ws[WS_TOTAL].as<uint64_t>(), st);
-        }
-        HIPCHK(c, hipGetLastError());
-        rc = d2h_u64(c, c->ws[WS_TOTAL].as<uint64_t>(), &P1);
-        uint64_t odd = 0;      // k_frames_perm met a residue type outside 0..19: no point in finishing this form of the build
-        if (!rc) rc = d2h_u64(c, (const uint64_t *)C.wide_flag, &odd);
-        if (!rc && odd) return FDGPU_RETRY_WIDE;
-    } else {
-        rc = count_and_scan(c, b, C, &P1, true);
-    }
-    if (rc) return rc;
-    P = P1 * n_cfg;                         // every bin pair of --multiple-bins contributes one key per ordered residue pair
-    // the MSD build addresses its keys with 64 bits (one call then covers 2^18 structures: ~8.7e9 keys of AFDB-shaped ones, 105 GB of sort
-    // workspace); the other paths keep 32-bit positions
-    if (P >= 0xffffffffull && !msd) FAIL(c, FDGPU_ERANGE, "more than 2^32 residue pairs in one build call; split the shard");
-    if (P >= (1ull << 35)) FAIL(c, FDGPU_ERANGE, "more than 2^35 residue pairs in one build call; split the shard");
-    if ((rc = ensure_sort_ws(c, P, el6 ? 2 : 4))) return rc;
-    uint32_t *ka = c->ws[WS_KEYS_A].as<uint32_t>(), *kb = c->ws[WS_KEYS_B].as<uint32_t>();
-    void *ia = c->ws[WS_IDS_A].p, *ib = c->ws[WS_IDS_B].p;
-    {
-        StageTimer t(c, "pair_emit", b->n_res * 37 + P * (el6 ? 6 : 8));
-        if (own) fd_launch_row_emit(b->view(), C, c->ws[WS_MISC1].as<uint64_t>(), ka, p->dist_cutoff, (uint32_t *)ia, (uint32_t)first_id, st);
-        else if (msd) fd_launch_pair_emit_msd(V, c->ws[WS_FRAMES].p, C, c->ws[WS_SEGOFF].as<uint64_t>(), ka, (uint16_t *)ia, st);
-        else for (uint32_t k = 0; k < n_cfg; ++k) {
-            fd_hash_consts Ck = fd_make_consts_cfg(p, k);
-            Ck.spec_miss = C.spec_miss; Ck.wide_flag = C.wide_flag; Ck.seg_mul = n_cfg; Ck.seg_cfg = k;
-            if (k) HIPCHK(c, hipMemsetAsync(c->ws[WS_CURSOR].p, 0, (S + 1) * 4, st));
-            fd_launch_pair_emit2(b->view(), c->ws[WS_FRAMES].p, Ck, c->ws[WS_SEGOFF].as<uint64_t>(), c->ws[WS_CURSOR].as<uint32_t>(), ka, ia, ids16,
-                                 (uint32_t)first_id, st);
-        }
-    }
-    int cur;
-    if (msd) {      // every bucket by hash bits [0, 24): three passes (hash[7:0] = u32 plane bits 31:24, hash[23:8] = the u16 plane); the bucket holds the other six
-        static const fd_rs_digit digits[3] = {{0, 24}, {1, 0}, {1, 8}};
-        HIPCHK(c, c->ws[WS_GHIST].ensure((size_t)256 * fd_rs_seg_num_tiles(P, NB) * 4));
-        HIPCHK(c, c->ws[WS_TOT].ensure(fd_rs_seg_tot_words(P, NB) * 8));
-        HIPCHK(c, c->ws[WS_SEG_TAB].ensure(fd_rs_seg_tab_bytes(P, NB)));
-        cur = fd_radix_sort_pairs16_seg(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, c->ws[WS_SEGOFF].as<uint64_t>(), b->n_work, NB, digits, 3, c->ws[WS_GHIST].as<uint32_t>(),
-                                        c->ws[WS_TOT].as<uint64_t>(), c->ws[WS_SEG_TAB].p, st, c, c->ws[WS_MISC3].as<unsigned long long>() + 4);
-    } else if (ids16) cur = fd_radix_sort_pairs16(ka, (uint16_t *)ia, kb, (uint16_t *)ib, P, 32, c->ws[WS_GHIST].as<uint32_t>(), c->ws[WS_TOT].as<uint64_t>(), st, c);
-    else cur = sort_pairs(c, ka, (uint32_t *)ia, kb, (uint32_t *)ib, P, 32);   // all 32 bits: unmasked field overflow can set bits 30-31
-    const uint32_t *ks = cur ? kb : ka;
-    const void *is = cur ? ib : ia;
-    return encode_sorted_stream(c, ks, is, codec, first_id, P, S, msd ? b->n_work : 0, out);
-}
-
-extern "C" int fdgpu_index_build(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, uint64_t first_id, fdgpu_index **out) { FD_LOCK(c);
-    const char *e32 = getenv("FDGPU_IDS32");   // FDGPU_IDS32=1 forces the 8-byte sort elements (read per call: tests flip it)
-    int rc = index_build_impl(c, b, p, first_id, out, e32 && e32[0] == '1');
-    if (rc == FDGPU_RETRY_WIDE) rc = index_build_impl(c, b, p, first_id, out, true);
-    return rc;
-}
-
-// Test-only (include/fdgpu_debug.h): the encoder alone on a caller-made stream, 8-byte elements (codec 0).
-extern "C" int fdgpu_debug_encode_stream(fdgpu_ctx *c, const uint32_t *hashes, const uint32_t *ids, uint64_t n, fdgpu_index **out) { FD_LOCK(c);
-    if (!c || !out || (n && (!hashes || !ids))) return FDGPU_EINVAL;
-    *out = nullptr;
-    if (n >= 0xffffffffull) FAIL(c, FDGPU_ERANGE, "encode_stream: 2^32 elements or more");
-    uint64_t S = 0;
-    for (uint64_t p = 0; p < n; ++p) {
-        if (p && (hashes[p - 1] > hashes[p] || (hashes[p - 1] == hashes[p] && ids[p - 1] > ids[p]))) FAIL(c, FDGPU_EINVAL, "encode_stream: the stream is not sorted by (hash, id)");
-        S = std::max<uint64_t>(S, (uint64_t)ids[p] + 1);
-    }
-    reset_timings(c);
-    hipStream_t st = c->stream;
-    HIPCHK(c, c->ws[WS_MISC3].ensure(512));
-    HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC3].p, 0, 64, st));
-    HIPCHK(c, c->ws[WS_KEYS_A].ensure(std::max<uint64_t>(n, 1) * 4));
-    HIPCHK(c, c->ws[WS_IDS_A].ensure(std::max<uint64_t>(n, 1) * 4));
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(c->ws[WS_KEYS_A].p, hashes, n * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->ws[WS_IDS_A].p, ids, n * 4, hipMemcpyHostToDevice, st));
-    }
-    return encode_sorted_stream(c, c->ws[WS_KEYS_A].as<uint32_t>(), c->ws[WS_IDS_A].p, 0, 0, n, S, 0, out);
-}
-// Test-only: the same on the 6-byte elements of the MSD build's stream (codec 2), packed here on the host; the 41 bucket starts go to WS_SEGOFF at stride 1.
-// The stream is checked before the context is looked at: without one (ctx NULL) the call is those checks alone, which a test without a device can reach.
-extern "C" int fdgpu_debug_encode_stream_b24(fdgpu_ctx *c, const uint32_t *hashes, const uint32_t *local_ids, uint64_t n, uint64_t first_id, fdgpu_index **out) { FD_LOCK(c);
-    if (!out || (n && (!hashes || !local_ids))) return FDGPU_EINVAL;
-    *out = nullptr;
-    const uint32_t NB = 40;
-    uint64_t S = 0;
-    const char *why = n >= 0xffffffffull ? "encode_stream_b24: 2^32 elements or more" : nullptr;
-    for (uint64_t p = 0; p < n && !why; ++p) {
-        const uint32_t h = hashes[p], id = local_ids[p];
-        if (h >= (1u << 30) || (h >> 24) >= NB) why = "encode_stream_b24: a hash of 2^30 or more, or in a bucket (hash >> 24) of 40 or more";
-        else if (id >= (1u << 24)) why = "encode_stream_b24: a local id of 2^24 or more";
-        else if (p && (hashes[p - 1] > h || (hashes[p - 1] == h && local_ids[p - 1] > id))) why = "encode_stream_b24: the stream is not sorted by (hash, id)";
-        S = std::max<uint64_t>(S, (uint64_t)id + 1);
-    }
-    if (!why && first_id + S > 0xffffffffull) why = "encode_stream_b24: structure ids exceed 32 bits";
-    if (why) { if (c) c->err = why; return FDGPU_EINVAL; }
-    if (!c) return FDGPU_OK;
-    std::vector<uint32_t> k32(std::max<uint64_t>(n, 1));
-    std::vector<uint16_t> v16(std::max<uint64_t>(n, 1));
-    std::vector<uint64_t> seg(NB + 2, 0);      // seg[b + 1] counts bucket b, then the running sum: seg[b] = where bucket b starts, seg[40] = n
-    for (uint64_t p = 0; p < n; ++p) {
-        const uint32_t h = hashes[p];
-        k32[p] = (h & 0xffu) << 24 | local_ids[p];
-        v16[p] = (uint16_t)(h >> 8);
-        ++seg[(h >> 24) + 1];
-    }
-    for (uint32_t b = 0; b < NB; ++b) seg[b + 1] += seg[b];
-    reset_timings(c);
-    hipStream_t st = c->stream;
-    HIPCHK(c, c->ws[WS_MISC3].ensure(512));
-    HIPCHK(c, hipMemsetAsync(c->ws[WS_MISC3].p, 0, 64, st));
-    HIPCHK(c, c->ws[WS_KEYS_A].ensure(k32.size() * 4));
-    HIPCHK(c, c->ws[WS_IDS_A].ensure(v16.size() * 2));
-    HIPCHK(c, c->ws[WS_SEGOFF].ensure((NB + 2) * 8));
-    HIPCHK(c, hipMemcpyAsync(c->ws[WS_SEGOFF].p, seg.data(), (NB + 1) * 8, hipMemcpyHostToDevice, st));
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(c->ws[WS_KEYS_A].p, k32.data(), n * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->ws[WS_IDS_A].p, v16.data(), n * 2, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(c, hipStreamSynchronize(st));      // the host vectors go out of scope with this call
-    return encode_sorted_stream(c, c->ws[WS_KEYS_A].as<uint32_t>(), c->ws[WS_IDS_A].p, 2, first_id, n, S, 1, out);
-}
 
 // A large device-to-host copy into ordinary (pageable) memory.  The runtime's own path stages through one internal buffer and one
 // host thread (~12 GB/s: 2.2 s for the 26 GB of a Swiss-Prot-scale index); here FD_PIN_SLOTS pinned buffers are filled by

@@ -632,7 +632,7 @@ __global__ void k_selfcheck(fd_quant q, uint32_t *__restrict__ out /*[24]*/) {
     }
 }
 
-// ------------------------------------------------------------------ launchers (called from fdgpu_api.hip)
+// ------------------------------------------------------------------ launchers (called from fd_api_build.hip)
 extern "C++" {
 void fd_launch_selfcheck(const fd_quant &q, uint32_t *out, hipStream_t st) { hipLaunchKernelGGL(k_selfcheck, dim3(1), dim3(64), 0, st, q, out); }
 void fd_launch_hash_ok(const uint8_t *aa, const uint8_t *cb_valid, uint8_t *ok, uint64_t n, hipStream_t st) {

@@ -10,7 +10,7 @@
 // Two streaming passes over the sorted pairs (sizes, then write), HBM-bound.
 //
 // Precondition of the MSD stream (codec 2, B24 below): inside every one of the forty buckets the u16 plane (hash[23:8]) is non-decreasing.  The
-// segmented sort guarantees it (fd_radix_sort_pairs16_seg, k_sort.hip, with the digit order of the build, fdgpu_api.hip: hash[7:0], then the u16
+// segmented sort guarantees it (fd_radix_sort_pairs16_seg, k_sort.hip, with the digit order of the build, fd_api_build.hip: hash[7:0], then the u16
 // plane's low byte, then its high byte LAST, each pass stable), and fdgpu_debug_encode_stream_b24 checks it of a caller's stream.  Both passes
 // rely on it: a tile of ENC_TILE elements that lies in one bucket, predecessor element included, and whose two end elements carry the same u16
 // value holds that value everywhere, so such a tile reads two elements of the plane and not its 4 KB (enc_b24::cst).  The two passes take the

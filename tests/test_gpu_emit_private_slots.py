@@ -1,4 +1,4 @@
-"""The MSD index build's slot tables (k_hash.hip: k_pair_count_msd, k_pair_emit2<.., MSD>; fdgpu_api.hip: index_build_impl).  The count pass
+"""The MSD index build's slot tables (k_hash.hip: k_pair_count_msd, k_pair_emit2<.., MSD>; fd_api_build.hip: ib_count_msd, ib_emit_msd).  The count pass
 writes counts[bucket][work item] for all forty buckets of every work item (a work item = one 64-residue tile of a structure in amino-acid
 order), zeros included and without clearing the table first; the exclusive scan of the table gives every work item private, contiguous slots
 in every bucket, and the emit pass fills them from a cursor in LDS.  The frames are built by the count work item that owns the tile, through
