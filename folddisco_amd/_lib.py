@@ -257,6 +257,8 @@ SYMBOLS = [
     ("fdgpu_debug_hash_is_symmetric", C.c_int, [C.c_uint32, u32p, C.c_uint64, u8p]),
     ("fdgpu_debug_host_retrieve_slot", C.c_int, [u32p, u32p, u32p, C.c_uint64, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.POINTER(QueryMap), C.c_uint32, C.c_uint32,
                                                  C.c_uint32, C.c_uint32, u64p, C.POINTER(f32p), C.POINTER(u32p), C.POINTER(C.POINTER(C.c_int32))]),
+    ("fdgpu_debug_match_tables", C.c_int, [C.c_uint64, C.POINTER(MatchQuery), u32p, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u32p), u64p, u64p,
+                                           C.POINTER(C.c_char_p)]),
     ("fdgpu_debug_merge_retrieved", C.c_int, [VP, C.c_uint32, C.c_uint64, u64p, C.POINTER(C.POINTER(MatchRec)), C.POINTER(C.POINTER(C.c_int32)), u64p,
                                               C.POINTER(C.POINTER(MatchRec)), C.POINTER(u64p), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(u64p)]),
 ]

@@ -266,10 +266,11 @@ static int rb_device_glue(const rb_in &I, const rb_out &out, bool *done, fd_rb_d
     rs_layout L;
     rs_plan R;
     std::vector<uint32_t> blk_own;
-    fd_pair_rec *f_none = nullptr; fd_cand_rec *c_none = nullptr;      // mode bit 4: the records stay on the device
+    fd_pair_rec *f_none = nullptr; fd_cand_rec *c_none = nullptr;      // MP_ON_DEVICE: the records stay on the device
     const std::function<void()> pack_tables = [&]() { L = rs_pack_tables(I, blk_own); };
-    int rc = fd_match_pairs_multi(c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &f_none, &R.nf_d, &c_none, &R.nc_d, 19u, nullptr, nullptr, 0,
-                                  nullptr, nullptr, nullptr, nullptr, &pack_tables);
+    fd_mp_request rq;
+    rq.mode = MP_FOUND | MP_CANDS | MP_ON_DEVICE; rq.while_scanning = &pack_tables;
+    int rc = fd_match_pairs_multi(c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &f_none, &R.nf_d, &c_none, &R.nc_d, rq);
     if (rc) return rc;
     if (!L.blk) pack_tables();
     const rb_time D1 = t_now();
@@ -298,7 +299,7 @@ struct rb_form {
     uint32_t path() const { return (two_pass ? FDGPU_RPATH_TWO_PASS : 0u) | (dev_glue ? FDGPU_RPATH_DEVICE_TRIED : 0u); }
 };
 // a pair scan's output on the host: found / cands are the call's own until the slots are processed (freed here on every return path);
-// pk_key / pk_val (packed, device-sorted candidate pairs, fd_match_pairs_multi mode bit 3) are the context's pinned buffers, not ours to free
+// pk_key / pk_val (packed, device-sorted candidate pairs, fd_match_pairs_multi with MP_CANDS_PACKED) are the context's pinned buffers, not ours to free
 struct rb_scan {
     fd_pair_rec *found = nullptr; fd_cand_rec *cands = nullptr; uint64_t nf = 0, nc = 0; uint32_t *pk_key = nullptr, *pk_val = nullptr;
     rb_scan() {}
@@ -316,7 +317,7 @@ struct rb_helper { std::thread t; void join() { if (t.joinable()) t.join(); } ~r
 struct rb_coords { std::vector<float> qb_ca, qb_cb, t_all; std::vector<uint64_t> g_dst, q_res0; uint64_t g_total = 0; };
 // per-slot arrays of the slot passes: slot -> query, the ranges of the scan output at hand, the plan pass's mappings (two-pass calls)
 struct rb_slots { std::vector<uint32_t> slot_q, mask_off; std::vector<size_t> f_lo, c_lo; std::vector<fd_rh_slot_plan> plans; };
-// rescue votes counted on the device (second scan, fd_match_pairs_multi mode bit 5): rows of (largest count, holders, which) per (slot, ordinal,
+// rescue votes counted on the device (second scan, fd_match_pairs_multi with MP_VOTES): rows of (largest count, holders, which) per (slot, ordinal,
 // query residue) come back instead of the candidate pairs
 struct rb_votes { std::vector<uint64_t> row_base; std::vector<fd_vote_row> rows; bool have = false; };
 }  // namespace
@@ -340,8 +341,10 @@ static int rb_first_scan(const rb_in &I, const rb_form &F, rb_helper_tabs &H, rb
         const fd_rb_prep *prep = I.prep; const uint64_t n_queries = I.n_queries; const fd_query_map *const *qms = I.qms; const bool two_pass = F.two_pass;
         helper.t = std::thread([prep, n_queries, qms, two_pass, &H]() { fd_rh_build_e_tab(*prep, H.tabs); if (two_pass) fd_rh_build_sorted_lists(n_queries, qms, H.sd_dist, H.sd_qi); });
     }
-    return fd_match_pairs_multi(I.c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &S.found, &S.nf, &S.cands, &S.nc, F.two_pass ? 1u : 15u,
-                                nullptr, nullptr, 0, &S.pk_key, &S.pk_val, nullptr, &mp_tab);
+    fd_mp_request rq;
+    rq.mode = F.two_pass ? MP_FOUND : MP_FOUND | MP_CANDS | MP_CANDS_UNORDERED | MP_CANDS_PACKED;
+    rq.pk_key = &S.pk_key; rq.pk_val = &S.pk_val; rq.tables = &mp_tab;
+    return fd_match_pairs_multi(I.c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &S.found, &S.nf, &S.cands, &S.nc, rq);
 }
 
 // stage 5
@@ -421,8 +424,10 @@ static int rb_scan_device_votes(const rb_in &I, const rb_coords &X, const rb_hel
     vp.row_off = row_off.data(); vp.row_len = row_len.data(); vp.n_rows = n_rows; vp.rows = V.rows.data();
     vp.sd_dist = H.sd_dist.empty() ? nullptr : H.sd_dist.data(); vp.sd_qi = H.sd_qi.empty() ? nullptr : H.sd_qi.data(); vp.n_sd = H.sd_dist.size();
     rb_scan S2;      // nothing of it is kept: the rows are the result
-    const int rc = fd_match_pairs_multi(I.c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &S2.found, &S2.nf, &S2.cands, &S2.nc, 32u, M.cj_mask.data(),
-                                        mask_off.data(), M.cj_mask.size(), nullptr, nullptr, &vp, &mp_tab);
+    fd_mp_request rq;
+    rq.mode = MP_VOTES; rq.votes = &vp; rq.tables = &mp_tab;
+    rq.cj_mask = M.cj_mask.data(); rq.mask_off = mask_off.data(); rq.mask_words = M.cj_mask.size();
+    const int rc = fd_match_pairs_multi(I.c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &S2.found, &S2.nf, &S2.cands, &S2.nc, rq);
     if (rc) return rc;
     V.have = true;
     return FDGPU_OK;
@@ -430,8 +435,10 @@ static int rb_scan_device_votes(const rb_in &I, const rb_coords &X, const rb_hel
 // stage 7, the host form: the candidate pairs of the marked partner residues come back (packed when the scan can) for the slots to count
 static int rb_scan_host_rescue(const rb_in &I, const fd_rh_marks &M, const std::vector<uint32_t> &mask_off, fd_mp_tables &mp_tab, rb_scan &S) {
     rb_scan S2;
-    const int rc = fd_match_pairs_multi(I.c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &S2.found, &S2.nf, &S2.cands, &S2.nc, 14u, M.cj_mask.data(),
-                                        mask_off.data(), M.cj_mask.size(), &S.pk_key, &S.pk_val, nullptr, &mp_tab);
+    fd_mp_request rq;
+    rq.mode = MP_CANDS | MP_CANDS_UNORDERED | MP_CANDS_PACKED; rq.pk_key = &S.pk_key; rq.pk_val = &S.pk_val; rq.tables = &mp_tab;
+    rq.cj_mask = M.cj_mask.data(); rq.mask_off = mask_off.data(); rq.mask_words = M.cj_mask.size();
+    const int rc = fd_match_pairs_multi(I.c, I.db, I.resname_std, I.n_queries, I.prep->mqs.data(), I.cand, I.cand_off, I.p, &S2.found, &S2.nf, &S2.cands, &S2.nc, rq);
     std::swap(S.cands, S2.cands); S.nc = S2.nc;      // (S.cands was dropped before the scan: S2 leaves with nothing but its found triples)
     return rc;
 }

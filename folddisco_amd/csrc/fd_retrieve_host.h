@@ -76,7 +76,7 @@ struct fd_rh_call {
     bool trace = false;
     std::chrono::steady_clock::time_point stage_t0;                              // for the trace lines of heavy slots
     // the scans' output, grouped by slot: found triples [f_lo[slot], f_lo[slot + 1]); candidate pairs [c_lo ...) either as records or packed
-    // (key = slot << 16 | partner residue j, sorted; value = qi << 16 | i; fd_match_pairs_multi mode bit 3)
+    // (key = slot << 16 | partner residue j, sorted; value = qi << 16 | i; fd_match_pairs_multi with MP_CANDS_PACKED)
     const fd_pair_rec *found = nullptr; const fd_cand_rec *cands = nullptr; const uint32_t *pk_key = nullptr, *pk_val = nullptr;
     const size_t *f_lo = nullptr, *c_lo = nullptr;
     // coordinates: the candidates' [CA of all | CB of all], slot k at residue g_dst[k]; the query structures' CA / CB, query t at residue q_res0[t]

@@ -12,59 +12,8 @@
 #include "fd_geom_other.h"
 #include "fd_retrieve_host.h"
 
-#include <condition_variable>
-#include <thread>
-// A context's host helper threads (the per-candidate glue of whole-structure retrievals, fd_host_query.hip): started once, woken per job — spawning
-// nineteen std::threads per pass cost ~1 ms of a 10 ms retrieval.  run(n, f): f() on n - 1 pool threads and on the caller, returns when all are done.
-struct fd_host_pool {
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv, cv_done;
-    const std::function<void()> *job = nullptr;
-    uint64_t gen = 0;
-    unsigned want = 0, taken = 0, active = 0;
-    bool stop = false;
-    void loop() {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void()> *f = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || (gen != seen && taken < want); });
-                if (stop) return;
-                seen = gen; ++taken; f = job;
-            }
-            (*f)();
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                --active;
-            }
-            cv_done.notify_one();
-        }
-    }
-    void run(unsigned n, const std::function<void()> &f) {
-        if (n <= 1) { f(); return; }
-        const unsigned helpers = n - 1;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            while (th.size() < helpers) th.emplace_back([this] { loop(); });
-            job = &f; want = helpers; taken = 0; active = helpers; ++gen;
-        }
-        cv.notify_all();
-        f();
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return active == 0; });
-        job = nullptr;
-    }
-    ~fd_host_pool() {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            stop = true;
-        }
-        cv.notify_all();
-        for (auto &t : th) t.join();
-    }
-};
+#include "fd_host_pool.h"
+#include "fd_match_tables.h"
 
 struct fd_devbuf {
     void *p = nullptr;
@@ -444,16 +393,17 @@ void fd_launch_cq_seg(const cq_args &A, const long long *kidx, const uint64_t *w
 void fd_launch_cq_rows_finalize(const cq_args &A, const uint64_t *q_rows, uint32_t n_queries, const uint64_t *slices, uint32_t n_slices, uint32_t *node_cnt,
                                 uint32_t *edge_cnt, uint8_t *flags, uint64_t max_rows_per_query, hipStream_t st);
 
-// k_match.hip
-struct mp_query_dev {   // per-query table of the pair scan (many queries in one launch)
-    uint32_t qh_off, n_hashes;   // sorted unique hashes: q_hashes[qh_off .. +n_hashes)
-    uint32_t aad_off, n_aad;     // grouped aa_dist_map: aad_dist / aad_qi [aad_off .. +n_aad); start table aad_start[1025 * query]
-    uint32_t aa1_mask, aa2_mask; // residue types of the hashes' first / second residue (prefilter_amino_acid)
-    int use_prefilter;
-    float ca_window;
-    uint32_t qs_off, qs_mask;    // more than MP_QH_LDS hashes: an open-addressing set of them, qset[qs_off .. + qs_mask + 1) (0xffffffff = empty); qs_mask = 0: none
+// k_match.hip (mp_query_dev and the host block fd_mp_tables: fd_match_tables.h)
+// What a pair scan emits and where it leaves it (mp_args.mode, fd_mp_request.mode).  The legal combinations: mp_choose_form (fd_api_match.hip).
+enum : uint32_t {
+    MP_FOUND = 1u,               // emit found triples
+    MP_CANDS = 2u,               // emit candidate pairs
+    MP_CANDS_UNORDERED = 4u,     // the caller buckets the candidate pairs itself and does not depend on their order
+    MP_CANDS_PACKED = 8u,        // candidate pairs come back packed (two words each) and sorted on the device, where the scan can (fd_mp_request.pk_key / pk_val)
+    MP_ON_DEVICE = 16u,          // the records stay on the device (ws[WS_KEYS_A] / ws[WS_KEYS_B], append order); only the counts return
+    MP_VOTES = 32u               // rescue votes counted on the device: the vote rows return instead of candidate pairs (fd_vote_plan)
 };
-#define MP_QH_LDS 1024          /* query hashes a drain copies into LDS for its membership test; larger sets are probed in their hash table (qset) */
+#define MP_QH_LDS 1024          /* query hashes a drain copies into LDS for its membership test; larger sets are probed in their hash table (qset); also in fd_match_tables.h */
 #define MP_SUBQ_STRIDE 16u      /* u64 words between the pair queue's sub-queue counters (one 128-byte line each) */
 struct mp_args {
     fd_batch_view B;
@@ -486,24 +436,17 @@ struct mp_args {
     unsigned long long cap_found, cap_cands;   // records the buffers hold (EMIT counts beyond them without writing)
     uint32_t n_cfg;                // --multiple-bins: bin pairs to hash every surviving pair with (1 = the single configuration in C)
     fd_quant qk[8];                // their quantisers (qk[0] == C.q)
-    uint32_t mode;                 // bit 0: emit found triples, bit 1: emit candidate pairs
+    uint32_t mode;                 // MP_* bits; the kernels read MP_FOUND, MP_CANDS and MP_VOTES
     const uint32_t *cj_mask;       // optional: only partner residues j whose bit mask_off[slot] + (j - r0) is set are scanned
     const uint32_t *mask_off;      // [n_cand] first bit of every candidate slot
-    // mode bit 5 (rescue votes on the device, second scan of a large query): instead of leaving the kernel, a candidate pair (qi, i, j) adds one
+    // MP_VOTES (rescue votes on the device, second scan of a large query): instead of leaving the kernel, a candidate pair (qi, i, j) adds one
     // to votes[vt_off[slot] + ((cj_comp[bit of j] - 1) * vt_qs[slot] + qi) * n_residues(slot) + i] — the table retrieve.rs:498-511 builds per component
     uint32_t *votes; const uint64_t *vt_off; const uint32_t *vt_qs; const uint8_t *cj_comp;
     const float *sd_dist; const uint32_t *sd_qi;      // optional, vote mode: every group's observed (distance, query residue) list sorted by distance
 };
-// rescue votes of a large query's second scan (fd_match_pairs_multi, mode bit 5).  In: per marked partner residue (bit position as in cj_mask) the
+// rescue votes of a large query's second scan (fd_match_pairs_multi, MP_VOTES).  In: per marked partner residue (bit position as in cj_mask) the
 // 1-based ordinal of the component that mapped it, per slot the first counter and the query's residue count, the table's size in counters.
 // Out: per (slot, ordinal, query residue) row of the table {largest count, number of target residues holding it, one of them}.
-// host block of a pair scan's work items and query tables (fd_match_pairs_multi builds it on the first call, reuses it on the next)
-struct fd_mp_tables {
-    std::vector<uint32_t> blk; size_t o[13] = {0}; size_t nw = 0; bool want_iv = false; uint32_t j_span = 0; bool valid = false;
-    const uint32_t *data = nullptr; size_t words = 0;      // the packed block: blk, or (tables not kept by the caller) the context's pinned staging buffer
-    bool dev_items = false; size_t o_wb = 0;                // work items written on the device from [first item | query] per candidate at o_wb (one-off blocks)
-    uint64_t qset_slots = 0, qset_max_hashes = 0;           // slots of the large queries' hash sets (mp_query_dev.qs_off / qs_mask), their largest hash count
-};
 // work items of the pair scan: candidate k (structure cand[k], first item wbase[k], query cq[k]) -> one item per (64-residue tile, span of j_span partners)
 void fd_launch_mp_items(const uint32_t *db_res_off, const uint32_t *cand, uint32_t n_cand, const uint32_t *wbase, const uint32_t *cq, uint32_t j_span, uint32_t *wc,
                         uint32_t *wi, uint32_t *wq, uint32_t *wj, hipStream_t st, const uint8_t *aa, const uint8_t *hash_ok, const uint8_t *resname_std, int tert,
@@ -516,6 +459,15 @@ struct fd_vote_plan {
     // optional: the queries' observed-distance lists in the scan's group layout (aad_start offsets), every group sorted by distance — the
     // entries inside a pair's window are then one contiguous run (fl(d - x) is monotone in x) instead of a walk over the whole group
     const float *sd_dist; const uint32_t *sd_qi; uint64_t n_sd;
+};
+// what a caller of fd_match_pairs_multi may ask for beyond the plain scan (found triples and candidate pairs to the host, both sorted)
+struct fd_mp_request {
+    uint32_t mode = MP_FOUND | MP_CANDS;
+    const uint32_t *cj_mask = nullptr, *mask_off = nullptr; uint64_t mask_words = 0;      // partner-residue filter (second scan of a large query): mask_off per slot
+    uint32_t **pk_key = nullptr, **pk_val = nullptr;      // MP_CANDS_PACKED: the context's pinned buffers (valid until its next packed scan, never freed by the caller); null = not packed
+    fd_vote_plan *votes = nullptr;                        // MP_VOTES
+    fd_mp_tables *tables = nullptr;                       // kept by a caller that scans the same candidates twice: built by the first call, reused by the second
+    const std::function<void()> *while_scanning = nullptr;      // host work of the caller that does not need the scan's result — run once, between the scan's launch and the wait for it
 };
 void fd_launch_vote_rows(const uint32_t *votes, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, fd_vote_row *out, hipStream_t st);
 void fd_launch_match_pairs(const mp_args &A, hipStream_t st);
@@ -594,7 +546,4 @@ void fd_launch_rs_records_dev(const void *matches, uint64_t n, const uint32_t *s
                               const float *rot, const float *tran, const float *met, const int32_t *residues, void *out, int32_t *out_res, hipStream_t st);
 int fd_match_pairs_multi(fdgpu_ctx *c, const fdgpu_batch *db, const uint8_t *resname_std, uint64_t n_queries, const fd_match_query *qs,
                          const uint32_t *cand, const uint64_t *cand_off, const fd_hash_params *p, fd_pair_rec **found, uint64_t *n_found,
-                         fd_cand_rec **cands, uint64_t *n_cands, uint32_t mode = 3, const uint32_t *cj_mask = nullptr,
-                         const uint32_t *mask_off = nullptr, uint64_t mask_words = 0, uint32_t **pk_key = nullptr, uint32_t **pk_val = nullptr,
-                         fd_vote_plan *votes = nullptr, struct fd_mp_tables *tables = nullptr, const std::function<void()> *while_scanning = nullptr);
-// (while_scanning: host work of the caller that does not need the scan's result — run once, between the scan's launch and the wait for it)
+                         fd_cand_rec **cands, uint64_t *n_cands, const fd_mp_request &rq = fd_mp_request());

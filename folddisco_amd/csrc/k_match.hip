@@ -77,18 +77,18 @@ __device__ __forceinline__ void match_drain(const mp_args &A, const mp_sel &Sx, 
         d = fd_dist(cai, caj);
         key = (aai & 31u) * 32u + (aaj & 31u);   // queued pairs have aa < 32
         e_lo = st_tab[key]; e_hi = st_tab[key + 1];
-        if (A.mode & 2u)      // the observed-distance window only feeds the candidate pairs: a found-only scan (first pass of a large query) skips it
+        if (A.mode & MP_CANDS)      // the observed-distance window only feeds the candidate pairs: a found-only scan (first pass of a large query) skips it
             for (uint32_t e = e_lo; e < e_hi; ++e) n_win += (fd_fabsf(d - dist_tab[e]) < Sx.ca_window) ? 1u : 0u;
         if (fd_own_descriptor(A.C.q.type)) {
             // encodings with their own descriptor: the pair may still have no feature (CB / point-pair distance, chain ends)
             float f9[FD_NFEAT];
             if (fd_feature_other(A.C.q.type, A.B, r0, r1, i, j, A.cutoff, f9)) {
                 h = fd_hash_other(A.C.q.type, f9, A.C.q);
-                hitmask = ((A.mode & 1u) && in_query(h)) ? 1u : 0u;
+                hitmask = ((A.mode & MP_FOUND) && in_query(h)) ? 1u : 0u;
             } else {
                 n_win = 0; has_feat = false;
             }
-        } else if (!(A.mode & 1u)) {
+        } else if (!(A.mode & MP_FOUND)) {
             // no found triples wanted (second scan of a large query): the PDBTrRosetta descriptor of a pair that passed hash_ok always exists
         } else if (A.C.use_tab && A.n_cfg == 1) {
             // default angle bins: frames + exhaustive tables (fd_geom.h) — same bits as the generic chain, a tenth of the code
@@ -98,7 +98,7 @@ __device__ __forceinline__ void match_drain(const mp_args &A, const mp_sel &Sx, 
             // the index build's speculative evaluation (fd_pair_both_spec: table lookups on the dot products, exact whenever it answers) with
             // the exact table form behind it for the pairs it declines — the same frames, so the same bits as the build's keys
             if (A.C.use_tab < 2 || !fd_pair_both_spec(Fi, Fj, aai, aaj, A.C.q, tab, tab + 32, &h, &h_ji)) fd_pair_both_tab(Fi, Fj, aai, aaj, A.C.q, tab, &h, &h_ji);
-            hitmask = ((A.mode & 1u) && in_query(h)) ? 1u : 0u;
+            hitmask = ((A.mode & MP_FOUND) && in_query(h)) ? 1u : 0u;
         } else {
             // one descriptor, one hash per bin pair (--multiple-bins: a found triple for every bin pair whose hash the query holds,
             // retrieve.rs:124-131)
@@ -106,12 +106,12 @@ __device__ __forceinline__ void match_drain(const mp_args &A, const mp_sel &Sx, 
             for (uint32_t k = 0; k < A.n_cfg; ++k) {
                 const uint32_t hk = fd_hash_enc(aai, aaj, feat, A.qk[k]);
                 if (k == 0) h = hk;
-                if ((A.mode & 1u) && in_query(hk)) hitmask |= 1u << k;
+                if ((A.mode & MP_FOUND) && in_query(hk)) hitmask |= 1u << k;
             }
         }
-        if (!(A.mode & 2u)) n_win = 0;
+        if (!(A.mode & MP_CANDS)) n_win = 0;
     }
-    if ((A.mode & 32u) && on && has_feat) {
+    if ((A.mode & MP_VOTES) && on && has_feat) {
         // rescue votes on the device: the pair's records (one per observed distance in the window) count into the table of the component
         // that mapped the partner residue j
         const uint32_t comp = A.cj_comp[A.mask_off[slot] + (j - r0)], nq = A.vt_qs[slot], nr = r1 - r0;

@@ -65,6 +65,17 @@ int fdgpu_debug_host_retrieve_slot(const uint32_t *found_i, const uint32_t *foun
                                    uint32_t hash_type, uint32_t node_count, uint32_t two_pass, uint32_t packed, uint64_t *n_recs, float **idf,
                                    uint32_t **same, int32_t **residues);
 
+/* The host block a pair scan (fdgpu_match_pairs and the retrieval's scans) sends to the device before its first launch (csrc/fd_match_tables.cpp), built
+ * without a device: query t scans the structures cand[cand_off[t] .. cand_off[t + 1]) of a batch of n_struct structures whose residues start at
+ * res_off[0 .. n_struct] (only lengths are read).  dev_items != 0: the form whose work items the device writes (every candidate's first item and query),
+ * else the four host-built item arrays.  pooled != 0: interval tables of queries with 8,192 observed distances and more on helper threads.
+ * Out: *block = the packed block (padding zeroed; libc free()), layout[16] = the word offsets of its sections {cand, wc, wi, wq, wj, hashes, start,
+ * dist, qi, qtab, iv_start, iv, iv_grp, wbase, cq} and its length in words, scalars[5] = {work items, j_span, interval tables built, hash-set slots,
+ * largest hash count of a query with a set}.  On FDGPU_EINVAL / FDGPU_ERANGE *message is the text the scan would leave as the context's error. */
+int fdgpu_debug_match_tables(uint64_t n_queries, const fd_match_query *qs, const uint32_t *cand, const uint64_t *cand_off, const uint64_t *res_off,
+                             uint64_t n_struct, uint32_t hash_type, uint32_t dev_items, uint32_t pooled, uint32_t **block, uint64_t *layout,
+                             uint64_t *scalars, const char **message);
+
 /* Which form the LAST count call on this context took (fdgpu_count_query, fdgpu_count_query_batch[_top], fdgpu_count_query_maps_top): the
  * booleans its dispatch computed, one bit each, so that a test at one of the dispatch's switches can tell which side it landed on.
  * OVERFLOW: the device selection met more ties at a cut than it holds and the call was ranked again by the compacting path — the other bits then
