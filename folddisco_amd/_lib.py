@@ -249,6 +249,15 @@ SYMBOLS = [
     ("fdgpu_debug_libm", C.c_int, [VP, C.c_int, f32p, f32p, f32p, C.c_uint64]),
     ("fdgpu_debug_last_count_path", C.c_int, [VP, u32p]),
     ("fdgpu_debug_last_retrieve_path", C.c_int, [VP, u32p]),
+    ("fdgpu_debug_last_query_map_path", C.c_int, [VP, u32p]),
+    ("fdgpu_debug_qm_pairs", C.c_int, [C.c_uint64, u32p, u64p, u32p, u64p, C.POINTER(u32p), C.POINTER(u32p), u64p]),
+    ("fdgpu_debug_qm_fields", C.c_int, [C.c_uint32, C.POINTER(C.c_int32)]),
+    ("fdgpu_debug_qm_expand", C.c_int, [f32p, u8p, u32p, u32p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, C.POINTER(u8p), u32p, C.c_uint32, f32p, C.c_uint64, f32p,
+                                        C.c_uint64, C.POINTER(f32p), C.POINTER(u32p), u64p]),
+    ("fdgpu_debug_qm_first_insertions", C.c_int, [u32p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(u32p), u64p]),
+    ("fdgpu_debug_qm_arena", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, u64p]),
+    ("fdgpu_debug_qm_fill", C.c_int, [u32p, C.c_uint64, u32p, C.c_uint64, C.c_uint32, C.c_uint64, u32p, u32p, C.c_uint64, u32p, u32p, C.c_uint64, f32p, u32p, u64p, u32p,
+                                      C.POINTER(C.c_longlong), C.c_uint64, u32p, C.c_uint64, u8p, u8p, f32p, u32p, C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(QueryMap))]),
     ("fdgpu_debug_encode_stream", C.c_int, [VP, u32p, u32p, C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_debug_encode_stream_b24", C.c_int, [VP, u32p, u32p, C.c_uint64, C.c_uint64, C.POINTER(VP)]),
     ("fdgpu_ingest_stats", None, [C.POINTER(C.c_double), C.c_int]),

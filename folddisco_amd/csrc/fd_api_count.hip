@@ -61,7 +61,7 @@ int fd_posting_lengths_segs(fdgpu_ctx *c, const fdgpu_index *ix, const uint32_t 
     int rc = fd_posting_lengths_dev(c, ix, q_hash, nq, &d);
     if (rc) return rc;
     // the three arrays land in one page-locked block (a pageable destination makes every copy a staged, blocking one)
-    uint8_t *land = (uint8_t *)c->host_pinned(3, nq * 20);
+    uint8_t *land = (uint8_t *)c->host_pinned(FD_HP_UP, nq * 20);
     if (!land) {
         HIPCHK(c, hipMemcpyAsync(lengths, d, nq * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(segs, c->ws[WS_CQ_NSEG].p, nq * 4, hipMemcpyDeviceToHost, c->stream));
@@ -468,7 +468,7 @@ static cq_inputs cq_upload(fdgpu_ctx *c, const fdgpu_index *ix, const cq_form &F
     const uint64_t nq = q_off[n_queries];
     cq_inputs In = {W.q_hash, W.row_meta, W.q_off, W.kidx, penalty ? W.penalty : ix->penalty, have_k};
     const size_t o_k = nq * 8, o_off = 2 * nq * 8, o_h = o_off + (n_queries + 1) * 8, up_bytes = o_h + nq * 4;
-    uint8_t *up = F.tiled ? (uint8_t *)c->host_pinned(5, up_bytes) : nullptr;
+    uint8_t *up = F.tiled ? (uint8_t *)c->host_pinned(FD_HP_PAIRS, up_bytes) : nullptr;
     bool k_up = false;      // the list positions went up with the block
     if (up) {
         memcpy(up, R.meta.data(), nq * 8);
@@ -632,7 +632,7 @@ static int cq_select_on_device(fdgpu_ctx *c, const cq_form &F, const cq_scratch 
     fd_count_rec *head = nullptr;      // the caller's candidates (fdgpu_query_batch: match_top per query) ride on the same wait
     if (e == hipSuccess && dev && dev->head_n) {
         const uint32_t mt = std::min(dev->head_n, top_n);
-        head = (fd_count_rec *)c->host_pinned(3, (size_t)n_queries * mt * sizeof(fd_count_rec));
+        head = (fd_count_rec *)c->host_pinned(FD_HP_UP, (size_t)n_queries * mt * sizeof(fd_count_rec));
         if (head) e = hipMemcpy2DAsync(head, (size_t)mt * sizeof(fd_count_rec), W.ranked, (size_t)top_n * sizeof(fd_count_rec), (size_t)mt * sizeof(fd_count_rec), n_queries,
                                        hipMemcpyDeviceToHost, st);
     }

@@ -128,7 +128,7 @@ static int mp_host_tables(const mp_in &I, const mp_form &F, fd_mp_tables &TB) {
     const char *msg = nullptr;
     const int rc = mp_build_tables(in, c->is_lane ? nullptr : &c->host_pool, B, TB, &msg);      // (a lane's short host loops stay on its own thread)
     if (rc) FAIL(c, rc, msg);
-    uint32_t *blk = I.rq.tables ? nullptr : (uint32_t *)c->host_pinned(0, TB.L.words * 4);
+    uint32_t *blk = I.rq.tables ? nullptr : (uint32_t *)c->host_pinned(FD_HP_SCAN_A, TB.L.words * 4);
     if (!blk) { TB.blk.assign(TB.L.words, 0); blk = TB.blk.data(); }
     mp_pack(in, TB.L, B, blk);
     TB.data = blk; TB.valid = true;
@@ -363,7 +363,7 @@ static int mp_out_packed(const mp_in &I, const mp_form &F, const mp_args &A, con
     hipStream_t st = c->stream;
     const uint64_t n = T.cands;
     // the packed pairs land in pinned buffers the CONTEXT keeps (valid until the next packed scan on this context; never freed by the caller)
-    uint32_t *hk = (uint32_t *)c->host_pinned(0, std::max<uint64_t>(n, 1) * 4), *hv = (uint32_t *)c->host_pinned(1, std::max<uint64_t>(n, 1) * 4);
+    uint32_t *hk = (uint32_t *)c->host_pinned(FD_HP_SCAN_A, std::max<uint64_t>(n, 1) * 4), *hv = (uint32_t *)c->host_pinned(FD_HP_SCAN_B, std::max<uint64_t>(n, 1) * 4);
     mp_host<fd_pair_rec> hf = mp_host_alloc<fd_pair_rec>(T.found);
     if (!hk || !hv || !hf) return FDGPU_ENOMEM;
     if (n) {

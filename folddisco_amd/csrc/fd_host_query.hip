@@ -114,8 +114,8 @@ static rs_layout rs_pack_tables(const rb_in &I, std::vector<uint32_t> &blk_own) 
     L.o_qt = 0; L.o_h = L.o_qt + up4(n_queries * (sizeof(rs_query_dev) / 4)); L.o_kf = L.o_h + up4(nh); L.o_sy = L.o_kf + up4(nh); L.o_qi = L.o_sy + up4((nh + 3) / 4);
     L.o_qj = L.o_qi + up4(nmap); L.o_idf = L.o_qj + up4(nmap); L.o_idx = L.o_idf + up4(nmap); L.o_sq = L.o_idx + up4(nidx); L.o_cd = L.o_sq + up4(n_cand);
     L.o_d0 = L.o_cd + up4(n_cand); L.o_co = L.o_d0 + up4(2 * FD_WAVE + 1); L.words = L.o_co + up4(2 * (n_queries + 1)) + 4;
-    // packed in a pinned staging buffer of the context (its own: the pair scan's block in slot 0 is being copied while this runs)
-    uint32_t *blk = (uint32_t *)I.c->host_pinned(2, L.words * 4);
+    // packed in a pinned staging buffer of the context (its own: the pair scan's block in FD_HP_SCAN_A is being copied while this runs)
+    uint32_t *blk = (uint32_t *)I.c->host_pinned(FD_HP_LAND, L.words * 4);
     if (!blk) { blk_own.assign(L.words, 0); blk = blk_own.data(); }
     memcpy(&blk[L.o_qt], qt.data(), n_queries * sizeof(rs_query_dev));
     if (nh) { memcpy(&blk[L.o_h], t_hash.data(), nh * 4); memcpy(&blk[L.o_kf], t_kfirst.data(), nh * 4); }
@@ -246,7 +246,7 @@ static int rs_finish(const rb_in &I, const rs_layout &L, const rs_plan &R, const
     if (e == hipSuccess && tot_res && !dev_out) e = hipMemcpyAsync(orr.p, c->ws[WS_RS_RECRES].p, tot_res * 4, hipMemcpyDeviceToHost, st);
     if (dev_out) { dev_out->got = true; dev_out->recs = c->ws[WS_RS_REC].p; dev_out->residues = c->ws[WS_RS_RECRES].as<int32_t>(); dev_out->n_recs = nm; dev_out->n_res = tot_res; }
     // the two offset arrays lie side by side on the device: one copy into the context's page-locked block, parted on the host
-    uint64_t *off_land = d_ro == d_mo + (n_queries + 1) ? (uint64_t *)c->host_pinned(1, 2 * (n_queries + 1) * 8) : nullptr;
+    uint64_t *off_land = d_ro == d_mo + (n_queries + 1) ? (uint64_t *)c->host_pinned(FD_HP_SCAN_B, 2 * (n_queries + 1) * 8) : nullptr;
     if (e == hipSuccess && off_land) e = hipMemcpyAsync(off_land, d_mo, 2 * (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && !off_land) e = hipMemcpyAsync(omo.p, d_mo, (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && !off_land) e = hipMemcpyAsync(oro.p, d_ro, (n_queries + 1) * 8, hipMemcpyDeviceToHost, st);
@@ -677,7 +677,7 @@ extern "C" int fdgpu_query_batch(fdgpu_ctx *c, const fdgpu_index *ix, const fdgp
         const fd_count_rec *head = D.head;       // came with the selection's state (one wait)
         hipError_t e = hipSuccess;
         if (!head) {
-            fd_count_rec *h2 = (fd_count_rec *)c->host_pinned(3, head_bytes);
+            fd_count_rec *h2 = (fd_count_rec *)c->host_pinned(FD_HP_UP, head_bytes);
             if (!h2) { head_v.resize((size_t)n_queries * std::max<uint32_t>(mt, 1)); h2 = head_v.data(); }
             if (mt && n_queries)
                 e = hipMemcpy2DAsync(h2, (size_t)mt * sizeof(fd_count_rec), D.recs, (size_t)top_n * sizeof(fd_count_rec), (size_t)mt * sizeof(fd_count_rec), n_queries,

@@ -8,14 +8,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <map>
-#include <unordered_map>
-#include <unordered_set>
-#include <atomic>
+#include <chrono>
 #include <thread>
 #include <vector>
 #include "fdgpu_internal.h"
-#include <chrono>
+#include "fd_query_map_host.h"
 
 #define HIPCHK(ctx, expr)                                                                                   \
     do {                                                                                                    \
@@ -65,8 +62,7 @@ __global__ void k_pair_features(fd_batch_view B, uint32_t s, const uint32_t *__r
 }
 // the same for every encoding, in the query map's own record: [0..9) the feature container of get_single_feature, [9] the CA
 // distance and [10], [11] the two residue types (get_list_amino_acids_and_distances, structure/core.rs:462-477 — what the
-// observed-distance map holds whatever the encoding puts into the container)
-#define FD_QF 12
+// observed-distance map holds whatever the encoding puts into the container); FD_QF floats (fd_query_map_host.h)
 __global__ void k_pair_features12(fd_batch_view B, const uint32_t *__restrict__ pi, const uint32_t *__restrict__ pj, uint32_t n, float cutoff,
                                   uint32_t type, float *__restrict__ feat /*[n][FD_QF]*/, uint8_t *__restrict__ valid) {
     uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -238,7 +234,7 @@ static int pair_features12(fdgpu_ctx *c, const fdgpu_batch *b, const uint32_t *p
     HIPCHK(c, c->ws[WS_MISC2].ensure(n * 4 * FD_QF + n));
     uint32_t *d_pi = c->ws[WS_MISC0].as<uint32_t>(), *d_pj = d_pi + n;
     uint8_t *d_valid = c->ws[WS_MISC2].as<uint8_t>() + n * 4 * FD_QF;
-    uint32_t *up = (uint32_t *)c->host_pinned(5, 2 * n * 4);
+    uint32_t *up = (uint32_t *)c->host_pinned(FD_HP_PAIRS, 2 * n * 4);
     if (up) {
         memcpy(up, pi, n * 4); memcpy(up + n, pj, n * 4);
         HIPCHK(c, hipMemcpyAsync(d_pi, up, 2 * n * 4, hipMemcpyHostToDevice, st));
@@ -249,8 +245,8 @@ static int pair_features12(fdgpu_ctx *c, const fdgpu_batch *b, const uint32_t *p
     hipLaunchKernelGGL(k_pair_features12, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, b->view(), d_pi, d_pj, (uint32_t)n, p->dist_cutoff, p->hash_type,
                        c->ws[WS_MISC2].as<float>(), d_valid);
     HIPCHK(c, hipGetLastError());
-    // page-locked landing block (slot 4, read in place by the caller until its next call): the copy does not stage, one wait, no second copy
-    uint8_t *land = land_out ? (uint8_t *)c->host_pinned(4, n * 4 * FD_QF + n) : nullptr;
+    // page-locked landing block (FD_HP_FEAT, read in place by the caller until its next call): the copy does not stage, one wait, no second copy
+    uint8_t *land = land_out ? (uint8_t *)c->host_pinned(FD_HP_FEAT, n * 4 * FD_QF + n) : nullptr;
     if (land) {
         HIPCHK(c, hipMemcpyAsync(land, c->ws[WS_MISC2].p, n * 4 * FD_QF + n, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
@@ -279,19 +275,371 @@ static int hash_features_q(fdgpu_ctx *c, const float *features, uint64_t n, fd_q
 }
 
 // ------------------------------------------------------------------------------------------ make_query_map
-template <typename T> static T *dup_vec(const std::vector<T> &v) {
-    T *p = (T *)malloc(std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (p && !v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
-
 extern "C" void fdgpu_query_map_free(fd_query_map *m) {
     if (!m) return;
-    if (m->arena_bytes) { free(m); return; }       // the map and its arrays are one block (fdgpu_make_query_map_batch)
+    if (m->arena_bytes) { free(m); return; }       // the map and its arrays are one block (qm_fill_map)
     free(m->hash); free(m->qi); free(m->qj); free(m->is_primary); free(m->idf); free(m->indices); free(m->primary_hash);
     free(m->aad_aa1); free(m->aad_aa2); free(m->aad_dist); free(m->aad_qi);
     free(m->post_len); free(m->post_seg); free(m->post_kidx);
     free(m);
+}
+
+// The stages of fdgpu_make_query_map_batch pass these.  The host steps between the kernels are fd_query_map_host.cpp's.
+struct qm_request {      // the call's arguments, checked and completed by qm_read_request
+    fdgpu_ctx *c; const fdgpu_batch *qb; uint64_t n_queries; const uint32_t *q_struct; const uint64_t *q_off; const uint32_t *q_index;
+    const uint8_t *const *subs; const uint32_t *n_subs; const float *dist_thr; uint64_t n_dist; const float *angle_thr_deg; uint64_t n_angle;
+    const fd_hash_params *p; const fdgpu_index *index; float total_structures; fd_query_map **out;
+    std::vector<float> athr = {};      // the angle thresholds in radians
+    bool any_subs = false;             // some residue of the batch has a substitution list
+    uint32_t n_cfg = 0;                // --multiple-bins: bin configurations every candidate is inserted under (0: the single one)
+    char qd_mode = 0;                  // the forced form, '0' / '1' / '2' (qm_read_request), 0: none
+    bool trace = false;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    qm_thresholds thresholds() const { return {dist_thr, n_dist, athr.data(), n_angle}; }
+    uint64_t r0(uint64_t t) const { return qb->h_res_off[q_struct[t]]; }      // first residue of query t's structure
+};
+// Which of the three forms "candidates -> hashes" a call takes:
+//   host expansion    substitutions, --multiple-bins, more than 8 thresholds of a kind, 2^31 candidates, no valid pair, forced form '0'
+//   device expansion  every candidate's place follows from its pair: the host neither builds nor uploads 48 bytes per candidate.  Then
+//     sort-dedupe     ONE query of 32,768 candidates and more (a whole-structure query: ~10^5 pairs, 3 x 10^5 candidates; forced form '1': any size)
+//     chain           a motif batch whose queries fit k_qm_dedupe's table (forced form '2': never), with the posting lengths when there is an index
+//     hashes only     the rest: first insertions and lengths on the host
+struct qm_form {
+    bool dev_expand = false, dev_dedupe = false, chain = false, chain_len = false;
+    uint64_t per_pair = 0;                   // candidates of a pair without substitutions: observed + near / far per threshold and field
+    std::vector<uint64_t> valid_off;         // valid pairs in front of every query
+    uint32_t path() const {
+        return (dev_expand ? FDGPU_QMPATH_DEVICE_EXPAND : FDGPU_QMPATH_HOST_EXPAND) | (chain ? FDGPU_QMPATH_CHAIN : 0u) | (chain_len ? FDGPU_QMPATH_CHAIN_LENGTHS : 0u) |
+               (dev_dedupe ? FDGPU_QMPATH_SORT_DEDUPE : 0u);
+    }
+};
+struct qm_feat_store { std::vector<float> feat; std::vector<uint8_t> valid; };      // the pair features when the landing block cannot be had
+struct qm_work {         // the batch's candidates, in the reference's insertion order; query t: [cand_off[t], cand_off[t + 1])
+    std::vector<qm_aad> aads;
+    std::vector<uint64_t> cand_off;
+    uint64_t nc = 0;
+    std::vector<uint32_t> vpairs;      // device expansion: the valid pairs, ascending — candidate z is insertion z % per_pair of pair vpairs[z / per_pair]
+    qm_cands cands;                    // host expansion: every candidate's container and (residues, observed?, pair)
+};
+struct qm_hashed {       // candidates -> hashes (+ first-insertion flags, + posting lengths)
+    std::vector<uint32_t> hashes;
+    std::vector<std::vector<uint32_t>> cfg;      // host form with --multiple-bins: the hashes under every bin pair
+    std::vector<const uint32_t *> planes;        // what an insertion's hash is read from: cfg[k], or hashes alone
+    std::vector<uint32_t> dev_keep;              // sort-dedupe: the kept positions
+    std::vector<uint8_t> land_v;                 // chain: the landing block without page-locked memory
+    // the chain's results per candidate (landing block, valid until the call returns); null = not computed
+    const uint8_t *ch_first = nullptr; const uint64_t *ch_len = nullptr; const long long *ch_kidx = nullptr; const uint32_t *ch_seg = nullptr;
+    qm_insertions insertions(const qm_work &W, uint64_t t) const { return {planes.data(), (uint32_t)planes.size(), W.cand_off[t], (W.cand_off[t + 1] - W.cand_off[t]) * planes.size()}; }
+};
+struct qm_kept { std::vector<std::vector<uint32_t>> keeps; uint64_t n_keep = 0; };      // per query: insertion positions (candidate * n_cfg + bin pair) that enter the map, ascending
+struct qm_lengths {      // per pair: hash and idf of its observed candidate; per kept entry (in query order): posting length, segments, list position
+    std::vector<float> pair_idf; std::vector<uint32_t> pair_primary;
+    std::vector<uint64_t> ent_len; std::vector<uint32_t> ent_seg; std::vector<long long> ent_kidx;
+    const uint64_t *e_len = nullptr; const uint32_t *e_seg = nullptr; const long long *e_kidx = nullptr;      // as the assembly reads them: the vectors, or a landing block
+};
+
+// every refusal, ahead of any device work; the only reader of the environment
+static int qm_read_request(qm_request &R) {
+    fdgpu_ctx *c = R.c;
+    if (!c || !R.qb || !R.p || !R.out || !R.q_off || (R.n_queries && !R.q_struct) || (R.q_off[R.n_queries] && !R.q_index)) return FDGPU_EINVAL;
+    for (uint64_t t = 0; t < R.n_queries; ++t) { R.out[t] = nullptr; if (R.q_struct[t] >= R.qb->n_struct) return FDGPU_EINVAL; }
+    CHECK_TYPE(c, R.p);
+    if (!fd_multiple_bins_valid(R.p)) { c->err = "multiple_bins: at most 8 (dist, angle) bin pairs, no zero counts"; return FDGPU_EINVAL; }
+    R.n_cfg = R.p->n_multiple_bins;
+    const float RADS_PER_DEG = 3.14159274101257324f / 180.0f;  // f32::to_radians
+    R.athr.resize(R.n_angle);
+    for (uint64_t t = 0; t < R.n_angle; ++t) R.athr[t] = R.angle_thr_deg[t] * RADS_PER_DEG;
+    if (R.subs && R.n_subs) for (uint64_t a = 0; a < R.q_off[R.n_queries] && !R.any_subs; ++a) R.any_subs = R.subs[a] != nullptr;
+    const char *qd = getenv("FDGPU_QM_DEVICE");      // 0: host form; 1: sort-dedupe for one query of any size; 2: device expansion without the chain (tests compare the forms)
+    R.qd_mode = qd ? qd[0] : 0;
+    R.trace = getenv("FDGPU_TRACE") != nullptr;
+    return FDGPU_OK;
+}
+
+// the landing block first; the caller's own arrays only when it cannot be had
+static int qm_pair_features(const qm_request &R, const qm_pairs &P, qm_feat_store &S, qm_feat &F) {
+    const uint64_t np = P.pi.size();
+    uint8_t *land = nullptr;
+    int rc = pair_features12(R.c, R.qb, P.pi.data(), P.pj.data(), np, R.p, nullptr, nullptr, &land);
+    if (!rc && np && !land) {
+        S.feat.resize(np * FD_QF); S.valid.resize(np);
+        rc = pair_features12(R.c, R.qb, P.pi.data(), P.pj.data(), np, R.p, S.feat.data(), S.valid.data());
+    }
+    F = land ? qm_feat{(const float *)land, land + np * 4 * FD_QF} : qm_feat{S.feat.data(), S.valid.data()};
+    return rc;
+}
+
+// the one place that decides the form (and what fdgpu_debug_last_query_map_path reports)
+static qm_form qm_choose_form(const qm_request &R, const qm_pairs &P, const qm_feat &F) {
+    qm_form f;
+    f.valid_off.assign(R.n_queries + 1, 0);
+    uint64_t max_valid = 0;
+    for (uint64_t t = 0; t < R.n_queries; ++t) {
+        uint64_t nv = 0;
+        for (uint64_t k = P.off[t]; k < P.off[t + 1]; ++k) nv += F.valid[k] ? 1 : 0;
+        f.valid_off[t + 1] = f.valid_off[t] + nv;
+        max_valid = std::max(max_valid, nv);
+    }
+    const qm_fields fl = qm_fields_of(R.p->hash_type);
+    f.per_pair = 1 + 2 * ((uint64_t)fl.ndi * R.n_dist + (uint64_t)fl.nai * R.n_angle);
+    const uint64_t n_valid = f.valid_off[R.n_queries], nc = n_valid * f.per_pair;
+    const uint64_t qd_min = R.qd_mode == '1' ? 1 : 32768;
+    f.dev_expand = !R.any_subs && R.p->n_multiple_bins == 0 && R.n_dist <= 8 && R.n_angle <= 8 && R.qd_mode != '0' && n_valid && nc < (1ull << 31);
+    f.dev_dedupe = f.dev_expand && R.n_queries == 1 && nc >= qd_min;
+    f.chain = f.dev_expand && !f.dev_dedupe && max_valid * f.per_pair <= QM_DD_MAX && R.qd_mode != '2';
+    f.chain_len = f.chain && R.index && R.index->lens && R.index->n_hashes && R.index->n_structures;
+    R.c->last_query_map_path = f.path();
+    return f;
+}
+
+// the (aa, aa, distance, qi) list of every query; a whole-structure query on the device forms (nothing else is left to do per pair) in eight parts
+static void qm_observed_lists(const qm_request &R, const qm_pairs &P, const qm_feat &F, const qm_form &form, qm_work &W) {
+    W.aads.resize(R.n_queries);
+    for (uint64_t t = 0; t < R.n_queries; ++t) {
+        const bool parts = form.dev_expand && P.off[t + 1] - P.off[t] >= QM_PARTS_MIN;      // (small_par asks the system for its CPUs: only where it is used)
+        qm_observed_list(F, P.pi.data(), P.off[t], P.off[t + 1], R.r0(t), parts ? &R.c->host_pool : nullptr, parts ? R.c->small_par(8) : 1u, W.aads[t]);
+    }
+}
+
+// device expansion: the candidates are implied by the valid pairs
+static void qm_implied_candidates(const qm_request &R, const qm_pairs &P, const qm_feat &F, const qm_form &form, qm_work &W) {
+    const uint64_t np = P.pi.size();
+    W.vpairs.reserve(form.valid_off[R.n_queries]);
+    for (uint64_t k = 0; k < np; ++k) if (F.valid[k]) W.vpairs.push_back((uint32_t)k);
+    W.cand_off.resize(R.n_queries + 1);
+    for (uint64_t t = 0; t <= R.n_queries; ++t) W.cand_off[t] = form.valid_off[t] * form.per_pair;
+    W.nc = W.cand_off[R.n_queries];
+}
+// host expansion: containers and records of every candidate (48 + 16 bytes each; reserved for the case without substitutions)
+static void qm_host_candidates(const qm_request &R, const qm_pairs &P, const qm_feat &F, const qm_form &form, qm_work &W) {
+    const uint64_t n_plain = form.valid_off[R.n_queries] * form.per_pair;
+    W.cands.vf.reserve(n_plain * FD_QF); W.cands.c.reserve(n_plain);
+    const qm_fields fl = qm_fields_of(R.p->hash_type);
+    W.cand_off.assign(R.n_queries + 1, 0);
+    for (uint64_t t = 0; t < R.n_queries; ++t) {
+        const uint64_t a = R.q_off[t];
+        qm_expand_query(F, P.pi.data(), P.pj.data(), P.off[t], P.off[t + 1], R.r0(t), R.q_index + a, R.q_off[t + 1] - a, R.any_subs ? R.subs + a : nullptr,
+                        R.any_subs ? R.n_subs + a : nullptr, fl, R.thresholds(), W.cands);
+        W.cand_off[t + 1] = W.cands.c.size();
+    }
+    W.nc = W.cands.c.size();
+}
+
+// ---- candidates -> hashes, one function per form
+// host expansion: the containers go up, the hashes come back — once per bin configuration.  --multiple-bins: every candidate is inserted under
+// every bin pair, in list order (insert_binned_hash, query.rs:59-70); the observed hash idf is looked up for stays the single-configuration one
+// (query.rs:283-288)
+static int qm_hash_host_form(const qm_request &R, const qm_work &W, qm_hashed &H) {
+    int rc = hash_features_q(R.c, W.cands.vf.data(), W.nc, fd_make_consts(R.p).q, H.hashes.data(), FD_QF);
+    H.cfg.resize(R.n_cfg);
+    for (uint32_t k = 0; k < R.n_cfg && !rc; ++k) {
+        H.cfg[k].resize(std::max<uint64_t>(W.nc, 1));
+        rc = hash_features_q(R.c, W.cands.vf.data(), W.nc, fd_make_consts_cfg(R.p, k).q, H.cfg[k].data(), FD_QF);
+    }
+    return rc;
+}
+static qm_expand_par qm_device_par(const qm_request &R, const qm_form &form) {
+    const qm_fields fl = qm_fields_of(R.p->hash_type);
+    qm_expand_par P;
+    memset(&P, 0, sizeof P);
+    for (int z = 0; z < fl.ndi; ++z) P.di[z] = fl.di[z];
+    for (int z = 0; z < fl.nai; ++z) P.ai[z] = fl.ai[z];
+    P.ndi = fl.ndi; P.nai = fl.nai; P.n_dist = (uint32_t)R.n_dist; P.n_angle = (uint32_t)R.n_angle; P.per_pair = (uint32_t)form.per_pair;
+    for (uint64_t z = 0; z < R.n_dist; ++z) P.dthr[z] = R.dist_thr[z];
+    for (uint64_t z = 0; z < R.n_angle; ++z) P.athr[z] = R.athr[z];
+    return P;
+}
+// The chain's outputs: ONE block of 25 bytes per candidate — [len u64 | kidx i64 | hash u32 | nseg u32 | first u8] x nc — on the device and, laid out
+// the same, in the landing block, so that they come home in one copy launch (they were five)
+struct qm_chain_block {
+    uint64_t nc;
+    size_t o_kidx() const { return nc * 8; }
+    size_t o_hash() const { return nc * 16; }
+    size_t o_nseg() const { return nc * 20; }
+    size_t o_first() const { return nc * 24; }
+    size_t bytes() const { return nc * 25; }
+    uint64_t *len(uint8_t *b) const { return (uint64_t *)b; }
+    long long *kidx(uint8_t *b) const { return (long long *)(b + o_kidx()); }
+    uint32_t *hash(uint8_t *b) const { return (uint32_t *)(b + o_hash()); }
+    uint32_t *nseg(uint8_t *b) const { return (uint32_t *)(b + o_nseg()); }
+    uint8_t *first(uint8_t *b) const { return b + o_first(); }
+};
+// a motif batch: expansion + hashes -> per-query first-insertion dedupe (k_qm_dedupe) -> posting lengths, segment counts and list positions of
+// EVERY candidate's hash (the index's length table; 17 k lookups per 128 queries) — three kernels back to back, one landing block, one wait; the
+// host neither dedupes nor makes a second round trip for the lengths.  Without the chain's preconditions: hashes only.
+// ws[WS_MISC2] still holds the pairs' containers (pair_features12)
+static int qm_hash_chain_form(const qm_request &R, const qm_form &form, const qm_work &W, qm_hashed &H) {
+    fdgpu_ctx *c = R.c;
+    hipStream_t st = c->stream;
+    const uint64_t nv = W.vpairs.size(), nc = W.nc, nq = R.n_queries;
+    const qm_chain_block B = {nc};
+    const size_t up_words = nv + 2 * (nq + 1) + 2, o_off = (nv + 1) & ~(size_t)1;      // upload: [valid pairs | cand_off, 8-byte aligned]
+    uint32_t *up = (uint32_t *)c->host_pinned(FD_HP_UP, up_words * 4);
+    std::vector<uint32_t> up_v;
+    if (!up) { up_v.resize(up_words); up = up_v.data(); }
+    memcpy(up, W.vpairs.data(), nv * 4);
+    memcpy(up + o_off, W.cand_off.data(), (nq + 1) * 8);
+    HIPCHK(c, c->ws[WS_MISC0].ensure(up_words * 4));
+    HIPCHK(c, c->ws[WS_MISC1].ensure(B.bytes() + 64));
+    uint32_t *d_up = c->ws[WS_MISC0].as<uint32_t>();
+    uint8_t *d_blk = c->ws[WS_MISC1].as<uint8_t>();
+    HIPCHK(c, hipMemcpyAsync(d_up, up, up_words * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_qm_expand_hash, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st, c->ws[WS_MISC2].as<float>(), d_up, (uint32_t)nv, qm_device_par(R, form),
+                       fd_make_consts(R.p).q, B.hash(d_blk));
+    if (form.chain) hipLaunchKernelGGL(k_qm_dedupe, dim3((unsigned)nq), dim3(256), 0, st, B.hash(d_blk), (const uint64_t *)(d_up + o_off), B.first(d_blk));
+    if (form.chain_len)
+        fd_launch_posting_lookup(R.index->hashes, R.index->offsets, R.index->lens, R.index->n_hashes, B.hash(d_blk), nc, B.len(d_blk), B.nseg(d_blk), B.kidx(d_blk), st);
+    HIPCHK(c, hipGetLastError());
+    uint8_t *land = (uint8_t *)c->host_pinned(FD_HP_LAND, B.bytes() + 64);
+    if (!land) { H.land_v.resize(B.bytes() + 64); land = H.land_v.data(); }
+    // the whole block; without the lengths from the hashes on: hashes (and first-insertion flags; the segment counts between them are not read)
+    const size_t from = form.chain_len ? 0 : B.o_hash(), to = form.chain ? B.bytes() : B.o_nseg();
+    HIPCHK(c, hipMemcpyAsync(land + from, d_blk + from, to - from, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(H.hashes.data(), B.hash(land), nc * 4);
+    if (form.chain) H.ch_first = B.first(land);
+    if (form.chain_len) { H.ch_len = B.len(land); H.ch_kidx = B.kidx(land); H.ch_seg = B.nseg(land); }
+    return FDGPU_OK;
+}
+// ONE large query (a whole-structure query): expansion, hashes and the first-insertion-wins dedupe on the device; only the hashes and the kept
+// positions come back.  First insertion wins: stable sort of (hash, position) by hash, first of every run marked, marks compacted in position
+// order.  The sort takes the build's key / id buffers
+static int qm_hash_sort_form(const qm_request &R, const qm_form &form, const qm_work &W, qm_hashed &H) {
+    fdgpu_ctx *c = R.c;
+    hipStream_t st = c->stream;
+    const uint64_t nv = W.vpairs.size(), nc = W.nc;
+    HIPCHK(c, c->ws[WS_MISC0].ensure(nv * 4)); HIPCHK(c, c->ws[WS_MISC1].ensure(nc * 4));
+    HIPCHK(c, c->ws[WS_KEYS_A].ensure(nc * 4)); HIPCHK(c, c->ws[WS_KEYS_B].ensure(nc * 4));
+    HIPCHK(c, c->ws[WS_IDS_A].ensure(nc * 4)); HIPCHK(c, c->ws[WS_IDS_B].ensure(nc * 4));
+    HIPCHK(c, c->ws[WS_GHIST].ensure((size_t)256 * std::max<uint32_t>(fd_rs_num_tiles(nc), 1) * 4));
+    HIPCHK(c, c->ws[WS_TOT].ensure((256 + (size_t)(fd_rs_num_tiles(nc) / 128 + 2) * 256) * 8));
+    HIPCHK(c, c->ws[WS_MISC4].ensure(nc + 8));
+    HIPCHK(c, c->ws[WS_TILE_BO].ensure((nc + 2) * 8));
+    HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(nc) * 8 + 64));
+    HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
+    HIPCHK(c, hipMemcpyAsync(c->ws[WS_MISC0].p, W.vpairs.data(), nv * 4, hipMemcpyHostToDevice, st));
+    uint32_t *d_hash = c->ws[WS_MISC1].as<uint32_t>();
+    hipLaunchKernelGGL(k_qm_expand_hash, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st, c->ws[WS_MISC2].as<float>(), c->ws[WS_MISC0].as<uint32_t>(), (uint32_t)nv,
+                       qm_device_par(R, form), fd_make_consts(R.p).q, d_hash);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(H.hashes.data(), d_hash, nc * 4, hipMemcpyDeviceToHost, st));
+    uint32_t *ka = c->ws[WS_KEYS_A].as<uint32_t>(), *kb = c->ws[WS_KEYS_B].as<uint32_t>(), *va = c->ws[WS_IDS_A].as<uint32_t>(), *vb = c->ws[WS_IDS_B].as<uint32_t>();
+    const unsigned gb = (unsigned)((nc + 255) / 256);
+    HIPCHK(c, hipMemcpyAsync(ka, d_hash, nc * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_qm_iota, dim3(gb), dim3(256), 0, st, va, nc);
+    const int cur = fd_radix_sort_pairs(ka, va, kb, vb, nc, 32, c->ws[WS_GHIST].as<uint32_t>(), c->ws[WS_TOT].as<uint64_t>(), st, nullptr);
+    uint8_t *d_first = c->ws[WS_MISC4].as<uint8_t>();
+    HIPCHK(c, hipMemsetAsync(d_first, 0, nc, st));
+    hipLaunchKernelGGL(k_qm_first, dim3(gb), dim3(256), 0, st, cur ? kb : ka, cur ? vb : va, nc, d_first);
+    fd_exclusive_scan<uint8_t>(d_first, nc, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), c->ws[WS_TOTAL].as<uint64_t>(), st);
+    uint32_t *d_keep = cur ? ka : kb;      // the sort's other buffer is free again
+    hipLaunchKernelGGL(k_qm_keep, dim3(gb), dim3(256), 0, st, d_first, c->ws[WS_TILE_BO].as<uint64_t>(), nc, d_keep);
+    HIPCHK(c, hipGetLastError());
+    uint64_t nk = 0;
+    HIPCHK(c, hipMemcpyAsync(&nk, c->ws[WS_TOTAL].p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    H.dev_keep.resize(nk);
+    // (a stray synchronous copy on the null stream into pageable memory, after the wait above: kept as it is)
+    if (nk) HIPCHK(c, hipMemcpy(H.dev_keep.data(), d_keep, nk * 4, hipMemcpyDeviceToHost));
+    return FDGPU_OK;
+}
+static int qm_hash_candidates(const qm_request &R, const qm_form &form, const qm_work &W, qm_hashed &H) {
+    H.hashes.resize(std::max<uint64_t>(W.nc, 1));
+    const int rc = !form.dev_expand ? qm_hash_host_form(R, W, H) : form.dev_dedupe ? qm_hash_sort_form(R, form, W, H) : qm_hash_chain_form(R, form, W, H);
+    if (R.n_cfg) for (uint32_t k = 0; k < R.n_cfg; ++k) H.planes.push_back(H.cfg[k].data());
+    else H.planes.push_back(H.hashes.data());
+    return rc;
+}
+
+// first insertion wins (the reference's hash map keeps the entry a hash was first inserted with): the device's answer where a device form gave
+// one, else per query on the host
+static void qm_first_insertions(const qm_request &R, const qm_form &form, const qm_work &W, qm_hashed &H, qm_kept &K) {
+    K.keeps.resize(R.n_queries);
+    std::vector<uint64_t> tab;
+    for (uint64_t t = 0; t < R.n_queries; ++t) {
+        const qm_insertions I = H.insertions(W, t);
+        std::vector<uint32_t> &keep = K.keeps[t];
+        if (form.dev_dedupe) keep.swap(H.dev_keep);
+        else if (H.ch_first) { keep.reserve((size_t)I.n_ins / 2 + 8); for (uint64_t pos = 0; pos < I.n_ins; ++pos) if (H.ch_first[I.c0 + pos]) keep.push_back((uint32_t)pos); }
+        else qm_first_wins(I, tab, keep);
+        K.n_keep += keep.size();
+    }
+}
+
+// the observed candidate of every valid pair, in candidate order: its pair and its hash
+struct qm_observed { std::vector<uint32_t> pair_v, hash; const uint32_t *pair = nullptr; };
+static void qm_observed_candidates(const qm_form &form, const qm_work &W, const qm_hashed &H, qm_observed &O) {
+    if (form.dev_expand) {
+        O.pair = W.vpairs.data();
+        O.hash.resize(W.vpairs.size());
+        for (size_t v = 0; v < O.hash.size(); ++v) O.hash[v] = H.hashes[v * form.per_pair];
+        return;
+    }
+    for (uint64_t z = 0; z < W.nc; ++z)
+        if (W.cands.c[z].primary) { O.hash.push_back(H.hashes[z]); O.pair_v.push_back(W.cands.c[z].pair); }
+    O.pair = O.pair_v.data();
+}
+// the chain looked every candidate up: pick the kept entries and the observed hashes
+static void qm_lengths_from_chain(const qm_form &form, const qm_work &W, const qm_hashed &H, const qm_kept &K, qm_lengths &L) {
+    size_t w = 0;
+    for (size_t t = 0; t < K.keeps.size(); ++t)
+        for (uint32_t pos : K.keeps[t]) { const uint64_t z = W.cand_off[t] + pos; L.ent_len[w] = H.ch_len[z]; L.ent_seg[w] = H.ch_seg[z]; L.ent_kidx[w] = H.ch_kidx[z]; ++w; }
+    for (uint64_t v = 0; v < W.vpairs.size(); ++v, ++w) { const uint64_t z = v * form.per_pair; L.ent_len[w] = H.ch_len[z]; L.ent_seg[w] = H.ch_seg[z]; L.ent_kidx[w] = H.ch_kidx[z]; }
+}
+// ... or one lookup of the kept entries' hashes, then the observed ones; large requests stay in the page-locked block (read once, in place)
+static int qm_lengths_lookup(const qm_request &R, const qm_work &W, const qm_hashed &H, const qm_kept &K, const qm_observed &O, qm_lengths &L) {
+    std::vector<uint32_t> ph;
+    ph.reserve(K.n_keep + O.hash.size());
+    for (uint64_t t = 0; t < R.n_queries; ++t) {
+        const qm_insertions I = H.insertions(W, t);
+        for (uint32_t pos : K.keeps[t]) ph.push_back(qm_hash_at(I, pos));
+    }
+    ph.insert(ph.end(), O.hash.begin(), O.hash.end());
+    const uint8_t *land = nullptr;
+    const int rc = fd_posting_lengths_segs(R.c, R.index, ph.data(), ph.size(), L.ent_len.data(), L.ent_seg.data(), L.ent_kidx.data(), ph.size() >= QM_PARTS_MIN ? &land : nullptr);
+    if (!rc && land) { L.e_len = (const uint64_t *)land; L.e_kidx = (const long long *)(land + ph.size() * 8); L.e_seg = (const uint32_t *)(land + ph.size() * 16); }
+    return rc;
+}
+// ONE posting-length pass: the observed (primary) hash of every pair — idf = log2(S / len), query.rs:17-32 — and every entry that enters a map;
+// the maps remember the latter (post_len / post_seg) so that scoring them needs no second pass over the same lists
+static int qm_posting_lengths(const qm_request &R, const qm_pairs &P, const qm_form &form, const qm_work &W, const qm_hashed &H, const qm_kept &K, qm_lengths &L) {
+    const size_t np = P.pi.size();
+    L.pair_idf.assign(std::max<size_t>(np, 1), 0.0f); L.pair_primary.assign(std::max<size_t>(np, 1), 0u);
+    qm_observed O;
+    qm_observed_candidates(form, W, H, O);
+    const size_t n_obs = O.hash.size(), n_ent = K.n_keep + n_obs;
+    for (size_t v = 0; v < n_obs; ++v) L.pair_primary[O.pair[v]] = O.hash[v];
+    if (!R.index) return FDGPU_OK;
+    L.ent_len.assign(std::max<size_t>(n_ent, 1), 0); L.ent_seg.assign(std::max<size_t>(n_ent, 1), 0); L.ent_kidx.assign(std::max<size_t>(n_ent, 1), -1);
+    L.e_len = L.ent_len.data(); L.e_seg = L.ent_seg.data(); L.e_kidx = L.ent_kidx.data();
+    if (H.ch_len) qm_lengths_from_chain(form, W, H, K, L);
+    else if (const int rc = qm_lengths_lookup(R, W, H, K, O, L)) return rc;
+    // idf of the observed hash of every pair: log2f is ~8 ns a call — 0.7 ms for the 88 k pairs of a whole-structure query on one thread
+    const uint64_t *len = L.e_len + K.n_keep;
+    const float S = R.total_structures;
+    const auto idf_part = [&](unsigned z) { for (size_t v = n_obs * z / 8; v < n_obs * (z + 1) / 8; ++v) L.pair_idf[O.pair[v]] = len[v] > 0 ? log2f(S / (float)len[v]) : 0.0f; };
+    // (this loop sizes its helpers without small_par, so on a lane context it alone leaves the lane's thread; making it follow the other two
+    // would change what a lane does and is left as it is)
+    if (n_obs < QM_PARTS_MIN) for (unsigned z = 0; z < 8; ++z) idf_part(z);
+    else qm_run_parts(&R.c->host_pool, std::min(8u, std::max(1u, std::thread::hardware_concurrency())), 8, idf_part);
+    return FDGPU_OK;
+}
+
+// one block per map (a map was 15 allocations, a batch of 128 queries two thousand)
+static int qm_assemble(const qm_request &R, const qm_pairs &P, const qm_form &form, const qm_work &W, const qm_hashed &H, const qm_kept &K, const qm_lengths &L) {
+    uint64_t keep_at = 0;      // entries of the queries in front
+    for (uint64_t t = 0; t < R.n_queries; ++t) {
+        const std::vector<uint32_t> &keep = K.keeps[t];
+        const qm_map_src S = {keep.data(), keep.size(), H.insertions(W, t), form.dev_expand ? nullptr : W.cands.c.data(), W.vpairs.data(), form.per_pair, P.pi.data(),
+                              P.pj.data(), R.r0(t), L.pair_idf.data(), L.pair_primary.data(), L.e_len ? L.e_len + keep_at : nullptr, L.e_seg ? L.e_seg + keep_at : nullptr,
+                              L.e_kidx ? L.e_kidx + keep_at : nullptr, R.index ? R.index->uid : 0, R.q_index + R.q_off[t], (size_t)(R.q_off[t + 1] - R.q_off[t]), &W.aads[t]};
+        fd_query_map *m = qm_fill_map(S, &R.c->host_pool, form.dev_expand && keep.size() >= QM_PARTS_MIN ? R.c->small_par(8) : 1u);
+        if (!m) { for (uint64_t u = 0; u < t; ++u) { fdgpu_query_map_free(R.out[u]); R.out[u] = nullptr; } return FDGPU_ENOMEM; }
+        R.out[t] = m;
+        keep_at += keep.size();
+    }
+    return FDGPU_OK;
 }
 
 // make_query_map (src/controller/query.rs:208-329) for MANY queries with three launches in total (pair features, hashes of
@@ -301,488 +649,33 @@ extern "C" int fdgpu_make_query_map_batch(fdgpu_ctx *c, const fdgpu_batch *qb, u
                                           const uint32_t *q_index, const uint8_t *const *subs, const uint32_t *n_subs, const float *dist_thr,
                                           uint64_t n_dist, const float *angle_thr_deg, uint64_t n_angle, const fd_hash_params *p,
                                           const fdgpu_index *index, float total_structures, fd_query_map **out) { FD_LOCK(c);
-    if (!c || !qb || !p || !out || !q_off || (n_queries && !q_struct) || (q_off[n_queries] && !q_index)) return FDGPU_EINVAL;
-    for (uint64_t t = 0; t < n_queries; ++t) { out[t] = nullptr; if (q_struct[t] >= qb->n_struct) return FDGPU_EINVAL; }
-    // all ordered pairs of every query's residues, row-major (CombinationIterator, utils/combination.rs:23-44), as residue
-    // indices of the whole batch
-    const bool qtrace = getenv("FDGPU_TRACE") != nullptr;
-    const auto q_t0 = std::chrono::steady_clock::now();
-    auto q_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - q_t0).count(); };
-    std::vector<uint32_t> pi, pj;
-    std::vector<uint64_t> pair_off(n_queries + 1, 0);
-    {       // (a whole-structure query lists ~10^5 pairs: growing the two arrays by doubling was a third of this stage)
-        uint64_t n_pairs_max = 0;
-        for (uint64_t t = 0; t < n_queries; ++t) { const uint64_t n_q = q_off[t + 1] - q_off[t]; n_pairs_max += n_q * (n_q ? n_q - 1 : 0); }
-        pi.reserve(n_pairs_max); pj.reserve(n_pairs_max);
-    }
-    for (uint64_t t = 0; t < n_queries; ++t) {
-        const uint64_t r0 = qb->h_res_off[q_struct[t]], R = qb->h_res_off[q_struct[t] + 1] - r0;
-        const uint32_t *qi = q_index + q_off[t];
-        const uint64_t n_q = q_off[t + 1] - q_off[t];
-        {       // (written through pointers into the reserved arrays: two push_backs per pair were most of this stage for a whole-structure query's 88 k pairs)
-            const size_t at = pi.size();
-            pi.resize(at + n_q * (n_q ? n_q - 1 : 0)); pj.resize(pi.size());
-            uint32_t *wi = pi.data() + at, *wj = pj.data() + at;
-            size_t w = 0;
-            for (uint64_t a = 0; a < n_q; ++a) {
-                if (!(qi[a] < R)) continue;
-                const uint32_t ra = (uint32_t)(r0 + qi[a]);
-                for (uint64_t b = 0; b < n_q; ++b)
-                    if (a != b && qi[b] < R) { wi[w] = ra; wj[w] = (uint32_t)(r0 + qi[b]); ++w; }
-            }
-            pi.resize(at + w); pj.resize(at + w);
-        }
-        pair_off[t + 1] = pi.size();
-    }
-    const uint64_t np = pi.size();
-    if (qtrace) fprintf(stderr, "[fdgpu_query_map] pairs listed at %.3f ms\n", q_ms());
-    std::vector<float> feat_v;
-    std::vector<uint8_t> valid_v;
-    CHECK_TYPE(c, p);
-    uint8_t *feat_land = nullptr;
-    feat_v.reserve(16); valid_v.reserve(16);
-    int rc = 0;
-    {
-        // try the landing block first; the vectors only when it cannot be had
-        rc = pair_features12(c, qb, pi.data(), pj.data(), np, p, nullptr, nullptr, &feat_land);
-        if (!rc && np && !feat_land) {
-            feat_v.resize(np * FD_QF); valid_v.resize(np);
-            rc = pair_features12(c, qb, pi.data(), pj.data(), np, p, feat_v.data(), valid_v.data());
-        }
-    }
+    qm_request R = {c, qb, n_queries, q_struct, q_off, q_index, subs, n_subs, dist_thr, n_dist, angle_thr_deg, n_angle, p, index, total_structures, out};
+    int rc = qm_read_request(R);
     if (rc) return rc;
-    const float *feat = feat_land ? (const float *)feat_land : feat_v.data();
-    const uint8_t *valid = feat_land ? feat_land + np * 4 * FD_QF : valid_v.data();
-    if (qtrace) fprintf(stderr, "[fdgpu_query_map] %llu pairs: features at %.3f ms\n", (unsigned long long)np, q_ms());
-    const float RADS_PER_DEG = 3.14159274101257324f / 180.0f;  // f32::to_radians
-    std::vector<float> athr(n_angle);
-    for (uint64_t t = 0; t < n_angle; ++t) athr[t] = angle_thr_deg[t] * RADS_PER_DEG;
-    // candidate lists in the reference's insertion order; hashed in one GPU call, then first-insert-wins per query
-    struct cand_t { uint32_t qi, qj; uint8_t primary; uint32_t pair; };
-    std::vector<float> vf;      // FD_QF floats per candidate
-    std::vector<cand_t> cands;
-    std::vector<uint64_t> cand_off(n_queries + 1, 0);
-    {
-        uint64_t n_valid = 0;
-        for (uint64_t k = 0; k < np; ++k) n_valid += valid[k] ? 1 : 0;
-        const uint64_t per_pair = 1 + 2 * (2 * n_dist + 5 * n_angle);       // observed + near / far per threshold and field (upper bound without substitutions)
-        vf.reserve(n_valid * per_pair * FD_QF); cands.reserve(n_valid * per_pair);
-    }
-    struct Aad { std::vector<uint8_t> a1, a2; std::vector<float> ad; std::vector<uint32_t> aq; };
-    std::vector<Aad> aads(n_queries);
-    auto push = [&](const float *f, uint32_t qi, uint32_t qj, bool primary, uint32_t pair) {
-        vf.insert(vf.end(), f, f + FD_QF);
-        cands.push_back({qi, qj, (uint8_t)(primary ? 1 : 0), pair});
-    };
-    // dist_index / angle_index of the encoding (controller/feature.rs:269-291): theta only for the two PDBMotif forms — and
-    // PDBMotif shifts its DEGREE-valued theta by the threshold converted to radians, like the reference
-    static const int d23[2] = {2, 3}, d2[1] = {2}, d7[1] = {7};
-    static const int a456[3] = {4, 5, 6}, a37[5] = {3, 4, 5, 6, 7}, a345[3] = {3, 4, 5}, a06[7] = {0, 1, 2, 3, 4, 5, 6}, a48[5] = {4, 5, 6, 7, 8};
-    const int *di = d23, *ai = a456;
-    int ndi = 2, nai = 3;
-    switch (p->hash_type) {
-        case FD_HASH_PDBMOTIF: case FD_HASH_PDBMOTIF_SINCOS: nai = 1; break;
-        case FD_HASH_TRROSETTA: di = d2; ndi = 1; ai = a37; nai = 5; break;
-        case FD_HASH_PPF: di = d2; ndi = 1; ai = a345; nai = 3; break;
-        case FD_HASH_TERTIARY: di = d7; ndi = 1; ai = a06; nai = 7; break;
-        case FD_HASH_HYBRID: ai = a48; nai = 5; break;
-        default: break;
-    }
-    // ONE large query without substitutions and with one bin configuration (a whole-structure query: ~10^5 pairs, 3 x 10^5 candidates): expansion,
-    // hashes and the first-insertion-wins dedupe run on the device (k_qm_*); only the hashes and the kept positions come back.  cands / vf stay
-    // empty: candidate z is (valid pair z / per_pair, insertion z % per_pair).  FDGPU_QM_DEVICE=0: the host form (tests).
-    std::vector<uint32_t> vpairs;      // device path: the valid pairs, ascending
-    uint64_t dev_pp = 0;
-    std::vector<uint32_t> dev_keep;
-    bool dev_expand = false, dev_dedupe = false, dev_chain = false;
-    const char *qd_env_chain = getenv("FDGPU_QM_DEVICE");      // 2: device expansion without the dedupe / length chain (tests compare the forms)
-    std::vector<uint8_t> land_v;
-    const uint8_t *ch_first = nullptr;       // the chain's results per candidate (page-locked landing block, valid until this call returns)
-    const uint64_t *ch_len = nullptr; const long long *ch_kidx = nullptr; const uint32_t *ch_seg = nullptr;
-    {
-        bool any_subs = false;
-        if (subs && n_subs) for (uint64_t a = 0; a < q_off[n_queries] && !any_subs; ++a) any_subs = subs[a] != nullptr;
-        uint64_t n_valid = 0;
-        for (uint64_t k = 0; k < np; ++k) n_valid += valid[k] ? 1 : 0;
-        const uint64_t per_pair = 1 + 2 * ((uint64_t)ndi * n_dist + (uint64_t)nai * n_angle);
-        const char *qd_env = getenv("FDGPU_QM_DEVICE");
-        const uint64_t qd_min = qd_env && qd_env[0] == '1' ? 1 : 32768;      // 1: also for small queries (tests)
-        // expansion + hashes on the device whenever every candidate's place follows from its pair (no substitutions, one bin configuration): a
-        // batch of motif queries too — the host then neither builds nor uploads 48 bytes per candidate; the dedupe moves along for one large query
-        dev_expand = !any_subs && p->n_multiple_bins == 0 && n_dist <= 8 && n_angle <= 8 && !(qd_env && qd_env[0] == '0') && n_valid &&
-                     n_valid * per_pair < (1ull << 31);
-        dev_dedupe = dev_expand && n_queries == 1 && n_valid * per_pair >= qd_min;
-        if (dev_expand) { dev_pp = per_pair; vpairs.reserve(n_valid); for (uint64_t k = 0; k < np; ++k) if (valid[k]) vpairs.push_back((uint32_t)k); }
-    }
-    std::vector<uint32_t> pair_q;       // device expansion: the query of every pair
-    if (dev_expand) { pair_q.resize(np); for (uint64_t t = 0; t < n_queries; ++t) for (uint64_t k = pair_off[t]; k < pair_off[t + 1]; ++k) pair_q[k] = (uint32_t)t; }
-    uint64_t n_valid_seen = 0;
-    for (uint64_t t = 0; t < n_queries; ++t) {
-        const uint64_t r0 = qb->h_res_off[q_struct[t]];
-        const uint32_t *qidx = q_index + q_off[t];
-        const uint64_t n_q = q_off[t + 1] - q_off[t];
-        // substitution map keyed by residue index: a later entry for the same residue overrides (query.rs:236-246)
-        std::map<uint32_t, std::pair<const uint8_t *, uint32_t>> sub_of;
-        if (subs && n_subs)
-            for (uint64_t a = 0; a < n_q; ++a)
-                if (subs[q_off[t] + a]) sub_of[qidx[a]] = std::make_pair(subs[q_off[t] + a], n_subs[q_off[t] + a]);
-        Aad &A = aads[t];
-        { const size_t n_p = (size_t)(pair_off[t + 1] - pair_off[t]); A.a1.reserve(n_p); A.a2.reserve(n_p); A.ad.reserve(n_p); A.aq.reserve(n_p); }
-        if (dev_expand && pair_off[t + 1] - pair_off[t] >= 16384) {
-            // a whole-structure query on the device path: all that is left here is the observed-distance list, read from the page-locked landing block (a cache
-            // miss per pair: the copy engine wrote it) — eight parts on the context's helper threads, joined in pair order
-            constexpr unsigned NP = 8;
-            Aad part[NP];
-            uint64_t n_val[NP] = {0, 0, 0, 0, 0, 0, 0, 0};
-            const uint64_t k0 = pair_off[t], k1 = pair_off[t + 1];
-            auto scan = [&](unsigned z) {
-                Aad P;              // (locals: the parts' counters and vector headers share cache lines)
-                uint64_t nv = 0;
-                const uint64_t ka = k0 + (k1 - k0) * z / NP, kb = k0 + (k1 - k0) * (z + 1) / NP;
-                P.a1.reserve(kb - ka); P.a2.reserve(kb - ka); P.ad.reserve(kb - ka); P.aq.reserve(kb - ka);
-                for (uint64_t k = ka; k < kb; ++k) {
-                    if (!valid[k]) continue;
-                    const float *f = &feat[(size_t)FD_QF * k];
-                    if (f[9] <= 20.0f) { P.a1.push_back((uint8_t)f[10]); P.a2.push_back((uint8_t)f[11]); P.ad.push_back(f[9]); P.aq.push_back((uint32_t)(pi[k] - r0)); }
-                    ++nv;
-                }
-                part[z] = std::move(P); n_val[z] = nv;
-            };
-            std::atomic<unsigned> nxt(0);
-            const std::function<void()> wk = [&]() { for (;;) { const unsigned z = nxt.fetch_add(1); if (z >= NP) break; scan(z); } };
-            c->host_pool.run(c->small_par(NP), wk);
-            for (unsigned z = 0; z < NP; ++z) {
-                A.a1.insert(A.a1.end(), part[z].a1.begin(), part[z].a1.end()); A.a2.insert(A.a2.end(), part[z].a2.begin(), part[z].a2.end());
-                A.ad.insert(A.ad.end(), part[z].ad.begin(), part[z].ad.end()); A.aq.insert(A.aq.end(), part[z].aq.begin(), part[z].aq.end());
-                n_valid_seen += n_val[z];
-            }
-            cand_off[t + 1] = n_valid_seen * dev_pp;
-            continue;
-        }
-        for (uint64_t k = pair_off[t]; k < pair_off[t + 1]; ++k) {
-            if (!valid[k]) continue;
-            const float *f = &feat[(size_t)FD_QF * k];
-            uint32_t qi = (uint32_t)(pi[k] - r0), qj = (uint32_t)(pj[k] - r0);
-            // observed (aa_i, aa_j, CA distance) list (structure/core.rs:462-477: distance <= 20.0)
-            if (f[9] <= 20.0f) { A.a1.push_back((uint8_t)f[10]); A.a2.push_back((uint8_t)f[11]); A.ad.push_back(f[9]); A.aq.push_back(qi); }
-            if (dev_expand) { ++n_valid_seen; continue; }
-            push(f, qi, qj, true, (uint32_t)k);
-            float near[FD_QF], far[FD_QF];
-            memcpy(near, f, sizeof near);
-            memcpy(far, f, sizeof far);
-            // substitutions touch the residue fields of the container: encodings without them take none (amino_acid_index,
-            // controller/feature.rs:260-267)
-            const bool has_aa = p->hash_type != FD_HASH_TERTIARY && p->hash_type != FD_HASH_HYBRID;
-            auto si = has_aa ? sub_of.find(qi) : sub_of.end(), sj = has_aa ? sub_of.find(qj) : sub_of.end();
-            if (si != sub_of.end()) {  // apply_substitutions (query.rs:86-156)
-                for (uint32_t a = 0; a < si->second.second; ++a) { float t2[FD_QF]; memcpy(t2, near, sizeof t2); t2[0] = (float)si->second.first[a]; push(t2, qi, qj, false, (uint32_t)k); }
-                if (sj != sub_of.end())
-                    for (uint32_t a = 0; a < si->second.second; ++a)
-                        for (uint32_t b = 0; b < sj->second.second; ++b) {
-                            float t2[FD_QF]; memcpy(t2, near, sizeof t2);
-                            t2[0] = (float)si->second.first[a]; t2[1] = (float)sj->second.first[b];
-                            push(t2, qi, qj, false, (uint32_t)k);
-                        }
-            } else if (sj != sub_of.end()) {
-                for (uint32_t b = 0; b < sj->second.second; ++b) { float t2[FD_QF]; memcpy(t2, near, sizeof t2); t2[1] = (float)sj->second.first[b]; push(t2, qi, qj, false, (uint32_t)k); }
-            }
-            auto expand = [&](const int *idxs, int n_idx, const float *thr, uint64_t n_thr) {  // expand_and_insert (query.rs:179-206)
-                for (uint64_t z2 = 0; z2 < n_thr; ++z2)
-                    for (int z = 0; z < n_idx; ++z) {
-                        int idx = idxs[z];
-                        near[idx] = near[idx] - thr[z2];
-                        far[idx] = far[idx] + thr[z2];
-                        push(near, qi, qj, false, (uint32_t)k);
-                        push(far, qi, qj, false, (uint32_t)k);
-                        // the reference restores with += / -= (f32, not an exact inverse): keep the drift
-                        near[idx] = near[idx] + thr[z2];
-                        far[idx] = far[idx] - thr[z2];
-                    }
-            };
-            expand(di, ndi, dist_thr, n_dist);
-            expand(ai, nai, athr.data(), n_angle);
-        }
-        cand_off[t + 1] = dev_expand ? n_valid_seen * dev_pp : cands.size();
-    }
-    const uint64_t nc = dev_expand ? vpairs.size() * dev_pp : cands.size();
-    // candidate z -> (query residues, observed?, pair): stored by the host expansion, implied by the position on the device path
-    auto cand_at = [&](uint64_t z) -> cand_t {
-        if (!dev_expand) return cands[z];
-        const uint32_t k = vpairs[z / dev_pp];
-        const uint64_t r0 = qb->h_res_off[q_struct[pair_q[k]]];
-        return cand_t{(uint32_t)(pi[k] - r0), (uint32_t)(pj[k] - r0), (uint8_t)(z % dev_pp == 0 ? 1 : 0), k};
-    };
-    if (qtrace) fprintf(stderr, "[fdgpu_query_map] %llu candidates expanded at %.3f ms\n", (unsigned long long)nc, q_ms());
-    std::vector<uint32_t> hashes(std::max<uint64_t>(nc, 1));
-    if (dev_expand && nc) {
-        hipStream_t st = c->stream;
-        const uint64_t nv = vpairs.size();
-        qm_expand_par P;
-        memset(&P, 0, sizeof P);
-        for (int z = 0; z < ndi; ++z) P.di[z] = di[z];
-        for (int z = 0; z < nai; ++z) P.ai[z] = ai[z];
-        P.ndi = ndi; P.nai = nai; P.n_dist = (uint32_t)n_dist; P.n_angle = (uint32_t)n_angle; P.per_pair = (uint32_t)dev_pp;
-        for (uint64_t z = 0; z < n_dist; ++z) P.dthr[z] = dist_thr[z];
-        for (uint64_t z = 0; z < n_angle; ++z) P.athr[z] = athr[z];
-        // ws[WS_MISC2] still holds the pairs' containers (pair_features12); the sort takes the build's key / id buffers
-        HIPCHK(c, c->ws[WS_MISC0].ensure(nv * 4));
-        HIPCHK(c, c->ws[WS_MISC1].ensure(nc * 4));
-        if (!dev_dedupe) {
-            // a motif batch: expansion + hashes -> per-query first-insertion dedupe (k_qm_dedupe) -> posting lengths, segment counts and list
-            // positions of EVERY candidate's hash (the index's length table; 17 k lookups per 128 queries) — three kernels back to back, one
-            // landing block, one wait; the host neither dedupes nor makes a second round trip for the lengths.  Without the chain's
-            // preconditions: hashes only, the rest on the host as before.
-            uint64_t max_ins = 0;
-            for (uint64_t t = 0; t < n_queries; ++t) max_ins = std::max(max_ins, cand_off[t + 1] - cand_off[t]);
-            dev_chain = max_ins <= QM_DD_MAX && !(qd_env_chain && qd_env_chain[0] == '2');
-            const bool chain_len = dev_chain && index && index->lens && index->n_hashes && index->n_structures;
-            const size_t up_words = nv + 2 * (n_queries + 1) + 2;
-            uint32_t *up = (uint32_t *)c->host_pinned(3, up_words * 4);
-            std::vector<uint32_t> up_v;
-            if (!up) { up_v.resize(up_words); up = up_v.data(); }
-            const size_t o_off = (nv + 1) & ~(size_t)1;      // 8-byte aligned
-            memcpy(up, vpairs.data(), nv * 4);
-            memcpy(up + o_off, cand_off.data(), (n_queries + 1) * 8);
-            HIPCHK(c, c->ws[WS_MISC0].ensure(up_words * 4));
-            // the chain's outputs in ONE device block laid out like the landing block — [len u64 | kidx i64 | hash u32 | nseg u32 | first u8] x nc —
-            // so that they come home in one copy launch (they were five)
-            HIPCHK(c, c->ws[WS_MISC1].ensure(nc * 25 + 64));
-            uint8_t *d_blk = c->ws[WS_MISC1].as<uint8_t>();
-            uint64_t *d_len = (uint64_t *)d_blk;
-            long long *d_kidx = (long long *)(d_blk + nc * 8);
-            uint32_t *d_hash = (uint32_t *)(d_blk + nc * 16), *d_nseg = (uint32_t *)(d_blk + nc * 20);
-            uint8_t *d_first = d_blk + nc * 24;
-            HIPCHK(c, hipMemcpyAsync(c->ws[WS_MISC0].p, up, up_words * 4, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_qm_expand_hash, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st, c->ws[WS_MISC2].as<float>(), c->ws[WS_MISC0].as<uint32_t>(), (uint32_t)nv, P,
-                               fd_make_consts(p).q, d_hash);
-            if (dev_chain)
-                hipLaunchKernelGGL(k_qm_dedupe, dim3((unsigned)n_queries), dim3(256), 0, st, d_hash, (const uint64_t *)(c->ws[WS_MISC0].as<uint32_t>() + o_off), d_first);
-            if (chain_len) fd_launch_posting_lookup(index->hashes, index->offsets, index->lens, index->n_hashes, d_hash, nc, d_len, d_nseg, d_kidx, st);
-            HIPCHK(c, hipGetLastError());
-            uint8_t *land = (uint8_t *)c->host_pinned(2, nc * 25 + 64);
-            if (!land) { land_v.resize(nc * 25 + 64); land = land_v.data(); }
-            if (chain_len) HIPCHK(c, hipMemcpyAsync(land, d_blk, nc * 25, hipMemcpyDeviceToHost, st));
-            else HIPCHK(c, hipMemcpyAsync(land + nc * 16, d_blk + nc * 16, dev_chain ? nc * 9 : nc * 4, hipMemcpyDeviceToHost, st));      // hashes (and first-insertion flags; the segment counts between them are not read)
-            HIPCHK(c, hipStreamSynchronize(st));
-            memcpy(hashes.data(), land + nc * 16, nc * 4);
-            if (dev_chain) ch_first = land + nc * 24;
-            if (chain_len) { ch_len = (const uint64_t *)land; ch_kidx = (const long long *)(land + nc * 8); ch_seg = (const uint32_t *)(land + nc * 20); }
-        } else {
-        HIPCHK(c, c->ws[WS_KEYS_A].ensure(nc * 4)); HIPCHK(c, c->ws[WS_KEYS_B].ensure(nc * 4));
-        HIPCHK(c, c->ws[WS_IDS_A].ensure(nc * 4)); HIPCHK(c, c->ws[WS_IDS_B].ensure(nc * 4));
-        HIPCHK(c, c->ws[WS_GHIST].ensure((size_t)256 * std::max<uint32_t>(fd_rs_num_tiles(nc), 1) * 4));
-        HIPCHK(c, c->ws[WS_TOT].ensure((256 + (size_t)(fd_rs_num_tiles(nc) / 128 + 2) * 256) * 8));
-        HIPCHK(c, c->ws[WS_MISC4].ensure(nc + 8));
-        HIPCHK(c, c->ws[WS_TILE_BO].ensure((nc + 2) * 8));
-        HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(nc) * 8 + 64));
-        HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
-        HIPCHK(c, hipMemcpyAsync(c->ws[WS_MISC0].p, vpairs.data(), nv * 4, hipMemcpyHostToDevice, st));
-        uint32_t *d_hash = c->ws[WS_MISC1].as<uint32_t>();
-        hipLaunchKernelGGL(k_qm_expand_hash, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st, c->ws[WS_MISC2].as<float>(), c->ws[WS_MISC0].as<uint32_t>(), (uint32_t)nv, P,
-                           fd_make_consts(p).q, d_hash);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(hashes.data(), d_hash, nc * 4, hipMemcpyDeviceToHost, st));
-        // first insertion wins: stable sort of (hash, position) by hash, first of every run marked, marks compacted in position order
-        uint32_t *ka = c->ws[WS_KEYS_A].as<uint32_t>(), *kb = c->ws[WS_KEYS_B].as<uint32_t>(), *va = c->ws[WS_IDS_A].as<uint32_t>(), *vb = c->ws[WS_IDS_B].as<uint32_t>();
-        const unsigned gb = (unsigned)((nc + 255) / 256);
-        HIPCHK(c, hipMemcpyAsync(ka, d_hash, nc * 4, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_qm_iota, dim3(gb), dim3(256), 0, st, va, nc);
-        const int cur = fd_radix_sort_pairs(ka, va, kb, vb, nc, 32, c->ws[WS_GHIST].as<uint32_t>(), c->ws[WS_TOT].as<uint64_t>(), st, nullptr);
-        uint8_t *d_first = c->ws[WS_MISC4].as<uint8_t>();
-        HIPCHK(c, hipMemsetAsync(d_first, 0, nc, st));
-        hipLaunchKernelGGL(k_qm_first, dim3(gb), dim3(256), 0, st, cur ? kb : ka, cur ? vb : va, nc, d_first);
-        fd_exclusive_scan<uint8_t>(d_first, nc, c->ws[WS_TILE_BO].as<uint64_t>(), c->ws[WS_SCANTMP].as<uint64_t>(), c->ws[WS_TOTAL].as<uint64_t>(), st);
-        uint32_t *d_keep = cur ? ka : kb;      // the sort's other buffer is free again
-        hipLaunchKernelGGL(k_qm_keep, dim3(gb), dim3(256), 0, st, d_first, c->ws[WS_TILE_BO].as<uint64_t>(), nc, d_keep);
-        HIPCHK(c, hipGetLastError());
-        uint64_t nk = 0;
-        HIPCHK(c, hipMemcpyAsync(&nk, c->ws[WS_TOTAL].p, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        dev_keep.resize(nk);
-        if (nk) HIPCHK(c, hipMemcpy(dev_keep.data(), d_keep, nk * 4, hipMemcpyDeviceToHost));
-        }
-    } else
-    if ((rc = hash_features_q(c, vf.data(), nc, fd_make_consts(p).q, hashes.data(), FD_QF))) return rc;
-    // --multiple-bins: every candidate is inserted under every bin pair, in list order (insert_binned_hash, query.rs:59-70); the
-    // observed hash idf is looked up for stays the single-configuration one (query.rs:283-288)
-    const uint32_t n_cfg = p->n_multiple_bins ? p->n_multiple_bins : 0u;
-    if (!fd_multiple_bins_valid(p)) { c->err = "multiple_bins: at most 8 (dist, angle) bin pairs, no zero counts"; return FDGPU_EINVAL; }
-    std::vector<std::vector<uint32_t>> mh_cfg(n_cfg);
-    for (uint32_t k = 0; k < n_cfg; ++k) {
-        mh_cfg[k].resize(std::max<uint64_t>(nc, 1));
-        if ((rc = hash_features_q(c, vf.data(), nc, fd_make_consts_cfg(p, k).q, mh_cfg[k].data(), FD_QF))) return rc;
-    }
-    if (qtrace) fprintf(stderr, "[fdgpu_query_map] hashed at %.3f ms\n", q_ms());
-    std::vector<uint32_t> pair_primary(std::max<uint64_t>(np, 1), 0u);
-    if (dev_expand) { for (uint64_t v = 0; v < vpairs.size(); ++v) pair_primary[vpairs[v]] = hashes[v * dev_pp]; }
-    else
-    for (uint64_t t = 0; t < nc; ++t)
-        if (cands[t].primary) pair_primary[cands[t].pair] = hashes[t];
-    // first insertion wins (the reference's hash map keeps the entry a hash was first inserted with).  Few candidates: a hash set;
-    // many (whole-structure queries, ~10^5): (hash << 32 | insertion position) keys through an LSD radix sort, first key of every
-    // hash kept, survivors back in insertion order — a third of the hash set's time there
-    const uint64_t ncfg1 = std::max(n_cfg, 1u);
-    std::vector<uint64_t> dd_tab;
-    std::vector<std::vector<uint32_t>> keeps(n_queries);      // per query: insertion positions (candidate * n_cfg + bin pair) that enter the map, ascending
-    uint64_t n_keep = 0;
-    for (uint64_t t = 0; t < n_queries; ++t) {
-        const uint64_t c0 = cand_off[t], c1 = cand_off[t + 1], n_ins = (c1 - c0) * ncfg1;
-        auto hash_at = [&](uint64_t pos) { const uint64_t z = c0 + pos / ncfg1; const uint32_t k = (uint32_t)(pos % ncfg1); return n_cfg ? mh_cfg[k][z] : hashes[z]; };
-        std::vector<uint32_t> &keep = keeps[t];
-        if (dev_dedupe) keep.swap(dev_keep);
-        else if (ch_first) { keep.reserve((size_t)n_ins / 2 + 8); for (uint64_t pos = 0; pos < n_ins; ++pos) if (ch_first[c0 + pos]) keep.push_back((uint32_t)pos); }
-        else if (n_ins <= 4096) {      // a motif query's few hundred insertions: a small open-addressing table (a node-based set cost 3x this)
-            uint32_t cap = 64;
-            while (cap < 2 * n_ins) cap <<= 1;
-            dd_tab.assign(cap, ~0ull);
-            keep.reserve((size_t)n_ins);
-            const uint32_t *h1 = n_cfg ? nullptr : hashes.data() + c0;       // one bin configuration: position = candidate (no division per insertion)
-            for (uint64_t pos = 0; pos < n_ins; ++pos) {
-                const uint32_t h = h1 ? h1[pos] : hash_at(pos);
-                uint32_t at = (h * 2654435761u) & (cap - 1);
-                while (dd_tab[at] != ~0ull && (uint32_t)dd_tab[at] != h) at = (at + 1) & (cap - 1);
-                if (dd_tab[at] == ~0ull) { dd_tab[at] = h; keep.push_back((uint32_t)pos); }
-            }
-        } else if (n_ins >= (1ull << 32)) {
-            std::unordered_set<uint32_t> have;
-            have.reserve((size_t)n_ins / 4 + 16);
-            for (uint64_t pos = 0; pos < n_ins; ++pos) if (have.insert(hash_at(pos)).second) keep.push_back((uint32_t)pos);
-        } else {
-            std::vector<uint64_t> key(n_ins), tmp(n_ins);
-            for (uint64_t pos = 0; pos < n_ins; ++pos) key[pos] = ((uint64_t)hash_at(pos) << 32) | pos;
-            for (int pass = 0; pass < 4; ++pass) {
-                const int sh = 32 + 8 * pass;
-                size_t cnt[257] = {0};
-                for (uint64_t k = 0; k < n_ins; ++k) ++cnt[((key[k] >> sh) & 255u) + 1];
-                for (int d = 0; d < 256; ++d) cnt[d + 1] += cnt[d];
-                for (uint64_t k = 0; k < n_ins; ++k) tmp[cnt[(key[k] >> sh) & 255u]++] = key[k];
-                key.swap(tmp);
-            }
-            std::vector<uint8_t> first(n_ins, 0);      // the stable sort left every hash's earliest insertion first: mark, then walk in order
-            for (uint64_t k = 0; k < n_ins; ++k) if (k == 0 || (key[k] >> 32) != (key[k - 1] >> 32)) first[(uint32_t)key[k]] = 1;
-            for (uint64_t pos = 0; pos < n_ins; ++pos) if (first[pos]) keep.push_back((uint32_t)pos);
-        }
-        n_keep += keep.size();
-    }
-    if (qtrace) fprintf(stderr, "[fdgpu_query_map] first insertions at %.3f ms\n", q_ms());
-    // ONE posting-length pass: the observed (primary) hash of every pair — idf = log2(S / len), query.rs:17-32 — and every entry that
-    // enters a map; the maps remember the latter (post_len / post_seg) so that scoring them needs no second pass over the same lists
-    std::vector<float> pair_idf(std::max<uint64_t>(np, 1), 0.0f);
-    std::vector<uint64_t> ent_len;
-    std::vector<uint32_t> ent_seg;
-    std::vector<long long> ent_kidx;
-    const uint64_t *e_len = nullptr; const uint32_t *e_seg = nullptr; const long long *e_kidx = nullptr;      // the three arrays as the loops read them (the vectors, or the landing block)
-    if (index) {
-        std::vector<uint32_t> ph, pk;
-        ph.reserve(n_keep + np);
-        for (uint64_t t = 0; t < n_queries; ++t) {
-            const uint64_t c0 = cand_off[t];
-            if (!n_cfg) { for (uint32_t pos : keeps[t]) ph.push_back(hashes[c0 + pos]); }
-            else for (uint32_t pos : keeps[t]) { const uint64_t z = c0 + pos / ncfg1; ph.push_back(mh_cfg[pos % ncfg1][z]); }
-        }
-        if (dev_expand) { for (uint64_t v = 0; v < vpairs.size(); ++v) { ph.push_back(hashes[v * dev_pp]); pk.push_back(vpairs[v]); } }
-        else
-        for (uint64_t t = 0; t < nc; ++t)
-            if (cands[t].primary) { ph.push_back(hashes[t]); pk.push_back(cands[t].pair); }
-        ent_len.assign(std::max<size_t>(ph.size(), 1), 0);
-        ent_seg.assign(std::max<size_t>(ph.size(), 1), 0);
-        ent_kidx.assign(std::max<size_t>(ph.size(), 1), -1);
-        e_len = ent_len.data(); e_seg = ent_seg.data(); e_kidx = ent_kidx.data();
-        if (ch_len) {      // the chain looked every candidate up: pick the kept entries and the observed hashes, in ph's order
-            size_t w = 0;
-            for (uint64_t t = 0; t < n_queries; ++t) {
-                const uint64_t c0 = cand_off[t];
-                for (uint32_t pos : keeps[t]) { const uint64_t z = c0 + pos; ent_len[w] = ch_len[z]; ent_seg[w] = ch_seg[z]; ent_kidx[w] = ch_kidx[z]; ++w; }
-            }
-            for (uint64_t v = 0; v < vpairs.size(); ++v, ++w) { const uint64_t z = v * dev_pp; ent_len[w] = ch_len[z]; ent_seg[w] = ch_seg[z]; ent_kidx[w] = ch_kidx[z]; }
-        } else
-        {
-            const uint8_t *pl_land = nullptr;       // large requests stay in the page-locked block (read once, in place, by the loops below)
-            if ((rc = fd_posting_lengths_segs(c, index, ph.data(), ph.size(), ent_len.data(), ent_seg.data(), ent_kidx.data(), ph.size() >= 16384 ? &pl_land : nullptr))) return rc;
-            if (pl_land) { e_len = (const uint64_t *)pl_land; e_kidx = (const long long *)(pl_land + ph.size() * 8); e_seg = (const uint32_t *)(pl_land + ph.size() * 16); }
-        }
-        // idf of the observed hash of every pair: log2f is ~8 ns a call — 0.7 ms for the 88 k pairs of a whole-structure query on one thread
-        auto idf_range = [&](size_t a, size_t b) {
-            for (size_t t = a; t < b; ++t) pair_idf[pk[t]] = e_len[n_keep + t] > 0 ? log2f(total_structures / (float)e_len[n_keep + t]) : 0.0f;
-        };
-        if (pk.size() < 16384) idf_range(0, pk.size());
-        else {
-            const unsigned nt = 8;
-            std::atomic<unsigned> part(0);
-            const std::function<void()> w = [&]() { for (;;) { const unsigned k = part.fetch_add(1); if (k >= nt) break; idf_range(pk.size() * k / nt, pk.size() * (k + 1) / nt); } };
-            c->host_pool.run(std::min(nt, std::max(1u, std::thread::hardware_concurrency())), w);
-        }
-    }
-    if (qtrace) fprintf(stderr, "[fdgpu_query_map] posting lengths at %.3f ms\n", q_ms());
-    uint64_t keep_at = 0;
-    for (uint64_t t = 0; t < n_queries; ++t) {
-        const uint64_t c0 = cand_off[t];
-        auto hash_at = [&](uint64_t pos) { const uint64_t z = c0 + pos / ncfg1; const uint32_t k = (uint32_t)(pos % ncfg1); return n_cfg ? mh_cfg[k][z] : hashes[z]; };
-        const std::vector<uint32_t> &keep = keeps[t];
-        const Aad &A = aads[t];
-        // the map and all its arrays in ONE block (fd_query_map.arena_bytes != 0: fdgpu_query_map_free releases the block; a map was 15
-        // allocations, a batch of 128 queries two thousand)
-        const size_t n = keep.size(), n_idx = (size_t)(q_off[t + 1] - q_off[t]), n_aad = A.ad.size();
-        const bool with_post = index && n;
-        auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        const size_t o_hash = up16(sizeof(fd_query_map)), o_qi = o_hash + up16(n * 4), o_qj = o_qi + up16(n * 4), o_idf = o_qj + up16(n * 4), o_ph = o_idf + up16(n * 4),
-                     o_pl = o_ph + up16(n * 4), o_pk = o_pl + (with_post ? up16(n * 8) : 0), o_ps = o_pk + (with_post ? up16(n * 8) : 0),
-                     o_idx = o_ps + (with_post ? up16(n * 4) : 0), o_ad = o_idx + up16(n_idx * 4), o_aq = o_ad + up16(n_aad * 4), o_prim = o_aq + up16(n_aad * 4),
-                     o_a1 = o_prim + up16(n), o_a2 = o_a1 + up16(n_aad), bytes = o_a2 + up16(n_aad) + 16;
-        uint8_t *blk = (uint8_t *)malloc(bytes);
-        if (!blk) { for (uint64_t u = 0; u < t; ++u) { fdgpu_query_map_free(out[u]); out[u] = nullptr; } return FDGPU_ENOMEM; }
-        fd_query_map *m = (fd_query_map *)blk;
-        memset(m, 0, sizeof *m);
-        m->arena_bytes = bytes;
-        m->n = n;
-        m->hash = (uint32_t *)(blk + o_hash); m->qi = (uint32_t *)(blk + o_qi); m->qj = (uint32_t *)(blk + o_qj); m->idf = (float *)(blk + o_idf);
-        m->primary_hash = (uint32_t *)(blk + o_ph); m->is_primary = blk + o_prim;
-        uint32_t *const o_hash_p = m->hash, *const o_qi_p = m->qi, *const o_qj_p = m->qj, *const o_ph_p = m->primary_hash;
-        uint8_t *const o_pr_p = m->is_primary;
-        float *const o_idf_p = m->idf;
-        size_t w = 0;
-        if (dev_expand && !n_cfg) {       // kept positions ascend: the pair a position belongs to advances with them (no division per entry)
-            const uint64_t r0 = qb->h_res_off[q_struct[t]];
-            auto fill = [&](size_t a, size_t b) {       // entries [a, b) of the map
-                if (a >= b) return;
-                uint64_t v = (c0 + keep[a]) / dev_pp, v_end = (v + 1) * dev_pp;      // candidates of valid pair v: [v * dev_pp, v_end)
-                for (size_t e = a; e < b; ++e) {
-                    const uint64_t z = c0 + keep[e];
-                    while (z >= v_end) { ++v; v_end += dev_pp; }
-                    const uint32_t k = vpairs[v];
-                    o_hash_p[e] = hashes[z]; o_qi_p[e] = (uint32_t)(pi[k] - r0); o_qj_p[e] = (uint32_t)(pj[k] - r0); o_pr_p[e] = z + dev_pp == v_end ? 1 : 0;
-                    o_idf_p[e] = pair_idf[k]; o_ph_p[e] = pair_primary[k];
-                }
-            };
-            if (n < 16384) fill(0, n);
-            else {       // a whole-structure query's ~10^5 entries: eight parts on the context's helper threads (0.5 ms of the call on one)
-                const unsigned nt = 8;
-                std::atomic<unsigned> part(0);
-                const std::function<void()> wk = [&]() { for (;;) { const unsigned k = part.fetch_add(1); if (k >= nt) break; fill(n * k / nt, n * (k + 1) / nt); } };
-                c->host_pool.run(c->small_par(nt), wk);
-            }
-            w = n;
-        } else
-        for (uint32_t pos : keep) {
-            const uint64_t z = c0 + pos / ncfg1;
-            const cand_t cz = cand_at(z);
-            o_hash_p[w] = hash_at(pos); o_qi_p[w] = cz.qi; o_qj_p[w] = cz.qj; o_pr_p[w] = cz.primary;
-            o_idf_p[w] = pair_idf[cz.pair]; o_ph_p[w] = pair_primary[cz.pair];
-            ++w;
-        }
-        if (with_post) {
-            m->post_len = (uint64_t *)(blk + o_pl); m->post_kidx = (long long *)(blk + o_pk); m->post_seg = (uint32_t *)(blk + o_ps);
-            memcpy(m->post_len, e_len + keep_at, n * 8); memcpy(m->post_seg, e_seg + keep_at, n * 4); memcpy(m->post_kidx, e_kidx + keep_at, n * 8);
-            m->post_index_uid = index->uid;
-        }
-        keep_at += n;
-        m->n_indices = n_idx; m->indices = (uint32_t *)(blk + o_idx);
-        if (n_idx) memcpy(m->indices, q_index + q_off[t], n_idx * 4);
-        m->n_aad = n_aad; m->aad_dist = (float *)(blk + o_ad); m->aad_qi = (uint32_t *)(blk + o_aq); m->aad_aa1 = blk + o_a1; m->aad_aa2 = blk + o_a2;
-        if (n_aad) { memcpy(m->aad_dist, A.ad.data(), n_aad * 4); memcpy(m->aad_qi, A.aq.data(), n_aad * 4); memcpy(m->aad_aa1, A.a1.data(), n_aad); memcpy(m->aad_aa2, A.a2.data(), n_aad); }
-        out[t] = m;
-    }
-    if (qtrace) fprintf(stderr, "[fdgpu_query_map] maps built at %.3f ms\n", q_ms());
+    qm_pairs P;
+    qm_list_pairs(n_queries, q_struct, q_off, q_index, qb->h_res_off.data(), P);
+    if (R.trace) fprintf(stderr, "[fdgpu_query_map] pairs listed at %.3f ms\n", R.ms());
+    qm_feat_store FS;
+    qm_feat F;
+    if ((rc = qm_pair_features(R, P, FS, F))) return rc;
+    if (R.trace) fprintf(stderr, "[fdgpu_query_map] %llu pairs: features at %.3f ms\n", (unsigned long long)P.pi.size(), R.ms());
+    const qm_form form = qm_choose_form(R, P, F);
+    qm_work W;
+    qm_observed_lists(R, P, F, form, W);
+    if (form.dev_expand) qm_implied_candidates(R, P, F, form, W);
+    else qm_host_candidates(R, P, F, form, W);
+    if (R.trace) fprintf(stderr, "[fdgpu_query_map] %llu candidates expanded at %.3f ms\n", (unsigned long long)W.nc, R.ms());
+    qm_hashed H;
+    if ((rc = qm_hash_candidates(R, form, W, H))) return rc;
+    if (R.trace) fprintf(stderr, "[fdgpu_query_map] hashed at %.3f ms\n", R.ms());
+    qm_kept K;
+    qm_first_insertions(R, form, W, H, K);
+    if (R.trace) fprintf(stderr, "[fdgpu_query_map] first insertions at %.3f ms\n", R.ms());
+    qm_lengths L;
+    if ((rc = qm_posting_lengths(R, P, form, W, H, K, L))) return rc;
+    if (R.trace) fprintf(stderr, "[fdgpu_query_map] posting lengths at %.3f ms\n", R.ms());
+    if ((rc = qm_assemble(R, P, form, W, H, K, L))) return rc;
+    if (R.trace) fprintf(stderr, "[fdgpu_query_map] maps built at %.3f ms\n", R.ms());
     return FDGPU_OK;
 }
 
@@ -794,4 +687,10 @@ extern "C" int fdgpu_make_query_map(fdgpu_ctx *c, const fdgpu_batch *qb, const u
     const uint32_t s0 = 0;
     const uint64_t off[2] = {0, n_q};
     return fdgpu_make_query_map_batch(c, qb, 1, &s0, off, q_index, subs, n_subs, dist_thr, n_dist, angle_thr_deg, n_angle, p, index, total_structures, out);
+}
+
+extern "C" int fdgpu_debug_last_query_map_path(fdgpu_ctx *c, uint32_t *flags) { FD_LOCK(c);
+    if (!c || !flags) return FDGPU_EINVAL;
+    *flags = c->last_query_map_path;
+    return FDGPU_OK;
 }

@@ -186,7 +186,7 @@ extern "C" void fdgpu_destroy(fdgpu_ctx *c) {
     for (auto &b : c->pool) (void)hipFree(b.p);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     for (int k = 0; k < 16; ++k) { if (c->pin[k]) (void)hipHostFree(c->pin[k]); if (c->pin_ev[k]) (void)hipEventDestroy(c->pin_ev[k]); }
-    for (int k = 0; k < 6; ++k) if (c->hbuf[k]) (void)hipHostFree(c->hbuf[k]);
+    for (int k = 0; k < FD_HP_SLOTS; ++k) if (c->hbuf[k]) (void)hipHostFree(c->hbuf[k]);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     const bool last = c->counted && fd_live_contexts.fetch_sub(1) == 1;

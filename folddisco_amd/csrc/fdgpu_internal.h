@@ -49,6 +49,20 @@ enum {
     WS_COUNT
 };
 
+// The context's page-locked host blocks (fdgpu_ctx::host_pinned): each grows on demand and is held by ONE stage at a time — a stage that asks for a
+// slot may move it, so two stages whose use overlaps never share one.  Who holds which, and until when (a fused query call runs query map -> count
+// -> pair scan -> retrieval):
+enum fd_hp_slot {
+    FD_HP_SCAN_A,       // pair scan: its table block on the way up (until the scan's first launch has it); a packed scan's keys (until the next packed scan)
+    FD_HP_SCAN_B,       // pair scan: a packed scan's values (as above); retrieval: the two offset arrays of the device glue (until they are parted, same call)
+    FD_HP_LAND,         // query map: the chain's landing block, read in place until the map call returns; retrieval: the device glue's upload block (until uploaded)
+    FD_HP_UP,           // query map: the chain's upload block (until the chain's wait), then the landing block of its posting-length lookup (until the map call
+                        // returns); count: the posting-length landing block and the candidates' head records — only after the maps exist
+    FD_HP_FEAT,         // query map: the pair features' landing block, read in place until the map call returns; nobody else
+    FD_HP_PAIRS,        // query map: the pairs' (i, j) on the way up (until the features' wait); count: the tiled form's upload block — only after the maps exist
+    FD_HP_SLOTS
+};
+
 struct fdgpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -56,6 +70,7 @@ struct fdgpu_ctx {
     std::string err;
     uint32_t last_retrieve_path = 0;       // FDGPU_RPATH_* decisions of the last fdgpu_retrieve_batch call (fdgpu_debug_last_retrieve_path)
     uint32_t last_count_path = 0;          // FDGPU_PATH_* decisions of the last count call (fdgpu_debug_last_count_path: tests at the dispatch's switches)
+    uint32_t last_query_map_path = 0;      // FDGPU_QMPATH_* of the last query-map call that reached qm_choose_form (fdgpu_debug_last_query_map_path)
     fd_devbuf ws[WS_COUNT];
     bool timing = false;
     // Every entry point that takes the context locks it: concurrent callers (the reference calls its seams from rayon workers,
@@ -71,9 +86,9 @@ struct fdgpu_ctx {
     // pinned host buffers that outlive a call (the packed candidate pairs of a whole-structure retrieval: 2 x ~100 MB per call — as
     // malloc'd blocks their first-touch page faults and their munmap cost more than the copy)
     hipStream_t side_stream = nullptr;      // second stream of the fused query call: the ranked records travel to the host while the retrieval's kernels run
-    void *hbuf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0, 1: retrieval; 2, 3: landing / upload blocks of the query-map stage; 4: its pair features; 5: their (i, j) upload
-    size_t hbuf_cap[6] = {0, 0, 0, 0, 0, 0};
-    void *host_pinned(int k, size_t bytes) {
+    void *hbuf[FD_HP_SLOTS] = {};
+    size_t hbuf_cap[FD_HP_SLOTS] = {};
+    void *host_pinned(fd_hp_slot k, size_t bytes) {
         if (hbuf_cap[k] >= bytes) return hbuf[k];
         if (hbuf[k]) (void)hipHostFree(hbuf[k]);
         hbuf[k] = nullptr; hbuf_cap[k] = 0;

@@ -99,6 +99,44 @@ int fdgpu_debug_last_count_path(fdgpu_ctx *ctx, uint32_t *flags);
 #define FDGPU_RPATH_SPLIT 32u        /* the device glue in its split form (k_rs_setup / k_rs_comp, k_rs_slots for the listed slots) */
 int fdgpu_debug_last_retrieve_path(fdgpu_ctx *ctx, uint32_t *flags);
 
+/* Which form the LAST fdgpu_make_query_map[_batch] call on this context took for "candidates -> hashes" (csrc/fd_query_map.hip, qm_choose_form: the
+ * only place that sets them).  A call refused before the form is chosen (bad arguments, hash type, multiple_bins) leaves the previous call's flags. */
+#define FDGPU_QMPATH_HOST_EXPAND 1u      /* candidates expanded on the host, their containers hashed per bin configuration */
+#define FDGPU_QMPATH_DEVICE_EXPAND 2u    /* expanded and hashed on the device (k_qm_expand_hash); alone: hashes only, first insertions and lengths on the host */
+#define FDGPU_QMPATH_CHAIN 4u            /* ... then first insertions per query in LDS (k_qm_dedupe) */
+#define FDGPU_QMPATH_CHAIN_LENGTHS 8u    /* ... and every candidate's posting length in the same chain (an index was given) */
+#define FDGPU_QMPATH_SORT_DEDUPE 16u     /* ... or, one large query: first insertions by a device sort */
+int fdgpu_debug_last_query_map_path(fdgpu_ctx *ctx, uint32_t *flags);
+
+/* The host steps of make_query_map (csrc/fd_query_map_host.cpp), callable without a context or a device.  Output arrays are released with libc free().
+ * fdgpu_debug_qm_pairs: the ordered residue pairs of queries (q_struct, q_off, q_index as fdgpu_make_query_map_batch) over a batch whose residues
+ *   start at res_off[]: *pair_i / *pair_j hold batch-wide residue indices, query t's pairs are [pair_off[t], pair_off[t + 1]) (pair_off: n_queries + 1).
+ * fdgpu_debug_qm_fields: out[12] = {n_dist_fields, dist_field[2], n_angle_fields, angle_field[7], takes substitutions}, unused entries -1.
+ * fdgpu_debug_qm_expand: the host expansion of ONE query's pairs (features[n_pairs][12], valid[n_pairs]; the query's structure starts at residue r0;
+ *   subs / n_subs parallel to q_index[n_q], or NULL; angle thresholds in RADIANS): *cand_features = [n][12], *cand_recs = [n][4] = (qi, qj, observed?, pair).
+ * fdgpu_debug_qm_first_insertions: first insertion wins over hashes[max(n_cfg, 1)][n_cands], the insertions in (candidate, bin configuration)
+ *   order (position = candidate * max(n_cfg, 1) + configuration): *keep = the kept positions, ascending.  table_max / set_min: the switches between the table, the radix
+ *   and the hash-set form (0 = the library's 4,096 and 2^32).
+ * fdgpu_debug_qm_arena: offsets[15] = byte offsets {hash, qi, qj, idf, primary_hash, post_len, post_kidx, post_seg, indices, aad_dist, aad_qi, is_primary,
+ *   aad_aa1, aad_aa2} of a map's block and its size.
+ * fdgpu_debug_qm_fill: one map (fdgpu_query_map_free) from kept positions and per-candidate / per-pair arrays: cand_recs != NULL = the host form's
+ *   stored candidates, else candidate z is insertion z % per_pair of valid pair valid_pairs[z / per_pair]; post_len NULL = no posting arrays. */
+int fdgpu_debug_qm_pairs(uint64_t n_queries, const uint32_t *q_struct, const uint64_t *q_off, const uint32_t *q_index, const uint64_t *res_off,
+                         uint32_t **pair_i, uint32_t **pair_j, uint64_t *pair_off);
+int fdgpu_debug_qm_fields(uint32_t hash_type, int32_t *out);
+int fdgpu_debug_qm_expand(const float *features, const uint8_t *valid, const uint32_t *pair_i, const uint32_t *pair_j, uint64_t n_pairs, uint64_t r0,
+                          const uint32_t *q_index, uint64_t n_q, const uint8_t *const *subs, const uint32_t *n_subs, uint32_t hash_type,
+                          const float *dist_thr, uint64_t n_dist, const float *angle_thr_rad, uint64_t n_angle, float **cand_features,
+                          uint32_t **cand_recs, uint64_t *n_cands);
+int fdgpu_debug_qm_first_insertions(const uint32_t *hashes, uint64_t n_cands, uint32_t n_cfg, uint64_t table_max, uint64_t set_min, uint32_t **keep,
+                                    uint64_t *n_keep);
+int fdgpu_debug_qm_arena(uint64_t n, uint64_t n_indices, uint64_t n_aad, uint32_t with_post, uint64_t *offsets);
+int fdgpu_debug_qm_fill(const uint32_t *keep, uint64_t n, const uint32_t *hashes, uint64_t n_cands, uint32_t n_cfg, uint64_t c0, const uint32_t *cand_recs,
+                        const uint32_t *valid_pairs, uint64_t per_pair, const uint32_t *pair_i, const uint32_t *pair_j, uint64_t r0, const float *pair_idf,
+                        const uint32_t *pair_primary, const uint64_t *post_len, const uint32_t *post_seg, const long long *post_kidx, uint64_t index_uid,
+                        const uint32_t *indices, uint64_t n_indices, const uint8_t *aad_aa1, const uint8_t *aad_aa2, const float *aad_dist,
+                        const uint32_t *aad_qi, uint64_t n_aad, uint32_t pooled, fd_query_map **out);
+
 #ifdef __cplusplus
 }
 #endif
