@@ -850,6 +850,68 @@ def cmd_neighbors(a):
               f"({sum(t.nbytes for t in tabs)} bytes)" + (f", {len(jac)} rows confirmed from their rows" if jac is not None else ""), file=sys.stderr)
 
 
+def cmd_cluster(a):
+    """`cluster`: a non-redundant subset of the index at PREFIX.  The signatures are taken as `dups` takes them and walked in the order of
+    --rep-by (hashes: the signature's n, descending; nres, plddt: that column of PREFIX.lookup, descending; id: ascending; ties by id): a
+    structure that no representative chosen so far is reported with at --min-similarity becomes a representative, any other joins its nearest
+    one (the order of `neighbors`), on the device (fdgpu_signature_clusters) or with --host on the CPU (no device is opened).  One TSV row per
+    structure with a non-empty row, sorted by (rep_id, id): rep_id rep_tid rep_n id tid n match filled estimate class[ jaccard]; class is
+    `representative`, `identical` or `similar`.  --redundant FILE gets the members' tids, one per line in id order: what `update --remove`
+    takes; it is refused when such a tid also names a kept row.  It removes nothing itself.  No structure file is read."""
+    from folddisco_amd import indexio
+    if a.rep_by not in indexio.CLUSTER_ORDER_KEYS:
+        print(f"[FAIL] cluster: unknown --rep-by key '{a.rep_by}' (one of {', '.join(indexio.CLUSTER_ORDER_KEYS)})")
+        sys.exit(1)
+    prefixes, tids = _sig_plan(a, "cluster")
+    prefix, tids = prefixes[0], tids[0]
+    thr64 = indexio.signature_threshold(a.min_similarity)
+    try:
+        rows = indexio.read_lookup_rows(prefix + ".lookup") if a.rep_by in ("nres", "plddt") else None
+        ctx = None
+        if not a.host:
+            import folddisco_amd as fd
+            ctx = fd.Context(a.device)
+        S = _dups_signatures(a, ctx, prefix, len(tids))
+        order = indexio.cluster_order(S, rows, a.rep_by)
+        cl = indexio.signature_clusters_host(S, order, thr64=thr64, threads=a.threads) if a.host else ctx.signature_clusters(S, order, thr64=thr64)
+        ids = np.arange(len(S), dtype=np.int64)
+        rep = cl["id"] == ids
+        member = ~rep & (cl["id"] != indexio.SIG_NO_ID)
+        if a.redundant:                              # `update --remove` removes every row with a listed tid: none of them may name a kept row
+            listed = {tids[p] for p in ids[member]}
+            clash = sorted({tids[p] for p in ids[~member] if tids[p] in listed})
+            if clash:
+                print(f"[FAIL] cluster: {len(clash)} tid(s) of --redundant also name a structure that is kept, and `update --remove` would remove that one too: "
+                      + ", ".join(clash[:10]) + (", ..." if len(clash) > 10 else ""))
+                sys.exit(1)
+        shown = ids[rep | member]
+        shown = shown[np.lexsort((shown, cl["id"][shown]))]
+        jac = _dups_jaccard(a, ctx, prefixes, [tids], cl["id"][shown[member[shown]]], shown[member[shown]]) if a.confirm else None
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] cluster: {e}", file=sys.stderr)
+        sys.exit(2 if isinstance(e, OSError) else 1)
+    lines, j = [], 0
+    for p in shown:
+        r, rec = int(cl["id"][p]), cl[p]
+        cols = [str(r), tids[r], str(int(S["n"][r])), str(int(p)), tids[p], str(int(S["n"][p])), str(int(rec["match"])), str(int(rec["filled"])),
+                f"{int(rec['match']) / max(int(rec['filled']), 1):.4f}",
+                "representative" if rep[p] else "identical" if int(rec["flags"]) & indexio.SIG_IDENTICAL else "similar"]
+        if jac is not None:
+            cols.append("1.0000" if rep[p] else f"{jac[j]:.4f}")
+            j += 0 if rep[p] else 1
+        lines.append("\t".join(cols) + "\n")
+    _write_tsv(a.output, lines, "cluster")
+    if a.redundant:
+        _write_tsv(a.redundant, [tids[p] + "\n" for p in ids[member]], "cluster")
+    sizes = np.bincount(cl["id"][shown].astype(np.int64), minlength=max(len(S), 1))
+    n_ident = int((member & ((cl["flags"] & indexio.SIG_IDENTICAL) != 0)).sum())
+    print(f"[OK] {prefix}: {len(S)} structures, {int(rep.sum())} clusters ({int((sizes[ids[rep]] == 1).sum())} singletons), {int(member.sum())} members "
+          f"({n_ident} identical), {int((cl['id'] == indexio.SIG_NO_ID).sum())} unclustered, largest cluster {int(sizes.max())}, threshold {thr64}/64")
+    if a.verbose:
+        print(f"[INFO] cluster on the {'host' if a.host else 'device'}: signatures of {len(S)} structures ({S.nbytes} bytes), walked by {a.rep_by}"
+              + (f", {len(jac)} members confirmed from their rows" if jac is not None else ""), file=sys.stderr)
+
+
 def _reshard_plan(a):
     """everything `reshard` decides before it opens a device: -> (source prefixes, structures).  Status 2 for missing or unreadable files,
     status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
@@ -1490,6 +1552,21 @@ def main(argv=None):
     pn.add_argument("--device", type=int, default=0)
     pn.add_argument("--verify", action="store_true", help="check every loaded index first (see `verify`) and stop with status 1 if it is damaged")
     pn.add_argument("-v", "--verbose", action="store_true")
+    pk = sub.add_parser("cluster")                                   # one representative per group of similar structures, by signature (no counterpart in the reference)
+    pk.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
+    pk.add_argument("--min-similarity", type=float, default=0.9, help="a structure joins a representative whose sketch agrees with its own in at least this share of their filled buckets, in (0, 1]")
+    pk.add_argument("--rep-by", default="hashes", help="the walk order, earlier structures represent: hashes (the row's size, descending; default), nres or plddt "
+                    "(that column of PREFIX.lookup, descending), id (ascending); ties by id")
+    pk.add_argument("-o", "--output", default="", help="the TSV file to write (default: standard output)")
+    pk.add_argument("--redundant", default="", help="also write the members' tids, one per line: the file `update --remove` takes")
+    pk.add_argument("--confirm", action="store_true", help="add the exact Jaccard similarity of every member with its representative, from their rows")
+    pk.add_argument("--window", type=int, default=16384, help="structures per walk over the index")
+    pk.add_argument("--host", action="store_true", help="reduce and cluster on the CPU (no device is opened)")
+    pk.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    pk.add_argument("--device", type=int, default=0)
+    pk.add_argument("--verify", action="store_true", help="check the loaded index first (see `verify`) and stop with status 1 if it is damaged")
+    pk.add_argument("-v", "--verbose", action="store_true")
+    pk.set_defaults(against=None)                                    # what the shared planning of `dups` and `neighbors` looks at
     pr = sub.add_parser("reshard")                                   # one index <-> shards by structure id range (no counterpart in the reference)
     pr.add_argument("-i", "--index", required=True)
     pr.add_argument("--to", type=int, required=True, help="shards to write (PREFIX.shard<r>ofW); 1 writes the single index")
@@ -1566,6 +1643,9 @@ def main(argv=None):
         return
     if a.cmd == "neighbors":
         cmd_neighbors(a)
+        return
+    if a.cmd == "cluster":
+        cmd_cluster(a)
         return
     if a.cmd == "reshard":
         cmd_reshard(a)

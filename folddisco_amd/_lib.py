@@ -215,6 +215,8 @@ SYMBOLS = [
     ("fdgpu_signature_pairs_host", C.c_int, [VP, C.c_uint64, VP, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(VP), u64p]),
     ("fdgpu_signature_neighbors", C.c_int, [VP, VP, C.c_uint64, VP, C.c_uint64, VP, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_signature_neighbors_host", C.c_int, [VP, C.c_uint64, VP, C.c_uint64, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
+    ("fdgpu_signature_clusters", C.c_int, [VP, VP, C.c_uint64, VP, C.c_uint32, C.POINTER(VP)]),
+    ("fdgpu_signature_clusters_host", C.c_int, [VP, C.c_uint64, VP, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_index_verify", C.c_int, [VP, VP, C.POINTER(VerifyReportC)]),
     ("fdgpu_verify_host", C.c_int, [u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyReportC)]),
     ("fdgpu_posting_bytes", C.c_int, [VP, VP, u32p, C.c_uint64, u64p]),

@@ -152,6 +152,15 @@ class Context:
                                                     None if exclude is None else exclude.ctypes.data, k, t, C.byref(op)))
         return indexio.signature_neighbors_result(self.L, op, len(Q), k)
 
+    def signature_clusters(self, S, order=None, min_similarity: float = 0.9, thr64=None) -> np.ndarray:
+        """the greedy clusters of a signature table, selected on the device (fdgpu_signature_clusters): one indexio.SIGNATURE_NEIGHBOR_DTYPE
+        record per position; the contract of indexio.signature_clusters_host, which it equals byte for byte"""
+        from . import indexio
+        S, order, t = indexio._sig_cluster_args(S, order, min_similarity, thr64)
+        op = C.c_void_p()
+        self.check(self.L.fdgpu_signature_clusters(self.h, S.ctypes.data, len(S), None if order is None else order.ctypes.data, t, C.byref(op)))
+        return indexio.signature_clusters_result(self.L, op, len(S))
+
     # ---- batches
     def upload(self, ps: PackedStructures) -> "Batch":
         d = BatchDesc(ps.n_struct, _ptr(ps.res_off, u64p), _ptr(ps.n_xyz, f32p), _ptr(ps.ca_xyz, f32p), _ptr(ps.cb_xyz, f32p),

@@ -38,3 +38,8 @@ FD_SIG_HD bool fd_sig_nearer(uint32_t mx, uint32_t fx, uint32_t idx, uint32_t my
 }
 static_assert(sizeof(fd_sig_neighbor) == 8, "fd_sig_neighbor layout");
 #define FD_SIG_NO_ID 0xffffffffu
+
+// a walk order of the clusters must be a permutation of 0 .. n - 1 (fd_signatures_host.cpp; host code): -> n if it is one, the first entry that is
+// not below n or repeats an earlier one if not, FD_SIG_ORDER_NOMEM when the n bits of the check could not be allocated
+#define FD_SIG_ORDER_NOMEM 0xffffffffffffffffull
+uint64_t fd_sig_order_fault(const uint32_t *order, uint64_t n);

@@ -9,6 +9,10 @@
 // Pairs: a blocked double loop, threads over the blocks of A, the records sorted by (a, b) at the end.
 // Neighbours: the same blocked loop over (Q blocks x D blocks), threads over the Q blocks; every query's k-list is its row of the result, kept
 // sorted by insertion under fd_sig_nearer, so no two threads touch the same row and the result does not depend on their number.
+// Clusters: the sequential walk in blocks of 1024 positions.  Per block, threads over its positions find each one's nearest among the
+// representatives chosen BEFORE the block (a position belongs to one thread: nothing depends on their number); then the block is settled in walk
+// order on the calling thread: a position without a best becomes a representative and every later position of the block that qualifies with it
+// and finds it nearer takes it.
 #include <cstring>
 #include "fd_signature.h"
 #include "fd_postings_host.h"
@@ -170,6 +174,69 @@ extern "C" int fdgpu_signature_neighbors_host(const fd_signature *Q, uint64_t nQ
             }
         }
     });
+    *out = res;
+    return FDGPU_OK;
+}
+
+uint64_t fd_sig_order_fault(const uint32_t *order, uint64_t n) {
+    try {
+        std::vector<uint64_t> seen((n + 63) / 64, 0);
+        for (uint64_t w = 0; w < n; ++w) {
+            const uint64_t p = order[w];
+            if (p >= n || (seen[p >> 6] >> (p & 63) & 1u)) return w;
+            seen[p >> 6] |= 1ull << (p & 63);
+        }
+    } catch (...) { return FD_SIG_ORDER_NOMEM; }
+    return n;
+}
+
+extern "C" int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, uint32_t n_threads,
+                                             fd_sig_neighbor **out) {
+    if (!out) return FDGPU_EINVAL;
+    *out = nullptr;
+    if (thr64 < 1 || thr64 > 64 || n > 0xffffffffull || (n && !S)) return FDGPU_EINVAL;
+    if (order) {
+        const uint64_t w = fd_sig_order_fault(order, n);
+        if (w != n) return w == FD_SIG_ORDER_NOMEM ? FDGPU_ENOMEM : FDGPU_EINVAL;
+    }
+    fd_sig_neighbor *res = (fd_sig_neighbor *)malloc(std::max<uint64_t>(n, 1) * sizeof(fd_sig_neighbor));
+    if (!res) return FDGPU_ENOMEM;
+    const fd_sig_neighbor none = {FD_SIG_NO_ID, 0, 0, 0};
+    for (uint64_t i = 0; i < std::max<uint64_t>(n, 1); ++i) res[i] = none;
+    auto take = [&](uint64_t p, uint64_t r) {           // r, a representative, for p if the pair is reported and r is nearer than p's best
+        const sg_stat s = sig_compare(S[p], S[r]);
+        if (!fd_sig_reported(S[p].n, S[r].n, s.eq, s.E, thr64)) return;
+        const uint32_t m = s.eq - s.E, f = 64u - s.E;
+        fd_sig_neighbor &b = res[p];
+        if (!fd_sig_nearer(m, f, (uint32_t)r, b.match, b.filled, b.id)) return;
+        b.id = (uint32_t)r; b.match = (uint8_t)m; b.filled = (uint8_t)f;
+        b.flags = S[p].n == S[r].n && S[p].d0 == S[r].d0 && S[p].d1 == S[r].d1 ? FD_SIG_IDENTICAL : 0u;
+    };
+    std::vector<uint32_t> reps;
+    const uint64_t BLK = 1024;
+    try {
+        for (uint64_t w0 = 0; w0 < n; w0 += BLK) {
+            const uint64_t nb = std::min(BLK, n - w0), R = reps.size();
+            auto at = [&](uint64_t i) { return order ? (uint64_t)order[w0 + i] : w0 + i; };
+            const uint64_t T = fd_host_threads(n_threads, nb * R, 1u << 16);      // a thread is worth starting for 65,536 compares
+            fd_over_ranges(T, [&](uint64_t t) {
+                for (uint64_t i = nb * t / T; i < nb * (t + 1) / T; ++i) {
+                    const uint64_t p = at(i);
+                    if (!S[p].n) continue;
+                    for (uint64_t k = 0; k < R; ++k) take(p, reps[k]);
+                }
+            });
+            for (uint64_t i = 0; i < nb; ++i) {
+                const uint64_t p = at(i);
+                if (!S[p].n || res[p].id != FD_SIG_NO_ID) continue;
+                uint32_t filled = 0;
+                for (unsigned k = 0; k < 64; ++k) filled += S[p].sk[k] != FD_SIG_EMPTY ? 1u : 0u;
+                res[p].id = (uint32_t)p; res[p].match = res[p].filled = (uint8_t)filled; res[p].flags = FD_SIG_IDENTICAL;
+                reps.push_back((uint32_t)p);
+                for (uint64_t j = i + 1; j < nb; ++j) if (S[at(j)].n) take(at(j), p);
+            }
+        }
+    } catch (...) { free(res); return FDGPU_ENOMEM; }
     *out = res;
     return FDGPU_OK;
 }

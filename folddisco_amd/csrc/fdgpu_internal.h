@@ -46,6 +46,8 @@ enum {
     WS_RS_TAB, WS_RS_SEG, WS_RS_OUT, WS_RS_RES, WS_RS_KX, WS_RS_KY, WS_RS_KOFF, WS_RS_SOL, WS_RS_CNT, WS_RS_GQ, WS_MP_ACT, WS_MP_Q,
     WS_SG_TAB /* signatures of a window; table A of a compare */, WS_SG_TAB_B, WS_SG_PAIRS, WS_SG_CURSOR,
     WS_SG_NB_PART /* signature neighbours: the k-lists of every split, [split][query][k] */, WS_SG_NB_OUT /* the merged lists, [query][k] */,
+    WS_SG_CL_TAB /* signature clusters: the table in walk order */, WS_SG_CL_REPS /* the representatives so far, compact, appended to */,
+    WS_SG_CL_OUT /* the records in walk order */, WS_SG_CL_PART /* a block's partial bests, [split][lane] */, WS_SG_CL_COUNT /* the number of representatives */,
     WS_COUNT
 };
 

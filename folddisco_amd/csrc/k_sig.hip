@@ -1,5 +1,6 @@
-// k_sig.hip — index signatures (fdgpu_index_signatures), their all-pairs compare (fdgpu_signature_pairs) and their k nearest neighbours
-// (fdgpu_signature_neighbors); the definitions are include/fdgpu.h and fd_signature.h, the host forms fd_signatures_host.cpp.
+// k_sig.hip — index signatures (fdgpu_index_signatures), their all-pairs compare (fdgpu_signature_pairs), their k nearest neighbours
+// (fdgpu_signature_neighbors) and their greedy clusters (fdgpu_signature_clusters, described at its kernels below); the definitions are
+// include/fdgpu.h and fd_signature.h, the host forms fd_signatures_host.cpp.
 //
 // Signatures: the index is walked in windows of structures.  Per window the device stage of the rows (fd_rows_device, k_rows.hip) leaves the
 // window's hashes in (id, hash) order and the row offsets in the context's workspaces, and
@@ -437,4 +438,211 @@ extern "C" int fdgpu_signature_neighbors(fdgpu_ctx *c, const fd_signature *Q, ui
     if (!D && exclude) FAIL(c, FDGPU_EINVAL, "signature neighbors: exclude is implied in self mode (D == NULL); pass none");
     if (nQ && !Q) FAIL(c, FDGPU_EINVAL, "signature neighbors: table Q is NULL");
     return neighbors_impl(c, Q, nQ, D, nD, exclude, k, thr64, out);
+}
+
+// ---- clusters (fdgpu_signature_clusters; the definition is include/fdgpu.h).  The table is uploaded in WALK order (the host gathers it and puts
+// every record's position into its reserved word), so block w0 of the walk is W[w0 .. w0 + 256), one signature per lane as in k_sg_match.  The
+// representatives chosen so far are the compact table R[0 .. *n_reps): copies of their records (the position in the reserved word), appended
+// to by k_sg_cl_resolve and never uploaded again.  *n_reps lives on the device: the host sizes the grids from an upper bound (the positions
+// walked so far) and never waits for it.  Per block, in stream order:
+//   k_sg_cl_scan     grid (1, splits): the block against R, the tiles of R shared by blockIdx.y as in k_sg_near; every lane keeps its ONE nearest
+//                    qualifying representative and writes it to part[blockIdx.y][lane].  A workgroup without a tile (blockIdx.y >= tiles of the
+//                    true count) leaves at once and writes nothing.
+//   k_sg_cl_resolve  one workgroup: merges the partial bests of the splits that had a tile under fd_sig_nearer, then settles the block in walk
+//                    order.  The block is staged 64 signatures at a time (sg_stage_tile); tile q holds exactly the signatures of wavefront q.
+//                    Wavefront q settles its own 64 in order with ballots alone: at step i lane i is a representative iff it is non-empty and
+//                    has no best yet, and if so every later lane that qualifies with it and finds it nearer takes it.  It then publishes the
+//                    mask of its representatives in LDS, and the wavefronts behind it compare with those.  The wavefronts before it are
+//                    earlier in the walk: nothing of tile q concerns them.  So a lane's best is its nearest among R and the representatives
+//                    before it in the block alike, which is the sequential walk.  A prefix sum over the workgroup gives every new representative
+//                    its slot of R; the lane copies its record there, writes its result record, and thread 0 moves *n_reps.
+// Nothing waits for another workgroup: no flag, no spin, no cooperative launch.  The order fd_sig_nearer is total, so neither the number of
+// splits nor the width of the block changes a byte.  Records leave in walk order; the host puts them at their positions.
+#define SG_CL_MAX_SPLIT 256u     // splits of a scan: one workgroup per CU; bounds WS_SG_CL_PART at 256 * 256 * 8 bytes
+
+struct sg_cl_args { const uint32_t *W; uint32_t *R; uint32_t *n_reps; uint2 *part; uint2 *out; uint32_t w0, nb, thr64, splits; };
+
+// the lane's signature W[w0 + t] into registers (a lane beyond the block: n = 0, which is never a candidate and never a representative)
+#define SG_CL_LOAD_LANE(P)                                                                                                       \
+    const uint32_t t = threadIdx.x;                                                                                              \
+    const bool have = t < (P).nb;                                                                                                \
+    uint32_t b[64];                                                                                                              \
+    uint32_t bn = 0, bpos = FD_SIG_NO_ID, bd0l = 0, bd0h = 0, bd1l = 0, bd1h = 0;                                                \
+    unsigned long long b_empty = 0;                                                                                              \
+    (void)bpos;                                                                                                                  \
+    {                                                                                                                            \
+        const uint32_t *pb = (P).W + (uint64_t)((P).w0 + (have ? t : 0u)) * FD_SIG_WORDS;                                        \
+        if (have) { bn = pb[0]; bpos = pb[1]; bd0l = pb[2]; bd0h = pb[3]; bd1l = pb[4]; bd1h = pb[5]; }                          \
+        _Pragma("unroll")                                                                                                        \
+        for (uint32_t k = 0; k < 64; ++k) {                                                                                      \
+            b[k] = have ? pb[6 + k] : FD_SIG_EMPTY;                                                                              \
+            b_empty |= (unsigned long long)(b[k] == FD_SIG_EMPTY ? 1u : 0u) << k;                                                \
+        }                                                                                                                        \
+    }
+
+// entry i of the staged tile against the lane's signature: the lane's best (id, match | filled << 8 | identical << 16) takes it if the pair
+// is reported and the entry, whose position is its reserved word, is nearer
+#define SG_CL_TAKE(i)                                                                                                            \
+    {                                                                                                                            \
+        uint32_t eq = 0;                                                                                                         \
+        _Pragma("unroll")                                                                                                        \
+        for (uint32_t k = 0; k < 64; ++k) eq += a_sk[i][k] == b[k] ? 1u : 0u;                                                    \
+        const uint32_t E = (uint32_t)__popcll(a_empty[i] & b_empty);                                                             \
+        const uint32_t a = a_head[i][1], m = eq - E, f = 64u - E;                                                                \
+        if (fd_sig_reported(bn, a_head[i][0], eq, E, thr64) && sg_nearer_packed(m, f, a, best_mf, best_id)) {                    \
+            const bool same = a_head[i][0] == bn && a_head[i][2] == bd0l && a_head[i][3] == bd0h && a_head[i][4] == bd1l && a_head[i][5] == bd1h; \
+            best_id = a; best_mf = m | f << 8 | (same ? FD_SIG_IDENTICAL : 0u) << 16;                                            \
+        }                                                                                                                        \
+    }
+
+// Reads W[w0 .. w0 + nb), R[0 .. *n_reps); writes part[blockIdx.y * 256 + t] for every t < 256 if it has a tile
+__global__ __launch_bounds__(256) void k_sg_cl_scan(sg_cl_args P) {
+    __shared__ uint32_t a_sk[SG_TILE_A][64];
+    __shared__ uint32_t a_head[SG_TILE_A][6];
+    __shared__ unsigned long long a_empty[SG_TILE_A];
+    const uint32_t nR = *P.n_reps, tiles = (nR + SG_TILE_A - 1) / SG_TILE_A, thr64 = P.thr64;
+    if (blockIdx.y >= tiles) return;                    // the grid came from an upper bound of the count
+    SG_CL_LOAD_LANE(P)
+    uint32_t best_id = FD_SIG_NO_ID, best_mf = 0u;
+    for (uint32_t ta = blockIdx.y; ta < tiles; ta += gridDim.y) {
+        sg_stage_tile(P.R, nR, (uint64_t)ta * SG_TILE_A, a_sk, a_head, a_empty);
+        for (uint32_t i = 0; i < SG_TILE_A; ++i) SG_CL_TAKE(i)
+    }
+    P.part[blockIdx.y * SG_BLOCK_B + t] = make_uint2(best_id, best_mf);
+}
+
+// One workgroup.  Reads part[y * 256 + t] for y < min(splits, tiles of *n_reps), W[w0 .. w0 + nb); writes out[w0 + t] for t < nb,
+// R[*n_reps .. *n_reps + new representatives) (at most nb more: the host sized R for every position) and *n_reps
+__global__ __launch_bounds__(256) void k_sg_cl_resolve(sg_cl_args P) {
+    __shared__ uint32_t a_sk[SG_TILE_A][64];
+    __shared__ uint32_t a_head[SG_TILE_A][6];
+    __shared__ unsigned long long a_empty[SG_TILE_A];
+    __shared__ unsigned long long rep_mask[SG_BLOCK_B / 64];
+    __shared__ uint32_t wave_reps[SG_BLOCK_B / 64];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, thr64 = P.thr64;
+    const uint32_t nR = *P.n_reps, valid = std::min<uint32_t>(P.splits, (nR + SG_TILE_A - 1) / SG_TILE_A);
+    SG_CL_LOAD_LANE(P)
+    uint32_t best_id = FD_SIG_NO_ID, best_mf = 0u;
+    for (uint32_t y = 0; y < valid; ++y) {
+        const uint2 c = P.part[y * SG_BLOCK_B + t];
+        if (sg_nearer_packed(c.y & 0xffu, (c.y >> 8) & 0xffu, c.x, best_mf, best_id)) { best_id = c.x; best_mf = c.y; }
+    }
+    bool is_rep = false;
+    for (uint32_t q = 0; q * SG_TILE_A < P.nb; ++q) {   // the same for the whole workgroup; a tile beyond the block is never staged
+        sg_stage_tile(P.W, P.w0 + P.nb, (uint64_t)P.w0 + q * SG_TILE_A, a_sk, a_head, a_empty);
+        if (wv == q) {
+            unsigned long long mine = 0;
+            for (uint32_t i = 0; i < SG_TILE_A; ++i) {
+                const unsigned long long open = __ballot(bn > 0 && best_id == FD_SIG_NO_ID);      // lane i's bit is final: only lanes behind a step change
+                if (!(open >> i & 1ull)) continue;      // the same for the whole wavefront
+                mine |= 1ull << i;
+                if (lane == i) is_rep = true;
+                else if (lane > i) SG_CL_TAKE(i)
+            }
+            if (lane == 0) rep_mask[q] = mine;
+        }
+        __syncthreads();
+        if (wv > q) {
+            for (unsigned long long left = rep_mask[q]; left; left &= left - 1ull) {
+                const uint32_t i = (uint32_t)__ffsll((long long)left) - 1u;
+                SG_CL_TAKE(i)
+            }
+        }
+    }
+    // the new representatives' slots of R: ranks inside the wavefront, the wavefronts' counts through LDS
+    const unsigned long long vote = __ballot(is_rep);
+    if (lane == 0) wave_reps[wv] = (uint32_t)__popcll(vote);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t w = 0; w < SG_BLOCK_B / 64; ++w) { before += w < wv ? wave_reps[w] : 0u; total += wave_reps[w]; }
+    if (is_rep) {
+        uint32_t *rec = P.R + (uint64_t)(nR + before + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull))) * FD_SIG_WORDS;
+        rec[0] = bn; rec[1] = bpos; rec[2] = bd0l; rec[3] = bd0h; rec[4] = bd1l; rec[5] = bd1h;
+#pragma unroll
+        for (uint32_t k = 0; k < 64; ++k) rec[6 + k] = b[k];
+        const uint32_t filled = 64u - (uint32_t)__popcll(b_empty);
+        best_id = bpos; best_mf = filled | filled << 8 | FD_SIG_IDENTICAL << 16;
+    }
+    if (have) P.out[P.w0 + t] = make_uint2(best_id, best_mf);
+    if (threadIdx.x == 0) *P.n_reps = nR + total;
+}
+
+static int clusters_impl(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, fd_sig_neighbor **out) {
+    reset_timings(c);
+    hipStream_t st = c->stream;
+    fd_sig_neighbor *res = (fd_sig_neighbor *)fd_out_alloc(std::max<uint64_t>(n, 1) * sizeof(fd_sig_neighbor));
+    if (!res) FAIL(c, FDGPU_ENOMEM, "signature clusters: out of host memory");
+    const fd_sig_neighbor none = {FD_SIG_NO_ID, 0, 0, 0};
+    res[0] = none;
+    if (!n) { *out = res; return FDGPU_OK; }
+    // the table in walk order, every record's position in its reserved word; the records come back in walk order into `walk`
+    fd_signature *W = (fd_signature *)malloc(n * sizeof(fd_signature));
+    fd_sig_neighbor *walk = (fd_sig_neighbor *)malloc(n * sizeof(fd_sig_neighbor));
+    if (!W || !walk) { free(W); free(walk); fdgpu_free(res); FAIL(c, FDGPU_ENOMEM, "signature clusters: out of host memory"); }
+    for (uint64_t w = 0; w < n; ++w) {
+        const uint64_t p = order ? order[w] : w;
+        W[w] = S[p];
+        W[w].reserved = (uint32_t)p;
+    }
+    long long forced = 0;
+    if (const char *e = getenv("FDGPU_SG_CL_SPLIT")) forced = atoll(e);
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = c->ws[WS_SG_CL_TAB].ensure(n * sizeof(fd_signature))) != hipSuccess) break;
+        if ((e = c->ws[WS_SG_CL_REPS].ensure(n * sizeof(fd_signature))) != hipSuccess) break;
+        if ((e = c->ws[WS_SG_CL_OUT].ensure(n * sizeof(fd_sig_neighbor))) != hipSuccess) break;
+        if ((e = c->ws[WS_SG_CL_PART].ensure((uint64_t)SG_CL_MAX_SPLIT * SG_BLOCK_B * sizeof(uint2))) != hipSuccess) break;
+        if ((e = c->ws[WS_SG_CL_COUNT].ensure(64)) != hipSuccess) break;
+        sg_cl_args P{c->ws[WS_SG_CL_TAB].as<uint32_t>(), c->ws[WS_SG_CL_REPS].as<uint32_t>(), c->ws[WS_SG_CL_COUNT].as<uint32_t>(),
+                     c->ws[WS_SG_CL_PART].as<uint2>(), c->ws[WS_SG_CL_OUT].as<uint2>(), 0u, 0u, thr64, 0u};
+        {
+            StageTimer t(c, "sigcl_upload", n * sizeof(fd_signature));
+            if ((e = hipMemcpyAsync((void *)P.W, W, n * sizeof(fd_signature), hipMemcpyHostToDevice, st)) != hipSuccess) break;
+            if ((e = hipMemsetAsync(P.n_reps, 0, 4, st)) != hipSuccess) break;
+        }
+        for (uint64_t w0 = 0; w0 < n && e == hipSuccess; w0 += SG_BLOCK_B) {
+            P.w0 = (uint32_t)w0; P.nb = (uint32_t)std::min<uint64_t>(SG_BLOCK_B, n - w0);
+            // at most w0 representatives so far: no more splits than their tiles; FDGPU_SG_CL_SPLIT (tests) moves the boundary
+            const uint32_t most = std::min<uint32_t>(fd_grid(w0, SG_TILE_A), SG_CL_MAX_SPLIT);
+            P.splits = forced > 0 ? (uint32_t)std::min<long long>(forced, most) : most;
+            if (P.splits) {
+                StageTimer t(c, "sigcl_scan", ((uint64_t)SG_BLOCK_B * P.splits + w0) * sizeof(fd_signature));
+                hipLaunchKernelGGL(k_sg_cl_scan, dim3(1, P.splits), dim3(256), 0, st, P);
+                if ((e = hipGetLastError()) != hipSuccess) break;
+            }
+            StageTimer t(c, "sigcl_resolve", (uint64_t)SG_BLOCK_B * (2 * sizeof(fd_signature) + P.splits * sizeof(uint2)));
+            hipLaunchKernelGGL(k_sg_cl_resolve, dim3(1), dim3(256), 0, st, P);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) break;
+        {
+            StageTimer t(c, "sigcl_copy", n * sizeof(fd_sig_neighbor));
+            e = fd_d2h_big(c, walk, P.out, n * sizeof(fd_sig_neighbor));
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    } while (false);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);                 // nothing of a failed call still reads the staging table
+        free(W); free(walk); fdgpu_free(res);
+        c->err = std::string("signature clusters: ") + hipGetErrorString(e);
+        return FDGPU_EHIP;
+    }
+    for (uint64_t w = 0; w < n; ++w) res[order ? order[w] : w] = walk[w];
+    free(W); free(walk);
+    *out = res;
+    return FDGPU_OK;
+}
+
+extern "C" int fdgpu_signature_clusters(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, fd_sig_neighbor **out) { FD_LOCK(c);
+    if (!c || !out) return FDGPU_EINVAL;
+    *out = nullptr;
+    if (thr64 < 1 || thr64 > 64) FAIL(c, FDGPU_EINVAL, "signature clusters: thr64 must be 1 .. 64");
+    if (n > 0xffffffffull) FAIL(c, FDGPU_EINVAL, "signature clusters: a table of 2^32 or more signatures");
+    if (n && !S) FAIL(c, FDGPU_EINVAL, "signature clusters: the table is NULL");
+    if (order) {
+        const uint64_t w = fd_sig_order_fault(order, n);
+        if (w == FD_SIG_ORDER_NOMEM) FAIL(c, FDGPU_ENOMEM, "signature clusters: out of host memory");
+        if (w != n) FAIL(c, FDGPU_EINVAL, "signature clusters: order is not a permutation of 0 .. n - 1 (entry " + std::to_string(w) + " = " + std::to_string(order[w]) + ")");
+    }
+    return clusters_impl(c, S, n, order, thr64, out);
 }

@@ -636,6 +636,108 @@ def signature_neighbors_host(Q, D=None, k: int = 8, min_similarity=None, thr64: 
     return signature_neighbors_result(L, op, len(Q), k)
 
 
+# ---- signature clusters (include/fdgpu.h: fdgpu_signature_clusters); the records are SIGNATURE_NEIGHBOR_DTYPE, one per position
+CLUSTER_ORDER_KEYS = ("hashes", "nres", "plddt", "id")
+
+
+def _sig_cluster_args(S, order, min_similarity, thr64):
+    S = _sig_table(S, "S")
+    t = signature_threshold(min_similarity) if thr64 is None else int(thr64)
+    if not 0 <= t <= 0xffffffff:
+        raise ValueError("signature clusters: thr64 must be 1 .. 64")
+    if order is not None:
+        o = np.asarray(order)
+        if o.shape != (len(S),) or o.dtype.kind not in "iu" or (len(o) and (int(o.min()) < 0 or int(o.max()) > 0xffffffff)):
+            raise ValueError(f"signature clusters: order needs one position per signature ({len(S)}), each of them 0 .. n - 1")
+        order = np.ascontiguousarray(o, dtype=np.uint32)
+    return S, order, t
+
+
+def signature_clusters_from_tables(S, order=None, thr64: int = 58) -> np.ndarray:
+    """THE SPECIFICATION of the signature clusters, in plain numpy: -> len(S) SIGNATURE_NEIGHBOR_DTYPE records.  The positions are visited in
+    `order` (a permutation of them; None: position order).  A position with an empty row (n = 0) is unclustered: id = SIG_NO_ID and zeros.
+    Any other position p looks at the representatives chosen so far that it would be reported with at thr64 (both rows non-empty, filled > 0,
+    match * 64 >= thr64 * filled).  None: p becomes a representative, its record is (p, its non-empty buckets twice, SIG_IDENTICAL).  Otherwise p
+    joins the nearest of them (descending match / filled, then descending filled, then ascending position in the table): (r, match, filled,
+    n, d0 and d1 agree).  The device form (Context.signature_clusters) and the host form (signature_clusters_host) agree with it byte for byte"""
+    S = _sig_table(S, "S")
+    n = len(S)
+    order = np.arange(n, dtype=np.int64) if order is None else np.asarray(order).astype(np.int64)
+    if order.shape != (n,) or not np.array_equal(np.sort(order), np.arange(n)):
+        raise ValueError(f"signature clusters: order is not a permutation of 0 .. {n - 1}")
+    if not 1 <= int(thr64) <= 64:
+        raise ValueError("signature clusters: thr64 must be 1 .. 64")
+    out = np.zeros(n, SIGNATURE_NEIGHBOR_DTYPE)
+    out["id"] = SIG_NO_ID
+    empty = S["sk"] == SIG_EMPTY
+    reps = np.zeros(n, np.int64)
+    n_reps = 0
+    for p in order.tolist():
+        if S["n"][p] == 0:
+            continue
+        r = reps[:n_reps]
+        eq = (S["sk"][r] == S["sk"][p]).sum(-1)
+        E = (empty[r] & empty[p]).sum(-1)
+        match, filled = eq - E, 64 - E
+        c = np.nonzero((filled > 0) & (match * 64 >= int(thr64) * filled))[0]
+        if not len(c):
+            k = 64 - int(empty[p].sum())
+            out[p] = (p, k, k, SIG_IDENTICAL)
+            reps[n_reps] = p
+            n_reps += 1
+            continue
+        ratio = (match[c] << 20) // np.maximum(filled[c], 1)      # as in signature_neighbors_from_tables
+        b = c[np.lexsort((r[c], -filled[c], -ratio))[0]]
+        q = int(r[b])
+        out[p] = (q, match[b], filled[b], int(S["n"][q] == S["n"][p] and S["d0"][q] == S["d0"][p] and S["d1"][q] == S["d1"][p]))
+    return out
+
+
+def signature_clusters_result(L, op, n: int) -> np.ndarray:
+    """the library's cluster records as an array of n; releases the block"""
+    if not n:
+        if op:
+            L.fdgpu_free(op)
+        return np.zeros(0, SIGNATURE_NEIGHBOR_DTYPE)
+    return _lib.owned_view(L, op, n * SIGNATURE_NEIGHBOR_DTYPE.itemsize, np.uint8).view(SIGNATURE_NEIGHBOR_DTYPE)
+
+
+def signature_clusters_host(S, order=None, min_similarity: float = 0.9, thr64=None, threads: int = 1) -> np.ndarray:
+    """the greedy clusters of a signature table on the CPU (fdgpu_signature_clusters_host: no context, no device): one
+    SIGNATURE_NEIGHBOR_DTYPE record per position, see signature_clusters_from_tables.  The threshold is thr64 / 64 if thr64 is given, else
+    signature_threshold(min_similarity).  The result does not depend on `threads`.  Raises ValueError for a thr64 outside 1 .. 64 and an
+    order that is not a permutation of the positions"""
+    S, order, t = _sig_cluster_args(S, order, min_similarity, thr64)
+    L = _lib.load()
+    op = C.c_void_p()
+    rc = L.fdgpu_signature_clusters_host(S.ctypes.data, len(S), None if order is None else order.ctypes.data, t, max(int(threads), 1), C.byref(op))
+    if rc != 0:
+        raise ValueError(f"signature clusters: fdgpu_signature_clusters_host failed ({rc}): thr64 must be 1 .. 64, the table holds fewer than 2^32 "
+                         "signatures and order is a permutation of 0 .. n - 1")
+    return signature_clusters_result(L, op, len(S))
+
+
+def cluster_order(S, lookup_rows, by: str = "hashes") -> np.ndarray:
+    """the walk orders of `cluster` -> the positions in the order they are visited (u32).  by = "hashes": the signature's n, descending (the
+    most complete structure represents); "nres" / "plddt": that column of PREFIX.lookup, descending; "id": ascending.  Ties go by ascending
+    id.  ValueError for another key, a row count that is not len(S), or a row with fewer than four columns"""
+    if by not in CLUSTER_ORDER_KEYS:
+        raise ValueError(f"unknown representative key '{by}' (one of {', '.join(CLUSTER_ORDER_KEYS)})")
+    n = len(S)
+    if by == "id":
+        return np.arange(n, dtype=np.uint32)
+    if by == "hashes":
+        key = np.asarray(S["n"]).astype(np.float64)
+    else:
+        if len(lookup_rows) != n:
+            raise ValueError(f".lookup holds {len(lookup_rows)} rows, the table {n} signatures")
+        cols = [r.rstrip("\n").split("\t") for r in lookup_rows]
+        if any(len(c) < 4 for c in cols):
+            raise ValueError("a .lookup row has fewer than four columns")
+        key = np.array([float(int(c[2])) if by == "nres" else float(c[3]) for c in cols], np.float64).reshape(n)
+    return np.lexsort((np.arange(n), -key)).astype(np.uint32)
+
+
 def permute_lookup_rows(rows, new_id, keep_db_keys: bool):
     """the rows of PREFIX.lookup after a reorder: row k moves to position new_id[k], tid, nres and plddt verbatim, the id renumbered 0 .. n - 1; the
     db_key column renumbered with it for a file-built index (there it equals the id) and kept for a Foldcomp-built one (its database key) -- the

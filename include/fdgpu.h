@@ -669,6 +669,31 @@ int fdgpu_signature_neighbors(fdgpu_ctx *ctx, const fd_signature *Q, uint64_t nQ
 int fdgpu_signature_neighbors_host(const fd_signature *Q, uint64_t nQ, const fd_signature *D, uint64_t nD, const uint32_t *exclude, uint32_t k,
                                    uint32_t thr64, uint32_t n_threads, fd_sig_neighbor **out);
 
+/* ---- signature clusters: one representative per group of a table S, every member reported with its representative.
+ * The result is a function of S[0 .. n), a walk order (a permutation of the positions 0 .. n - 1; NULL = position order) and thr64 alone.
+ * The positions are visited as p = order[0], order[1], ...:
+ *   S[p].n == 0   p is unclustered: its record is {id = 0xFFFFFFFF, 0, 0, 0}.  Never a representative, never a candidate.
+ *   otherwise     the candidates of p are the representatives chosen so far whose pair with p would be reported at thr64 (eq, E, match and
+ *                 filled as for fd_sig_pair).  No candidate: p becomes a representative, its record is {id = p, match = filled = the number
+ *                 of its non-empty buckets, flags = FD_SIG_IDENTICAL}.  Otherwise p joins the nearest candidate r in the order of the
+ *                 neighbours (the larger match / filled, then the larger filled, then the smaller position in the table, not in the walk):
+ *                 its record is {id = r, match, filled, flags bit 0 = n, d0 and d1 agree}.
+ * Integers only and a total order: the result is unique.  No two representatives are a reported pair at thr64, every member is one with its
+ * representative.  One fd_sig_neighbor per position; *out holds max(n, 1) of them, released with fdgpu_free, byte-identical from run to run.
+ * FDGPU_EINVAL and *out NULL: thr64 outside 1 .. 64, n >= 2^32, a NULL table with n > 0, an order that is not a permutation of 0 .. n - 1
+ * (a repeat, or a value >= n).  n == 0: an empty result.
+ * On the device (csrc/k_sig.hip) no pair list is made: the walk goes in blocks of 256 positions; k_sg_cl_scan compares a block with the
+ * representatives chosen so far (a compact device table that is only appended to; its count stays on the device), k_sg_cl_resolve merges
+ * the splits, settles the block in walk order and appends its new representatives.  Stream order alone orders the steps, the host waits
+ * once at the end.  The message of a refusal opens "signature clusters:" and nothing is launched.  Workspace: 2 * 280 + 8 bytes per
+ * signature, 2 KB per split.  Test switch, read per call: FDGPU_SG_CL_SPLIT=n sets the number of splits of the scan (clamped to
+ * 1 .. min(tiles of 64 representatives there can be, 256)); the result does not depend on it. */
+int fdgpu_signature_clusters(fdgpu_ctx *ctx, const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, fd_sig_neighbor **out);
+/* The same clusters on the CPU: the same walk in blocks, n_threads host threads (0 = 1) over a block's positions for the scan of the
+ * representatives chosen before the block; the result does not depend on n_threads.  No device.  The same refusals (code only). */
+int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, uint32_t n_threads,
+                                  fd_sig_neighbor **out);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
