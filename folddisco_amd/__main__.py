@@ -622,12 +622,22 @@ def cmd_rows(a):
         print(f"[INFO] rows of {a.index} on the {'host' if a.host else 'device'}: {n_windows} window(s) of up to {a.window} structures", file=sys.stderr)
 
 
-def _dups_plan(a):
-    """everything `dups` decides before it opens a device: -> (prefixes, their tids).  Status 2 for missing or unreadable files, status 1 and a
-    [FAIL] line for a refusal; nothing is written in either case."""
+def _dups_plan(a, cmd="dups"):
+    """everything `dups` (and `overlap`, which plans like it) decides before it opens a device: -> (prefixes, their tids).  Status 2 for missing
+    or unreadable files, status 1 and a [FAIL] line for a refusal; nothing is written in either case."""
     if a.max_pairs < 0:
-        sys.exit("[FAIL] dups: --max-pairs must not be negative")
-    return _sig_plan(a, "dups")
+        sys.exit(f"[FAIL] {cmd}: --max-pairs must not be negative")
+    _min_jaccard_plan(a, cmd)
+    return _sig_plan(a, cmd)
+
+
+def _min_jaccard_plan(a, cmd):
+    """--min-jaccard F: outside (0, 1] (NaN too) is a refusal; given, it implies --confirm"""
+    if getattr(a, "min_jaccard", None) is None:
+        return
+    if not 0.0 < a.min_jaccard <= 1.0:
+        sys.exit(f"[FAIL] {cmd}: --min-jaccard {a.min_jaccard} is outside (0, 1]")
+    a.confirm = True
 
 
 def _sig_plan(a, cmd):
@@ -686,41 +696,49 @@ def _dups_signatures(a, ctx, prefix, n):
     return np.array(ix.signatures(window=a.window))
 
 
-def _dups_rows(a, ctx, prefix, n, ids):
-    """the rows of the ascending unique ids of one index, fetched as `rows --tids` does: windows that cover them -> {id: hashes}"""
+def _dups_overlaps(a, ctx, prefixes, tids, ia, ib, stats=None, verify=False):
+    """the exact row overlaps of the pairs (ia[k] of the first index, ib[k] of the second one, or of the first if there is one only) ->
+    (inter, n_a, n_b) as int64 arrays, from the tiling drivers: indexio.row_overlaps on the device, row_overlaps_host with --host.  At most
+    --pool-mb (default 4096) megabytes of rows are resident at a time"""
     from folddisco_amd import indexio
-    out = {}
-    if not len(ids):
-        return out
-    v, h, o = indexio.read_index_files(prefix)
+    ia, ib = np.asarray(ia).astype(np.int64), np.asarray(ib).astype(np.int64)
+    stats = a.overlap_stats = {"extractions": 0, "distinct": 0, "tiles": 0} if stats is None else stats      # what -v prints
+    if not len(ia) and not verify:
+        return tuple(np.zeros(0, np.int64) for _ in range(3))
+    pool = int(getattr(a, "pool_mb", 4096)) * (1 << 20) // 4
+    files = [indexio.read_index_files(p) + (len(t),) for p, t in zip(prefixes, tids)]
     if a.host:
-        window = lambda lo, hi: indexio.rows_host(v, h, o, n, lo=lo, hi=hi, threads=a.threads)
+        if verify:
+            for p, (v, h, o, n) in zip(prefixes, files):
+                _stop_if_unsound(indexio.verify_host(v, h, o, n, threads=a.threads), p)
+        got = indexio.row_overlaps_host(files[0], files[1] if len(files) == 2 else None, ia, ib, window=a.window, pool_hashes=pool, threads=a.threads,
+                                        stats=stats)
     else:
         import folddisco_amd as fd
-        ix = fd.FolddiscoIndex.load(ctx, h, o, v, n)
-        del v, h, o
-        window = ix.rows
-    for lo, hi, k0, k1 in _windows(ids, a.window, n):
-        wh, woff = window(lo, hi)
-        for k in range(k0, k1):
-            s = int(ids[k]) - lo
-            out[int(ids[k])] = np.array(wh[int(woff[s]):int(woff[s + 1])])
-    return out
+        ixs = [fd.FolddiscoIndex.load(ctx, h, o, v, n) for v, h, o, n in files]
+        del files
+        if verify:
+            for p, ix in zip(prefixes, ixs):
+                _stop_if_unsound(ix.verify(), p)
+        got = indexio.row_overlaps(ixs[0], ixs[1] if len(ixs) == 2 else None, ia, ib, window=a.window, pool_hashes=pool, stats=stats)
+    return tuple(np.asarray(x).astype(np.int64) for x in got)
+
+
+def _extractions(a):
+    """the -v clause of the commands that confirm: a row may be extracted more than once when the pool is small"""
+    st = getattr(a, "overlap_stats", None)
+    return f" ({st['extractions']} row extractions for {st['distinct']} distinct rows)" if st else ""
+
+
+def _jaccard_values(exact):
+    """inter / max(union, 1) of every pair, from the integers"""
+    return [int(i) / max(int(x) + int(y) - int(i), 1) for i, x, y in zip(*exact)]
 
 
 def _dups_jaccard(a, ctx, prefixes, tids, ia, ib):
     """the exact Jaccard similarity of the pairs (ia[k] of the first index, ib[k] of the second one, or of the first if there is one only),
     from the rows of their structures"""
-    two = len(prefixes) == 2
-    ids_a = np.unique(np.concatenate([ia, ib]) if not two else ia).astype(np.int64)
-    rows_a = _dups_rows(a, ctx, prefixes[0], len(tids[0]), ids_a)
-    rows_b = _dups_rows(a, ctx, prefixes[1], len(tids[1]), np.unique(ib).astype(np.int64)) if two else rows_a
-    jac = []
-    for ka, kb in zip(ia, ib):
-        x, y = rows_a[int(ka)], rows_b[int(kb)]
-        inter = len(np.intersect1d(x, y))
-        jac.append(inter / max(len(x) + len(y) - inter, 1))
-    return jac
+    return _jaccard_values(_dups_overlaps(a, ctx, prefixes, tids, ia, ib))
 
 
 def _write_tsv(output, lines, cmd):
@@ -744,7 +762,8 @@ def cmd_dups(a):
     --against, with those of a second one, on the device (fdgpu_signature_pairs) or with --host on the CPU (no device is opened).  One TSV row
     per reported pair, sorted by (id_a, id_b): id_a tid_a n_a id_b tid_b n_b match filled estimate class[ jaccard]; class is `identical` (same
     size and digests: the same hash set) or `similar` (estimate = match / filled of the sketches reaches --min-similarity); --confirm adds the
-    exact Jaccard similarity from the rows of the reported structures.  It reports and removes nothing.  No structure file is read."""
+    exact Jaccard similarity from the rows of the reported structures (indexio.row_overlaps); --min-jaccard F implies it and keeps only the
+    reported pairs whose exact similarity reaches F (indexio.jaccard_reaches).  It reports and removes nothing.  No structure file is read."""
     from folddisco_amd import indexio
     prefixes, tids = _dups_plan(a)
     two = len(prefixes) == 2
@@ -764,7 +783,13 @@ def cmd_dups(a):
             sys.exit(1)
         if a.identical_only:
             pairs = pairs[(pairs["flags"] & indexio.SIG_IDENTICAL) != 0]
-        jac = _dups_jaccard(a, ctx, prefixes, tids, pairs["a"], pairs["b"]) if a.confirm else None
+        jac = None
+        if a.confirm:
+            exact = _dups_overlaps(a, ctx, prefixes, tids, pairs["a"], pairs["b"])
+            if a.min_jaccard is not None:            # only the reported pairs whose exact similarity reaches the floor
+                keep = indexio.jaccard_reaches(exact[0], exact[1] + exact[2] - exact[0], a.min_jaccard)
+                pairs, exact = pairs[keep], tuple(x[keep] for x in exact)
+            jac = _jaccard_values(exact)
     except (OSError, ValueError) as e:
         print(f"[FAIL] dups: {e}", file=sys.stderr)
         sys.exit(2 if isinstance(e, OSError) else 1)
@@ -782,7 +807,78 @@ def cmd_dups(a):
     print(f"[OK] {' x '.join(prefixes)}: {' x '.join(str(len(t)) for t in tids)} structures, {len(pairs)} pairs ({n_ident} identical), threshold {thr64}/64")
     if a.verbose:
         print(f"[INFO] dups on the {'host' if a.host else 'device'}: signatures of {sum(len(t) for t in tids)} structures ({sum(t.nbytes for t in tabs)} bytes)"
-              + (f", {len(jac)} pairs confirmed from their rows" if jac is not None else ""), file=sys.stderr)
+              + (f", {len(jac)} pairs confirmed from their rows" + _extractions(a) if jac is not None else ""), file=sys.stderr)
+
+
+def _overlap_plan(a):
+    """everything `overlap` decides before it opens a device: the planning of `dups`, then the pairs of --pairs FILE looked up in the .lookup
+    files -> (prefixes, their tids, ids of the first index, ids of the second).  Status 2 for missing or unreadable files, status 1 and a
+    [FAIL] line for a refusal; nothing is written in either case."""
+    if a.pool_mb < 1:
+        sys.exit("[FAIL] overlap: --pool-mb must be at least 1")
+    if not os.path.isfile(a.pairs):
+        print(f"[FAIL] {a.pairs} not found", file=sys.stderr)
+        sys.exit(2)
+    prefixes, tids = _dups_plan(a, "overlap")
+    try:
+        with open(a.pairs) as f:
+            lines = [line.rstrip("\n") for line in f if line.strip()]
+    except (OSError, UnicodeDecodeError) as e:
+        print(f"[FAIL] overlap: unreadable input ({e})", file=sys.stderr)
+        sys.exit(2)
+    cols = [line.split("\t") for line in lines]
+    bad = [k for k, c in enumerate(cols) if len(c) != 2 or not c[0] or not c[1]]
+    if bad:
+        print(f"[FAIL] overlap: {len(bad)} line(s) of {a.pairs} are not tid_a<TAB>tid_b, the first: {lines[bad[0]]!r}")
+        sys.exit(1)
+    out = []
+    for side, (p, t) in enumerate(zip([prefixes[0], prefixes[-1]], [tids[0], tids[-1]])):
+        where = {}
+        for k, x in enumerate(t):
+            where.setdefault(x, []).append(k)
+        asked = list(dict.fromkeys(c[side] for c in cols))
+        unknown = [x for x in asked if x not in where]
+        if unknown:
+            print(f"[FAIL] overlap: {len(unknown)} tid(s) of {a.pairs} are not in {p}.lookup: " + ", ".join(unknown[:10]) + (" ..." if len(unknown) > 10 else ""))
+            sys.exit(1)
+        twice = [x for x in asked if len(where[x]) > 1]
+        if twice:
+            print(f"[FAIL] overlap: {len(twice)} tid(s) of {a.pairs} name more than one row of {p}.lookup: " + ", ".join(twice[:10]) + (" ..." if len(twice) > 10 else ""))
+            sys.exit(1)
+        out.append(np.array([where[c[side]][0] for c in cols], dtype=np.int64))
+    return prefixes, tids, out[0], out[1]
+
+
+def cmd_overlap(a):
+    """`overlap`: the exact similarity of given pairs of structures.  --pairs FILE holds one tid_a<TAB>tid_b per line (column 2 of PREFIX.lookup;
+    with --against, tid_b is looked up in PREFIX2).  The rows of the named structures are kept on the device in sets of at most --pool-mb
+    megabytes (fdgpu_index_rowset) and intersected pair by pair (fdgpu_rowset_intersect), or with --host on the CPU (no device is opened).  One
+    TSV row per pair in the file's order: id_a tid_a n_a id_b tid_b n_b inter union jaccard, where inter = |R_a ∩ R_b| over the two rows,
+    union = n_a + n_b - inter and jaccard = inter / max(union, 1); --min-jaccard F keeps the pairs that reach F (indexio.jaccard_reaches).
+    Integers only: device and host write the same file.  No structure file is read."""
+    prefixes, tids, ia, ib = _overlap_plan(a)
+    from folddisco_amd import indexio
+    stats = {"extractions": 0, "distinct": 0, "tiles": 0}
+    try:
+        ctx = None
+        if not a.host:
+            import folddisco_amd as fd
+            ctx = fd.Context(a.device)
+        inter, n_a, n_b = _dups_overlaps(a, ctx, prefixes, tids, ia, ib, stats=stats, verify=a.verify)
+    except (OSError, ValueError) as e:
+        print(f"[FAIL] overlap: {e}", file=sys.stderr)
+        sys.exit(2 if isinstance(e, OSError) else 1)
+    union = n_a + n_b - inter
+    keep = indexio.jaccard_reaches(inter, union, a.min_jaccard) if a.min_jaccard is not None else np.ones(len(ia), bool)
+    ta, tb = tids[0], tids[-1]
+    lines = ["\t".join([str(int(ia[k])), ta[ia[k]], str(int(n_a[k])), str(int(ib[k])), tb[ib[k]], str(int(n_b[k])), str(int(inter[k])), str(int(union[k])),
+                        f"{int(inter[k]) / max(int(union[k]), 1):.4f}"]) + "\n" for k in np.nonzero(keep)[0]]
+    _write_tsv(a.output, lines, "overlap")
+    print(f"[OK] {' x '.join(prefixes)}: {len(ia)} pairs, {stats['distinct']} distinct rows"
+          + (f", {int(keep.sum())} at or above {a.min_jaccard}" if a.min_jaccard is not None else ""))
+    if a.verbose:
+        print(f"[INFO] overlap on the {'host' if a.host else 'device'}: {stats['extractions']} row extractions for {stats['distinct']} distinct rows, "
+              f"{stats['tiles']} tile(s) within {a.pool_mb} MB", file=sys.stderr)
 
 
 def cmd_neighbors(a):
@@ -847,7 +943,7 @@ def cmd_neighbors(a):
           f"{n_ident} with an identical nearest, floor {thr64}/64")
     if a.verbose:
         print(f"[INFO] neighbors on the {'host' if a.host else 'device'}: {len(ids)} queries, signatures of {sum(len(t) for t in tids)} structures "
-              f"({sum(t.nbytes for t in tabs)} bytes)" + (f", {len(jac)} rows confirmed from their rows" if jac is not None else ""), file=sys.stderr)
+              f"({sum(t.nbytes for t in tabs)} bytes)" + (f", {len(jac)} rows confirmed from their rows" + _extractions(a) if jac is not None else ""), file=sys.stderr)
 
 
 def cmd_cluster(a):
@@ -857,11 +953,14 @@ def cmd_cluster(a):
     one (the order of `neighbors`), on the device (fdgpu_signature_clusters) or with --host on the CPU (no device is opened).  One TSV row per
     structure with a non-empty row, sorted by (rep_id, id): rep_id rep_tid rep_n id tid n match filled estimate class[ jaccard]; class is
     `representative`, `identical` or `similar`.  --redundant FILE gets the members' tids, one per line in id order: what `update --remove`
-    takes; it is refused when such a tid also names a kept row.  It removes nothing itself.  No structure file is read."""
+    takes; it is refused when such a tid also names a kept row.  --min-jaccard F (implies --confirm) changes no cluster: it lists in --redundant
+    only the members whose exact similarity with their representative reaches F; a member below it is kept, and counts among the kept rows of
+    that refusal.  It removes nothing itself.  No structure file is read."""
     from folddisco_amd import indexio
     if a.rep_by not in indexio.CLUSTER_ORDER_KEYS:
         print(f"[FAIL] cluster: unknown --rep-by key '{a.rep_by}' (one of {', '.join(indexio.CLUSTER_ORDER_KEYS)})")
         sys.exit(1)
+    _min_jaccard_plan(a, "cluster")
     prefixes, tids = _sig_plan(a, "cluster")
     prefix, tids = prefixes[0], tids[0]
     thr64 = indexio.signature_threshold(a.min_similarity)
@@ -877,16 +976,30 @@ def cmd_cluster(a):
         ids = np.arange(len(S), dtype=np.int64)
         rep = cl["id"] == ids
         member = ~rep & (cl["id"] != indexio.SIG_NO_ID)
-        if a.redundant:                              # `update --remove` removes every row with a listed tid: none of them may name a kept row
-            listed = {tids[p] for p in ids[member]}
-            clash = sorted({tids[p] for p in ids[~member] if tids[p] in listed})
+        def refuse_clash(listed_rows):               # `update --remove` removes every row with a listed tid: none of them may name a kept row
+            listed = {tids[p] for p in ids[listed_rows]}
+            clash = sorted({tids[p] for p in ids[~listed_rows] if tids[p] in listed})
             if clash:
                 print(f"[FAIL] cluster: {len(clash)} tid(s) of --redundant also name a structure that is kept, and `update --remove` would remove that one too: "
                       + ", ".join(clash[:10]) + (", ..." if len(clash) > 10 else ""))
                 sys.exit(1)
+        removable, n_below = member, 0               # the rows --redundant lists
+        if a.redundant and a.min_jaccard is None:
+            refuse_clash(removable)
         shown = ids[rep | member]
         shown = shown[np.lexsort((shown, cl["id"][shown]))]
-        jac = _dups_jaccard(a, ctx, prefixes, [tids], cl["id"][shown[member[shown]]], shown[member[shown]]) if a.confirm else None
+        jac = None
+        if a.confirm:
+            mem = shown[member[shown]]
+            exact = _dups_overlaps(a, ctx, prefixes, [tids], cl["id"][mem], mem)
+            jac = _jaccard_values(exact)
+            if a.min_jaccard is not None:            # a member below the exact floor is kept: keeping a redundant structure is harmless, deleting a distinct one is not
+                below = ~indexio.jaccard_reaches(exact[0], exact[1] + exact[2] - exact[0], a.min_jaccard)
+                removable = member.copy()
+                removable[mem[below]] = False
+                n_below = int(below.sum())
+                if a.redundant:
+                    refuse_clash(removable)
     except (OSError, ValueError) as e:
         print(f"[FAIL] cluster: {e}", file=sys.stderr)
         sys.exit(2 if isinstance(e, OSError) else 1)
@@ -902,14 +1015,15 @@ def cmd_cluster(a):
         lines.append("\t".join(cols) + "\n")
     _write_tsv(a.output, lines, "cluster")
     if a.redundant:
-        _write_tsv(a.redundant, [tids[p] + "\n" for p in ids[member]], "cluster")
+        _write_tsv(a.redundant, [tids[p] + "\n" for p in ids[removable]], "cluster")
     sizes = np.bincount(cl["id"][shown].astype(np.int64), minlength=max(len(S), 1))
     n_ident = int((member & ((cl["flags"] & indexio.SIG_IDENTICAL) != 0)).sum())
     print(f"[OK] {prefix}: {len(S)} structures, {int(rep.sum())} clusters ({int((sizes[ids[rep]] == 1).sum())} singletons), {int(member.sum())} members "
-          f"({n_ident} identical), {int((cl['id'] == indexio.SIG_NO_ID).sum())} unclustered, largest cluster {int(sizes.max())}, threshold {thr64}/64")
+          f"({n_ident} identical), {int((cl['id'] == indexio.SIG_NO_ID).sum())} unclustered, largest cluster {int(sizes.max())}, threshold {thr64}/64"
+          + (f", {n_below} members below the exact floor kept" if a.min_jaccard is not None else ""))
     if a.verbose:
         print(f"[INFO] cluster on the {'host' if a.host else 'device'}: signatures of {len(S)} structures ({S.nbytes} bytes), walked by {a.rep_by}"
-              + (f", {len(jac)} members confirmed from their rows" if jac is not None else ""), file=sys.stderr)
+              + (f", {len(jac)} members confirmed from their rows" + _extractions(a) if jac is not None else ""), file=sys.stderr)
 
 
 def _reshard_plan(a):
@@ -1530,6 +1644,8 @@ def main(argv=None):
     pd.add_argument("--min-similarity", type=float, default=0.9, help="report pairs whose sketches agree in at least this share of their filled buckets, in (0, 1]")
     pd.add_argument("--identical-only", action="store_true", help="only pairs with the same hash set (same size and digests)")
     pd.add_argument("--confirm", action="store_true", help="add the exact Jaccard similarity of every reported pair, from the rows of its structures")
+    pd.add_argument("--min-jaccard", type=float, default=None, help="implies --confirm: keep only the reported pairs whose exact Jaccard similarity reaches this "
+                    "floor, in (0, 1]")
     pd.add_argument("-o", "--output", default="", help="the TSV file to write (default: standard output)")
     pd.add_argument("--window", type=int, default=16384, help="structures per walk over the index")
     pd.add_argument("--max-pairs", type=int, default=1 << 24, help="most pairs to report; more end the command with their number")
@@ -1538,7 +1654,21 @@ def main(argv=None):
     pd.add_argument("--device", type=int, default=0)
     pd.add_argument("--verify", action="store_true", help="check every loaded index first (see `verify`) and stop with status 1 if it is damaged")
     pd.add_argument("-v", "--verbose", action="store_true")
-    pn = sub.add_parser("neighbors")                                 # the k nearest structures of every structure, by signature (no counterpart in the reference)
+    px = sub.add_parser("overlap")                                   # the exact similarity of given pairs, from their rows (no counterpart in the reference)
+    px.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
+    px.add_argument("--against", default=None, help="a second index prefix: tid_b of every pair is a structure of it (default: of PREFIX)")
+    px.add_argument("--pairs", required=True, help="text file with one tid_a<TAB>tid_b per line (column 2 of the .lookup files); the rows come out in the file's order")
+    px.add_argument("-o", "--output", default="", help="the TSV file to write (default: standard output)")
+    px.add_argument("--min-jaccard", type=float, default=None, help="keep only the pairs whose exact Jaccard similarity reaches this floor, in (0, 1]")
+    px.add_argument("--window", type=int, default=16384, help="structures per walk over the index")
+    px.add_argument("--pool-mb", type=int, default=4096, help="megabytes of rows resident at a time, both sides of a tile together (4 bytes per hash)")
+    px.add_argument("--host", action="store_true", help="extract and intersect on the CPU (no device is opened)")
+    px.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
+    px.add_argument("--device", type=int, default=0)
+    px.add_argument("--verify", action="store_true", help="check every loaded index first (see `verify`) and stop with status 1 if it is damaged")
+    px.add_argument("-v", "--verbose", action="store_true")
+    px.set_defaults(max_pairs=0, min_similarity=1.0)                 # what the shared planning of `dups` looks at
+    pn = sub.add_parser("neighbors")                               # the k nearest structures of every structure, by signature (no counterpart in the reference)
     pn.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
     pn.add_argument("--against", default=None, help="a second index prefix: the neighbours are looked for among its structures (default: among the others of PREFIX)")
     pn.add_argument("-k", type=int, default=8, help="neighbours per structure, 1..32")
@@ -1560,6 +1690,8 @@ def main(argv=None):
     pk.add_argument("-o", "--output", default="", help="the TSV file to write (default: standard output)")
     pk.add_argument("--redundant", default="", help="also write the members' tids, one per line: the file `update --remove` takes")
     pk.add_argument("--confirm", action="store_true", help="add the exact Jaccard similarity of every member with its representative, from their rows")
+    pk.add_argument("--min-jaccard", type=float, default=None, help="implies --confirm: --redundant lists only the members whose exact Jaccard similarity with "
+                    "their representative reaches this floor, in (0, 1]; a member below it is kept")
     pk.add_argument("--window", type=int, default=16384, help="structures per walk over the index")
     pk.add_argument("--host", action="store_true", help="reduce and cluster on the CPU (no device is opened)")
     pk.add_argument("-t", "--threads", type=int, default=1, help="host threads of --host")
@@ -1640,6 +1772,9 @@ def main(argv=None):
         return
     if a.cmd == "dups":
         cmd_dups(a)
+        return
+    if a.cmd == "overlap":
+        cmd_overlap(a)
         return
     if a.cmd == "neighbors":
         cmd_neighbors(a)

@@ -217,6 +217,13 @@ SYMBOLS = [
     ("fdgpu_signature_neighbors_host", C.c_int, [VP, C.c_uint64, VP, C.c_uint64, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_signature_clusters", C.c_int, [VP, VP, C.c_uint64, VP, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_signature_clusters_host", C.c_int, [VP, C.c_uint64, VP, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
+    ("fdgpu_index_rowset", C.c_int, [VP, VP, u32p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(VP), u64p]),
+    ("fdgpu_rowset_info", C.c_int, [VP, u64p, u64p]),
+    ("fdgpu_rowset_lengths", C.c_int, [VP, C.POINTER(u32p)]),
+    ("fdgpu_rowset_export", C.c_int, [VP, VP, C.POINTER(u32p), C.POINTER(u64p)]),
+    ("fdgpu_rowset_intersect", C.c_int, [VP, VP, VP, u32p, u32p, C.c_uint64, C.POINTER(u32p)]),
+    ("fdgpu_rowset_destroy", None, [VP]),
+    ("fdgpu_rows_intersect_host", C.c_int, [u32p, u64p, C.c_uint64, u32p, u64p, C.c_uint64, u32p, u32p, C.c_uint64, C.c_uint32, C.POINTER(u32p)]),
     ("fdgpu_index_verify", C.c_int, [VP, VP, C.POINTER(VerifyReportC)]),
     ("fdgpu_verify_host", C.c_int, [u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyReportC)]),
     ("fdgpu_posting_bytes", C.c_int, [VP, VP, u32p, C.c_uint64, u64p]),

@@ -161,6 +161,17 @@ class Context:
         self.check(self.L.fdgpu_signature_clusters(self.h, S.ctypes.data, len(S), None if order is None else order.ctypes.data, t, C.byref(op)))
         return indexio.signature_clusters_result(self.L, op, len(S))
 
+    def rowset_intersect(self, A: "RowSet", B, ka, kb) -> np.ndarray:
+        """exact row overlaps on the device (fdgpu_rowset_intersect): inter[p] = |row ka[p] of A ∩ row kb[p] of B| as u32, in the order of the
+        pairs; B = None: both rows from A.  The contract of indexio.rows_intersect_host, which it equals value for value"""
+        ka = np.ascontiguousarray(ka, dtype=np.uint32)
+        kb = np.ascontiguousarray(kb, dtype=np.uint32)
+        if ka.ndim != 1 or ka.shape != kb.shape:
+            raise ValueError("rowset_intersect: ka and kb are 1-d arrays of one length")
+        op = u32p()
+        self.check(self.L.fdgpu_rowset_intersect(self.h, A.h, None if B is None else B.h, _ptr(ka, u32p), _ptr(kb, u32p), len(ka), C.byref(op)))
+        return _lib.owned_view(self.L, op, max(len(ka), 1) * 4, np.uint32)[: len(ka)]
+
     # ---- batches
     def upload(self, ps: PackedStructures) -> "Batch":
         d = BatchDesc(ps.n_struct, _ptr(ps.res_off, u64p), _ptr(ps.n_xyz, f32p), _ptr(ps.ca_xyz, f32p), _ptr(ps.cb_xyz, f32p),
@@ -248,6 +259,47 @@ def get_geometric_hash_as_u32(ctx: Context, batch: Batch, nbin_dist=0, nbin_angl
     ctx.L.fdgpu_free(hp)
     ctx.L.fdgpu_free(op)
     return h, off
+
+
+class RowSet:
+    """rows of chosen structures of one index, resident on the device (fdgpu_rowset): row k is the row of the k-th id it was made from.
+    Made by FolddiscoIndex.rowset, consumed by Context.rowset_intersect; close() (or the context manager) gives its blocks back."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h = ctx, h
+        n, nh = C.c_uint64(), C.c_uint64()
+        ctx.check(ctx.L.fdgpu_rowset_info(h, C.byref(n), C.byref(nh)))
+        self.n_rows, self.n_hashes = int(n.value), int(nh.value)
+
+    def lengths(self) -> np.ndarray:
+        """-> u32[n_rows]: the size of every row (no device work)"""
+        lp = u32p()
+        self.ctx.check(self.ctx.L.fdgpu_rowset_lengths(self.h, C.byref(lp)))
+        return _lib.owned_view(self.ctx.L, lp, max(self.n_rows, 1) * 4, np.uint32)[: self.n_rows]
+
+    def export(self):
+        """-> (hashes u32[n_hashes], row_off u64[n_rows + 1]): the set as CSR, the shape of FolddiscoIndex.rows"""
+        hp, op = u32p(), u64p()
+        self.ctx.check(self.ctx.L.fdgpu_rowset_export(self.ctx.h, self.h, C.byref(hp), C.byref(op)))
+        off = _lib.owned_view(self.ctx.L, op, (self.n_rows + 1) * 8, np.uint64)
+        return _lib.owned_view(self.ctx.L, hp, max(self.n_hashes, 1) * 4, np.uint32)[: self.n_hashes], off
+
+    def close(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx.L.fdgpu_rowset_destroy(self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FolddiscoIndex:
@@ -380,6 +432,19 @@ class FolddiscoIndex:
         self.ctx.check(self.ctx.L.fdgpu_index_rows(self.ctx.h, self.h, lo, hi, C.byref(hp), C.byref(op)))
         off = _lib.owned_view(self.ctx.L, op, (hi - lo + 1) * 8, np.uint64)
         return _lib.owned_view(self.ctx.L, hp, int(off[-1]) * 4, np.uint32), off
+
+    def rowset(self, ids, window: int = 16384, max_hashes: int = 0):
+        """the rows of the structures `ids` (absolute, strictly ascending) kept on the device (fdgpu_index_rowset) -> (RowSet, n_taken).  Rows
+        are taken in the order of ids, in windows of `window` structures, until the next row would bring the set above max_hashes hashes
+        (0: no limit; the first row is always taken): n_taken = the number of ids whose rows are in the set, which depends on the rows'
+        lengths alone, not on `window`.  The index is not changed"""
+        a = np.asarray(ids)
+        if a.ndim != 1 or (len(a) and (a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 0xffffffff)) or int(window) < 0 or int(max_hashes) < 0:
+            raise ValueError("rowset: ids are absolute structure ids (1-d, below 2^32), window and max_hashes are counts")
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        h, n = C.c_void_p(), C.c_uint64()
+        self.ctx.check(self.ctx.L.fdgpu_index_rowset(self.ctx.h, self.h, _ptr(a, u32p), len(a), int(window), int(max_hashes), C.byref(h), C.byref(n)))
+        return RowSet(self.ctx, h), int(n.value)
 
     def signatures(self, lo=None, hi=None, window: int = 16384) -> np.ndarray:
         """index signatures (fdgpu_index_signatures): one indexio.SIGNATURE_DTYPE record for each of the structures lo .. hi - 1 (absolute ids;

@@ -244,7 +244,7 @@ static inline int fd_index_last_ids_staged(fdgpu_ctx *c, const fdgpu_index *ix, 
 }
 // k_rows.hip: the device stage of fdgpu_index_rows (plan, count, scan, emit, sort, bounds) without the copy out: the window's rows stay in the
 // context's workspaces (val: the n hashes in (id, hash) order; row_off: id_hi - id_lo + 1 offsets) until its next call that uses the sort buffers.
-// Same checks, codes and messages as the rows, the messages opened by `what`; consumed by the signatures (k_sig.hip)
+// Same checks, codes and messages as the rows, the messages opened by `what`; consumed by the signatures (k_sig.hip) and the row sets (k_overlap.hip)
 struct fd_rows_dev { const uint32_t *val; const uint64_t *row_off; uint64_t n; };
 int fd_rows_device(fdgpu_ctx *c, const fdgpu_index *ix, uint64_t id_lo, uint64_t id_hi, const char *what, fd_rows_dev *out);
 // the failure tail of an operation: the stream's work may still write into the n indexes that were made (null entries: not made), so it ends

@@ -442,8 +442,193 @@ def rows_host(value, hashes, offsets, n_structures: int, first_id: int = 0, lo=N
     return _lib.owned_view(L, oh, int(off[-1]) * 4, np.uint32), off
 
 
+# ---- exact row overlaps (include/fdgpu.h: fdgpu_rowset, fdgpu_rows_intersect_host) ------------------------------------------------------------
+# For structures a and b with rows R_a, R_b: inter = |R_a ∩ R_b|, union = |R_a| + |R_b| - inter, jaccard = inter / max(union, 1).  Integers only.
+OVERLAP_POOL_HASHES = 1 << 30      # 4096 MB of u32 hashes, both sides of a tile together
+
+
+def _csr_rows(rows, name):
+    h, off = rows
+    h = np.ascontiguousarray(h, dtype=np.uint32)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    if h.ndim != 1 or off.ndim != 1 or len(off) < 1 or int(off[-1]) > len(h):
+        raise ValueError(f"{name}: rows as CSR (hashes u32[...], row_off u64[n + 1]) expected")
+    return h, off
+
+
+def _pair_slots(ka, kb):
+    ka, kb = np.asarray(ka), np.asarray(kb)
+    if ka.ndim != 1 or ka.shape != kb.shape:
+        raise ValueError("rows intersect: ka and kb are 1-d arrays of one length")
+    for k in (ka, kb):
+        if len(k) and (k.dtype.kind not in "iu" or int(k.min()) < 0 or int(k.max()) > 0xffffffff):
+            raise ValueError("rows intersect: a pair slot is not a row of its set")
+    return np.ascontiguousarray(ka, dtype=np.uint32), np.ascontiguousarray(kb, dtype=np.uint32)
+
+
+def rows_intersect_host(rows_a, rows_b, ka, kb, threads: int = 1) -> np.ndarray:
+    """exact row overlaps on the CPU (fdgpu_rows_intersect_host: no context, no device): rows_a / rows_b are CSR pairs (hashes, row_off) as
+    FolddiscoIndex.rows, rows_host and RowSet.export return them (rows_b = None: both rows from rows_a) -> inter u32[len(ka)],
+    inter[p] = |row ka[p] of rows_a ∩ row kb[p] of rows_b|, in the order of the pairs.  The result does not depend on `threads`.  Raises
+    ValueError opening "rows intersect:" for a slot that is not a row of its set or 2^32 pairs"""
+    ha, oa = _csr_rows(rows_a, "rows_a")
+    hb, ob = (None, None) if rows_b is None else _csr_rows(rows_b, "rows_b")
+    ka, kb = _pair_slots(ka, kb)
+    L = _lib.load()
+    op = u32p()
+    rc = L.fdgpu_rows_intersect_host(ha.ctypes.data_as(u32p), oa.ctypes.data_as(u64p), len(oa) - 1, None if hb is None else hb.ctypes.data_as(u32p),
+                                     None if ob is None else ob.ctypes.data_as(u64p), 0 if ob is None else len(ob) - 1, ka.ctypes.data_as(u32p),
+                                     kb.ctypes.data_as(u32p), len(ka), max(int(threads), 1), C.byref(op))
+    if rc != 0:
+        raise ValueError(f"rows intersect: fdgpu_rows_intersect_host failed ({rc}): a pair slot at or above its set's row count, offsets that "
+                         "descend, or 2^32 or more pairs")
+    return _lib.owned_view(L, op, max(len(ka), 1) * 4, np.uint32)[: len(ka)]
+
+
+def row_overlaps_from_rows(rows_a, rows_b, ka, kb) -> np.ndarray:
+    """THE SPECIFICATION of the row overlaps, in plain numpy: np.intersect1d per pair over CSR rows (rows_b = None: both from rows_a) ->
+    inter u32[len(ka)].  The device form (Context.rowset_intersect) and the host form (rows_intersect_host) agree with it exactly"""
+    ha, oa = _csr_rows(rows_a, "rows_a")
+    hb, ob = (ha, oa) if rows_b is None else _csr_rows(rows_b, "rows_b")
+    ka, kb = _pair_slots(ka, kb)
+    out = np.zeros(len(ka), np.uint32)
+    for p, (x, y) in enumerate(zip(ka, kb)):
+        out[p] = len(np.intersect1d(ha[int(oa[x]):int(oa[x + 1])], hb[int(ob[y]):int(ob[y + 1])]))
+    return out
+
+
+def jaccard_floor(F: float) -> int:
+    """T of a floor F in (0, 1]: round(F * 10^4); ValueError outside (NaN too)"""
+    if not 0.0 < float(F) <= 1.0:
+        raise ValueError(f"a Jaccard floor of {F} is outside (0, 1]")
+    return int(round(float(F) * 10000))
+
+
+def jaccard_reaches(inter, union, F: float):
+    """does a pair reach the floor F?  True if and only if union > 0 and inter * 10^4 >= round(F * 10^4) * union, in 64-bit integers; the one
+    expression every form uses.  Scalars give a bool, arrays a bool array"""
+    T = np.int64(jaccard_floor(F))
+    i, u = np.asarray(inter).astype(np.int64), np.asarray(union).astype(np.int64)
+    r = (u > 0) & (i * np.int64(10000) >= T * u)
+    return bool(r) if r.ndim == 0 else r
+
+
+def _overlap_pairs_ids(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("row overlaps: a and b are 1-d arrays of absolute structure ids, one length")
+    for x in (a, b):
+        if len(x) and (x.dtype.kind not in "iu" or int(x.min()) < 0 or int(x.max()) > 0xffffffff):
+            raise ValueError("row overlaps: an id is not a structure id")
+    return a.astype(np.int64), b.astype(np.int64)
+
+
+def _row_overlap_tiles(take_a, take_b, intersect, a, b, pool_hashes, stats):
+    """the tiling both drivers share.  take_x(ids, max_hashes) -> (set, its row lengths, n_taken) extracts a prefix of the ascending ids;
+    intersect(A, B, ka, kb) -> inter; sets are released with .close() where they have one"""
+    a, b = _overlap_pairs_ids(a, b)
+    P = len(a)
+    inter, n_a, n_b = np.zeros(P, np.uint32), np.zeros(P, np.uint32), np.zeros(P, np.uint32)
+    half = max(int(pool_hashes) // 2, 1)
+    ua = np.unique(a)
+    st = {"extractions": 0, "distinct": len(ua) + len(np.unique(b)), "tiles": 0}
+    pa = 0
+    while pa < len(ua):
+        A, len_a, ta = take_a(ua[pa:], half)
+        st["extractions"] += ta
+        ca = ua[pa:pa + ta]
+        sel = np.nonzero((a >= ca[0]) & (a <= ca[-1]))[0]         # the pairs of this A chunk
+        ub = np.unique(b[sel])
+        pb = 0
+        while pb < len(ub):
+            B, len_b, tb = take_b(ub[pb:], half)
+            st["extractions"] += tb
+            cb = ub[pb:pb + tb]
+            t = sel[(b[sel] >= cb[0]) & (b[sel] <= cb[-1])]       # the pairs of this (A chunk, B chunk) tile
+            ka, kb = np.searchsorted(ca, a[t]).astype(np.uint32), np.searchsorted(cb, b[t]).astype(np.uint32)
+            inter[t] = intersect(A, B, ka, kb)
+            n_a[t], n_b[t] = len_a[ka], len_b[kb]
+            st["tiles"] += 1
+            if hasattr(B, "close"):
+                B.close()
+            pb += tb
+        if hasattr(A, "close"):
+            A.close()
+        pa += ta
+    if stats is not None:
+        stats.update(st)
+    return inter, n_a, n_b
+
+
+def row_overlaps(ix_a, ix_b, a, b, window: int = 16384, pool_hashes: int = OVERLAP_POOL_HASHES, stats=None):
+    """exact row overlaps of the pairs (a[p], b[p]) on the device: absolute ids a[p] of the resident index ix_a and b[p] of ix_b (ix_b = None or
+    ix_a itself: one index; both on one context) -> (inter, n_a, n_b), u32 arrays in the order of the pairs: the overlap and the two rows'
+    sizes (union = n_a + n_b - inter).  At most pool_hashes hashes are resident at a time, half for each side: the distinct ascending a ids
+    are taken in chunks (one FolddiscoIndex.rowset call each, advancing by its n_taken), for each A chunk the distinct ascending b ids of
+    its pairs in chunks the same way, and the pairs of every (A chunk, B chunk) tile are intersected (Context.rowset_intersect).  The result
+    does not depend on pool_hashes or window.  With a small pool a row is extracted more than once — a B row once per A chunk that has a
+    pair with it; stats (a dict, if given) receives `extractions`, `distinct` (distinct a ids + distinct b ids) and `tiles`"""
+    ix_b = ix_a if ix_b is None else ix_b
+    ctx = ix_a.ctx
+
+    def take(ix):
+        def f(ids, half):
+            rs, t = ix.rowset(ids, window=window, max_hashes=half)
+            return rs, rs.lengths(), t
+        return f
+    return _row_overlap_tiles(take(ix_a), take(ix_b), ctx.rowset_intersect, a, b, pool_hashes, stats)
+
+
+def _rowset_host(files, ids, window, max_hashes, threads):
+    """FolddiscoIndex.rowset over host arrays: files = (value, hashes, offsets, n_structures[, first_id]); the same windows and the same budget
+    rule -> ((hashes, row_off), row lengths, n_taken)"""
+    value, hashes, offsets, n = files[:4]
+    first = int(files[4]) if len(files) > 4 else 0
+    window = int(window) or 16384
+    pieces, lens, k, total, full = [], [], 0, 0, False
+    while k < len(ids) and not full:
+        lo = int(ids[k])
+        hi = min(lo + window, first + int(n))
+        k1 = int(np.searchsorted(ids, hi))
+        wh, woff = rows_host(value, hashes, offsets, n, first_id=first, lo=lo, hi=hi, threads=threads)
+        t = 0
+        for j in range(k, k1):
+            s = int(ids[j]) - lo
+            r0, r1 = int(woff[s]), int(woff[s + 1])
+            if max_hashes and j > 0 and total + (r1 - r0) > max_hashes:
+                full = True
+                break
+            total += r1 - r0
+            lens.append(r1 - r0)
+            pieces.append(np.array(wh[r0:r1]))
+            t += 1
+        k += t
+    off = np.zeros(len(lens) + 1, np.uint64)
+    off[1:] = np.cumsum(np.asarray(lens, dtype=np.uint64), dtype=np.uint64)
+    return (np.concatenate(pieces).astype(np.uint32, copy=False) if pieces else np.zeros(0, np.uint32), off), np.asarray(lens, dtype=np.uint32), k
+
+
+def row_overlaps_host(files_a, files_b, a, b, window: int = 16384, pool_hashes: int = OVERLAP_POOL_HASHES, threads: int = 1, stats=None):
+    """row_overlaps on the CPU (no context, no device): files_a / files_b = (value, hashes, offsets, n_structures[, first_id]) of the two
+    indices (files_b = None: one index).  The same tiles over rows_host windows, so no more than pool_hashes hashes of rows are held at a time;
+    the same result, whatever pool_hashes, window and threads are"""
+    files_b = files_a if files_b is None else files_b
+
+    def take(files):
+        files = (np.ascontiguousarray(files[0], dtype=np.uint8), np.ascontiguousarray(files[1], dtype=np.uint32),
+                 np.ascontiguousarray(files[2], dtype=np.uint64)) + tuple(files[3:])
+        ids_end = (int(files[4]) if len(files) > 4 else 0) + int(files[3])
+
+        def f(ids, half):
+            if len(ids) and (int(ids[0]) < ids_end - int(files[3]) or int(ids[-1]) >= ids_end):
+                raise ValueError("row overlaps: an id is outside [first_id, first_id + n_structures)")
+            return _rowset_host(files, ids, window, half, threads)
+        return f
+    return _row_overlap_tiles(take(files_a), take(files_b), lambda A, B, ka, kb: rows_intersect_host(A, B, ka, kb, threads=threads), a, b, pool_hashes, stats)
+
+
 # ---- index signatures (include/fdgpu.h: fd_signature, fd_sig_pair) ---------------------------------------------------------------------------
-SIGNATURE_DTYPE = np.dtype([("n", "<u4"), ("reserved", "<u4"), ("d0", "<u8"), ("d1", "<u8"), ("sk", "<u4", (64,))])      # 280 bytes
+SIGNATURE_DTYPE =np.dtype([("n", "<u4"), ("reserved", "<u4"), ("d0", "<u8"), ("d1", "<u8"), ("sk", "<u4", (64,))])      # 280 bytes
 SIGNATURE_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("match", "u1"), ("filled", "u1"), ("flags", "<u2")])      # 12 bytes; flags bit 0 = identical
 SIGNATURE_PAIRS_DTYPE = np.dtype(SIGNATURE_PAIR_DTYPE.descr + [("estimate", "<f8")])      # what the pair calls return: the record + match / filled
 SIG_EMPTY = 0xffffffff

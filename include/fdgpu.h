@@ -694,6 +694,46 @@ int fdgpu_signature_clusters(fdgpu_ctx *ctx, const fd_signature *S, uint64_t n, 
 int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, uint32_t n_threads,
                                   fd_sig_neighbor **out);
 
+/* ---- exact row overlaps ------------------------------------------------------------------------------------------------------
+ * For structures a and b with rows R_a and R_b (the ascending distinct hashes whose posting lists hold them; what fdgpu_index_rows returns):
+ * the overlap is the integer inter = |R_a ∩ R_b|, union = |R_a| + |R_b| - inter, jaccard = inter / max(union, 1).  Integers only: the device
+ * form, the host form and a plain set intersection agree exactly.  A row set keeps the rows of chosen structures on the device; the
+ * intersect takes pairs of its row slots. */
+typedef struct fdgpu_rowset fdgpu_rowset;      /* rows of chosen structures, resident on the device */
+
+/* ids[0 .. n_ids): absolute structure ids of ix, strictly ascending.  Rows are taken in that order, window by window (windows of `window`
+ * structures, 0 = 16384, each starting at the first id not yet taken), until taking the next id's row would bring the set above max_hashes
+ * hashes; the first row of a call is always taken, whatever its size (max_hashes == 0: no limit).  *n_taken = the number of ids whose rows
+ * are in the set (a prefix of ids).  Row k of the set is the row of ids[k].
+ * The budget depends on the lengths of the rows alone: with L_k = |row of ids[k]|, n_taken is the largest t with t <= 1 or
+ * L_0 + .. + L_(t-1) <= max_hashes.  `window` decides which rows one pass over the index extracts, never which are taken.
+ * Per window the device stage of fdgpu_index_rows runs as it is, then a gather copies only the wanted rows into a block of the set (one
+ * block per window, from the allocator the indices share; lengths and destinations from a scan, no atomics); the full rows of a window
+ * never leave the device (csrc/k_overlap.hip).  FDGPU_EINVAL with a message opening "index rowset:", before any launch, no stage recorded
+ * and *out NULL: ids that do not ascend strictly, an id outside [first_id, first_id + n_structures), ids NULL with n_ids > 0, 2^32 or
+ * more ids.  A damaged index gives the codes of fdgpu_index_rows.  n_ids == 0: an empty set.  On any error *out is NULL, no device block is
+ * kept and the context stays usable.  Release with fdgpu_rowset_destroy. */
+int fdgpu_index_rowset(fdgpu_ctx *ctx, const fdgpu_index *ix, const uint32_t *ids, uint64_t n_ids, uint64_t window, uint64_t max_hashes,
+                       fdgpu_rowset **out, uint64_t *n_taken);
+int fdgpu_rowset_info(const fdgpu_rowset *rs, uint64_t *n_rows, uint64_t *n_hashes);
+/* lengths[k] = |row k|: max(n_rows, 1) values from the set's host side (no device work), released with fdgpu_free */
+int fdgpu_rowset_lengths(const fdgpu_rowset *rs, uint32_t **lengths);
+/* the set as CSR: hashes[row_off[k] .. row_off[k + 1]) = row k; n_rows + 1 offsets; both released with fdgpu_free */
+int fdgpu_rowset_export(fdgpu_ctx *ctx, const fdgpu_rowset *rs, uint32_t **hashes, uint64_t **row_off);
+/* inter[p] = |row ka[p] of A  ∩  row kb[p] of B| for p < n_pairs, in the order of the pairs; B == NULL: both rows from A.  max(n_pairs, 1)
+ * values, released with fdgpu_free.  One wavefront per pair walks both rows in 64-element tiles; the pairs are handed out longest first and
+ * the results written back in input order; a pure function of the two rows, no global atomic.  FDGPU_EINVAL with a message opening
+ * "rowset intersect:", before any launch, no stage recorded and *inter NULL: ka or kb NULL with n_pairs > 0, a slot >= the set's row
+ * count, 2^32 or more pairs.  n_pairs == 0: an empty result. */
+int fdgpu_rowset_intersect(fdgpu_ctx *ctx, const fdgpu_rowset *A, const fdgpu_rowset *B, const uint32_t *ka, const uint32_t *kb,
+                           uint64_t n_pairs, uint32_t **inter);
+void fdgpu_rowset_destroy(fdgpu_rowset *rs);
+/* the same intersect over host CSR arrays (rows ascending, as fdgpu_index_rows / fdgpu_rows_host return them; n_a and n_b are row counts,
+ * off_b == NULL: both rows from A), n_threads host threads (0 = 1), result independent of their number; no device.  The same refusals
+ * (code only; and FDGPU_EINVAL for offsets that descend); *inter is released with fdgpu_free. */
+int fdgpu_rows_intersect_host(const uint32_t *ha, const uint64_t *off_a, uint64_t n_a, const uint32_t *hb, const uint64_t *off_b, uint64_t n_b,
+                              const uint32_t *ka, const uint32_t *kb, uint64_t n_pairs, uint32_t n_threads, uint32_t **inter);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
