@@ -38,6 +38,40 @@ __host__ __device__ __forceinline__ uint64_t fd_varint_pack(uint32_t v, uint32_t
     return (uint64_t)(v >> 28) << 32 | (g | cont);
 }
 
+// ---- one element of a "constant" tile of the encoder's MSD stream (k_index.hip, enc_b24::cst): the element and its predecessor share the
+// bucket and hash[23:8], so their u32 key words k, pk (hash[7:0] << 24 | local id, pk <= k) carry all that tells them apart.  A list head is a
+// change of the top byte — never decided by k - pk: pk = 0x01000005, k = 0x02000001 differ by 0x00fffffc, a head that looks like a delta.
+__host__ __device__ __forceinline__ bool fd_const_is_head(uint32_t k, uint32_t pk) { return ((k ^ pk) >> 24) != 0; }
+// bytes a delta d < 2^31 writes: 0 for 0 (a repeat of the predecessor), else fd_varint_len(d) = ceil(bits(d) / 7).  d << 1 | 1 has one bit
+// more than d and is never 0, so the count of leading zeros needs no test for it; n / 7 = n * 37 >> 8 for the n <= 37 that occur.
+__host__ __device__ __forceinline__ uint32_t fd_delta_len(uint32_t d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t z = (uint32_t)__clz((int)(d << 1 | 1u));
+#else
+    const uint32_t z = (uint32_t)__builtin_clz(d << 1 | 1u);
+#endif
+    return (37u - z) * 37u >> 8;
+}
+// an element that is no head: the delta between the two words is the delta of the ids, exact because the top bytes are equal, and below 2^24
+__host__ __device__ __forceinline__ uint32_t fd_const_delta(uint32_t k, uint32_t pk, uint32_t *len) {
+    const uint32_t d = k - pk;
+    *len = fd_delta_len(d);
+    return d;
+}
+// a head: its absolute id
+__host__ __device__ __forceinline__ uint32_t fd_const_head(uint32_t k, uint32_t first_id, uint32_t *len) {
+    const uint32_t id = first_id + (k & 0xffffffu);
+    *len = fd_varint_len(id);
+    return id;
+}
+// the whole rule: is the element a head, the value it writes and its bytes.  The encoder runs fd_const_delta on every element and
+// fd_const_head behind a test of the wavefront's heads; tools/check_enc_const.cpp compares this with the rule on full hashes and ids.
+__host__ __device__ __forceinline__ bool fd_const_classify(uint32_t k, uint32_t pk, uint32_t first_id, uint32_t *value, uint32_t *len) {
+    const bool head = fd_const_is_head(k, pk);
+    *value = head ? fd_const_head(k, first_id, len) : fd_const_delta(k, pk, len);
+    return head;
+}
+
 // value and byte length of the varint at the low end of an 8-byte window
 __device__ __forceinline__ uint32_t fd_varint_at(unsigned long long w, uint32_t *nf) {
     const unsigned long long stop = ~w & 0x8080808080ull;            // terminator bits of the first five bytes

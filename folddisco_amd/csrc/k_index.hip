@@ -14,7 +14,8 @@
 // plane's low byte, then its high byte LAST, each pass stable), and fdgpu_debug_encode_stream_b24 checks it of a caller's stream.  Both passes
 // rely on it: a tile of ENC_TILE elements that lies in one bucket, predecessor element included, and whose two end elements carry the same u16
 // value holds that value everywhere, so such a tile reads two elements of the plane and not its 4 KB (enc_b24::cst).  The two passes take the
-// same decision for a tile: same predicate, same inputs.  Codecs 0 and 1 have no such path: their second plane is the id.
+// same decision for a tile: same predicate, same inputs.  A constant tile that is full and not tile 0 is also classified from the u32 key word alone
+// (enc_classify_const: 98 % of a protein build's tiles; again one predicate for both passes).  Codecs 0 and 1 have no such path: their second plane is the id.
 #include "fd_device.h"
 #include "fd_postings.h"
 
@@ -46,13 +47,15 @@ struct enc_b24 {              // B24: where the forty buckets start (bo[0..40], 
     uint32_t b0, b1;
     bool cst;                 // the tile and its predecessor element hold ONE u16 value, `ev` (workgroup-uniform; see the precondition above)
     uint32_t ev;
+    uint32_t wpk;             // the key word in front of the WAVE's first element: lane 0's predecessor (wave-uniform; meaningless where there is none)
     __device__ __forceinline__ uint32_t at(uint64_t p) const { uint32_t b = b0; while (b < b1 && p >= bo[b + 1]) ++b; return b; }      // tiles on a boundary only
 };
 // What a wave reads to classify its tile, per wave, no LDS and no barrier: lane l holds bo[l], every lane the u16 values at the tile's two ends (tp =
 // the predecessor of its first element, t1 = its last valid one).  Issued BEFORE the tile's key loads: the memory counter retires loads in issue
 // order, so enc_b24_setup's wait for these three leaves the key loads in flight, where behind them it would be the wait for the keys as well.
-struct enc_b24_raw { uint64_t o; uint32_t e0, e1; };
-__device__ __forceinline__ enc_b24_raw enc_b24_fetch(const uint64_t *__restrict__ bo, const uint16_t *__restrict__ vals, uint64_t n) {
+// With them, and for the same reason not behind the keys: the key word in front of the wave's first element (index clamped into the stream).
+struct enc_b24_raw { uint64_t o; uint32_t e0, e1, wpk; };
+__device__ __forceinline__ enc_b24_raw enc_b24_fetch(const uint32_t *__restrict__ keys, const uint64_t *__restrict__ bo, const uint16_t *__restrict__ vals, uint64_t n, bool full) {
     const uint64_t t0 = (uint64_t)blockIdx.x * (256 * 8);
     const uint64_t t1 = (t0 + 256 * 8 < n ? t0 + 256 * 8 : n) - 1;
     const uint64_t tp = t0 ? t0 - 1 : 0;
@@ -61,6 +64,9 @@ __device__ __forceinline__ enc_b24_raw enc_b24_fetch(const uint64_t *__restrict_
     R.o = lane >= 1 && lane <= ENC_BUCKETS ? bo[lane] : ~0ull;
     R.e0 = vals[tp];
     R.e1 = vals[t1];
+    const uint64_t w0 = t0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (64u * 8u);
+    const uint64_t wq = full || w0 < n ? w0 : n;      // full: the tile lies inside the stream; n >= 1
+    R.wpk = keys[wq ? wq - 1 : 0];
     return R;
 }
 __device__ __forceinline__ enc_b24 enc_b24_setup(const uint64_t *__restrict__ bo, uint64_t n, const enc_b24_raw &R) {
@@ -80,6 +86,7 @@ __device__ __forceinline__ enc_b24 enc_b24_setup(const uint64_t *__restrict__ bo
     const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)R.e0);
     K.ev = (uint32_t)__builtin_amdgcn_readfirstlane((int)R.e1);
     K.cst = (K.b0 == K.b1) & (e0 == K.ev);
+    K.wpk = R.wpk;
     return K;
 }
 __global__ void k_enc_bucket_starts(const uint64_t *__restrict__ seg_off, uint64_t S, uint64_t *__restrict__ bo) {
@@ -96,15 +103,13 @@ __device__ __forceinline__ enc_b24 enc_load_full(const uint32_t *__restrict__ ke
                                                  const uint64_t *__restrict__ bo, uint32_t *k, uint32_t *v) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     enc_b24_raw R = {};
-    if (B24) R = enc_b24_fetch(bo, (const uint16_t *)ids, n);
+    if (B24) R = enc_b24_fetch(keys, bo, (const uint16_t *)ids, n, true);
     const u32x4 *kp = reinterpret_cast<const u32x4 *>(keys + base);
     u32x4 a = __builtin_nontemporal_load(&kp[0]), b = __builtin_nontemporal_load(&kp[1]);
     k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w; k[4] = b.x; k[5] = b.y; k[6] = b.z; k[7] = b.w;
     enc_b24 K = {};
     if (B24) K = enc_b24_setup(bo, n, R);
-    if (B24 && K.cst) {      // workgroup-uniform
-#pragma unroll
-        for (int j = 0; j < ENC_ITEMS; ++j) v[j] = K.ev;
+    if (B24 && K.cst) {      // workgroup-uniform: nothing to load, and enc_load_classify fills v with K.ev where it goes the general way
     } else if (sizeof(V) == 2) {
         u32x4 w = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ids + base));
         v[0] = w.x & 0xffffu; v[1] = w.x >> 16; v[2] = w.y & 0xffffu; v[3] = w.y >> 16;
@@ -120,7 +125,7 @@ template <typename V, bool B24>
 __device__ __forceinline__ enc_b24 enc_load_tail(const uint32_t *__restrict__ keys, const V *__restrict__ ids, uint64_t n, uint64_t base,
                                                  const uint64_t *__restrict__ bo, uint32_t *k, uint32_t *v) {
     enc_b24 K = {};
-    if (B24) K = enc_b24_setup(bo, n, enc_b24_fetch(bo, (const uint16_t *)ids, n));
+    if (B24) K = enc_b24_setup(bo, n, enc_b24_fetch(keys, bo, (const uint16_t *)ids, n, false));
 #pragma unroll
     for (int j = 0; j < ENC_ITEMS; ++j) {
         uint64_t p = base + j;
@@ -130,18 +135,73 @@ __device__ __forceinline__ enc_b24 enc_load_tail(const uint32_t *__restrict__ ke
     return K;
 }
 
+// A full constant tile behind tile 0 (enc_load_classify's fast path; 98 % of a protein build's tiles): bucket and u16 value are the tile's, so the
+// key word alone tells heads, repeats and deltas (fd_postings.h: fd_const_*), no element lies beyond n, and every element has a predecessor —
+// the previous item, the neighbouring lane's last one, or for lane 0 keys[base - 1] (enc_b24::wpk), which belongs to the same constant run by the
+// definition of `cst`.  Every element is classified as a delta; what a list head needs beyond that (its id, its hash, the id in front of the thread) is made
+// behind one test of the wavefront's heads — one element in ~700 is a head — or, in the tile that ends the stream, for its last-id store.
+// -> ENC_FAST if the wavefront holds no head (it[].head, it[].hash are 0 and *pred_id is not written), else ENC_FAST_HEADS
+enum { ENC_GENERAL = 0, ENC_FAST = 1, ENC_FAST_HEADS = 2 };
+__device__ __forceinline__ int enc_classify_const(uint64_t n, uint32_t first_id, const enc_b24 &K,
+                                                  const uint32_t *k, enc_item *it, uint32_t *bytes, uint32_t *heads, uint32_t *pred_id) {
+    // the lane below's last key in one DPP move (wave_shr:1); lane 0 has no lane below and keeps the move's old value, the wave's predecessor
+    const uint32_t pk0 = (uint32_t)__builtin_amdgcn_update_dpp((int)K.wpk, (int)k[ENC_ITEMS - 1], 0x138, 0xf, 0xf, false);
+    uint32_t pk = pk0, hx = 0;
+#pragma unroll
+    for (int j = 0; j < ENC_ITEMS; ++j) {
+        hx |= k[j] ^ pk;
+        it[j].delta = fd_const_delta(k[j], pk, &it[j].len);
+        it[j].head = 0u; it[j].hash = 0u;
+        pk = k[j];
+    }
+    int path = ENC_FAST;
+    *heads = 0u;
+    const bool ends_stream = ((uint64_t)blockIdx.x + 1) * ENC_TILE == n;      // workgroup-uniform
+    if (__ballot((hx >> 24) != 0u) != 0ull || ends_stream) {      // wave-uniform
+        path = ENC_FAST_HEADS;
+        const uint32_t hash_hi = K.b0 << 24 | K.ev << 8;
+        uint32_t nh = 0;
+        pk = pk0;
+#pragma unroll
+        for (int j = 0; j < ENC_ITEMS; ++j) {
+            if (fd_const_is_head(k[j], pk)) {
+                it[j].delta = fd_const_head(k[j], first_id, &it[j].len);
+                it[j].head = 1u; it[j].hash = hash_hi | k[j] >> 24;
+                ++nh;
+            }
+            pk = k[j];
+        }
+        *heads = nh;
+        if (pred_id) *pred_id = first_id + (pk0 & 0xffffffu);
+    }
+    uint32_t b = 0;
+#pragma unroll
+    for (int j = 0; j < ENC_ITEMS; ++j) b += it[j].len;
+    *bytes = b;
+    return path;
+}
+
 // Loads the thread's elements and classifies them; the predecessor of the thread's first element comes from the neighbouring lane (shuffle)
-// or, for lane 0 of a wave, from memory.  B24: a constant tile (enc_b24::cst) reads nothing of the u16 plane but its two end elements.
+// or, for lane 0 of a wave, from memory.  B24: a constant tile (enc_b24::cst) reads nothing of the u16 plane but its two end elements, and if it is
+// full and not tile 0 it takes enc_classify_const — a workgroup-uniform decision, and the one expression for both passes.  Every other tile
+// (tile 0, whose element 0 has no predecessor; the stream's partial last tile; a tile on a bucket boundary or with a change of the u16 value)
+// goes the general way.  -> the path taken, the thread's bytes and heads; an element that writes nothing (a repeat, one beyond n) has len 0, delta 0.
 template <typename V, bool B24>
-__device__ __forceinline__ void enc_load_classify(const uint32_t *__restrict__ keys, const V *__restrict__ ids, uint64_t n, uint64_t base,
-                                                  uint32_t first_id, enc_item *it, const uint64_t *__restrict__ bo, uint32_t *pred_id = nullptr) {
+__device__ __forceinline__ int enc_load_classify(const uint32_t *__restrict__ keys, const V *__restrict__ ids, uint64_t n, uint64_t base,
+                                                 uint32_t first_id, enc_item *it, const uint64_t *__restrict__ bo, uint32_t *bytes, uint32_t *heads,
+                                                 uint32_t *pred_id = nullptr) {
     uint32_t k[ENC_ITEMS], v[ENC_ITEMS];
     // B24: by the tile and not by the thread, so that the whole workgroup goes one way (enc_b24_setup holds wave-wide ballots)
     const bool full = B24 ? ((uint64_t)blockIdx.x + 1) * ENC_TILE <= n : base + ENC_ITEMS <= n;
     const enc_b24 K = full ? enc_load_full<V, B24>(keys, ids, n, base, bo, k, v) : enc_load_tail<V, B24>(keys, ids, n, base, bo, k, v);
+    if (B24 && full && K.cst && blockIdx.x != 0) return enc_classify_const(n, first_id, K, k, it, bytes, heads, pred_id);
+    if (B24 && full && K.cst) {
+#pragma unroll
+        for (int j = 0; j < ENC_ITEMS; ++j) v[j] = K.ev;
+    }
     // predecessor of element 0
     uint32_t pk = __shfl_up(k[ENC_ITEMS - 1], 1, FD_WAVE), pv = __shfl_up(v[ENC_ITEMS - 1], 1, FD_WAVE);
-    if ((threadIdx.x & 63) == 0 && base > 0 && base < n) { pk = keys[base - 1]; pv = B24 && K.cst ? K.ev : (uint32_t)ids[base - 1]; }
+    if ((threadIdx.x & 63) == 0 && base > 0 && base < n) { pk = B24 ? K.wpk : keys[base - 1]; pv = B24 && K.cst ? K.ev : (uint32_t)ids[base - 1]; }
     uint32_t ph, pid;
     uint32_t hb[ENC_ITEMS];      // B24: the items' bucket << 24 — one value for the whole tile unless it lies on one of the 40 boundaries
     if (B24) {
@@ -157,6 +217,7 @@ __device__ __forceinline__ void enc_load_classify(const uint32_t *__restrict__ k
     } else { ph = enc_codec<V>::hash(pk); pid = enc_codec<V>::id(pk, (V)pv, first_id); }
     if (pred_id) *pred_id = pid;     // id of the element before the thread's first one (undefined for element 0)
     bool have_prev = base > 0;
+    uint32_t b = 0, nh = 0;
 #pragma unroll
     for (int j = 0; j < ENC_ITEMS; ++j) {
         uint64_t p = base + j;
@@ -168,12 +229,26 @@ __device__ __forceinline__ void enc_load_classify(const uint32_t *__restrict__ k
         bool dup = !head && pid == id;
         it[j].hash = h;
         it[j].head = (in && head) ? 1u : 0u;
-        it[j].delta = head ? id : id - pid;
+        it[j].delta = !in ? 0u : head ? id : id - pid;
         it[j].len = (!in || dup) ? 0u : fd_varint_len(it[j].delta);
+        b += it[j].len; nh += it[j].head;
         ph = h; pid = id; have_prev = true;
     }
+    *bytes = b; *heads = nh;
+    return ENC_GENERAL;
 }
 
+// inclusive prefix sum over the wavefront in six DPP adds (k_qtile.h: qt_wave_incl): row_shr 1/2/4/8 inside the rows of 16 lanes, then row_bcast:15 /
+// row_bcast:31 carry the row totals across; lane 63 ends with the wave's total
+__device__ __forceinline__ uint32_t enc_wave_incl(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+    return v;
+}
 __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
     uint32_t lane = threadIdx.x & 63;
     for (int off = 1; off < 64; off <<= 1) {
@@ -210,13 +285,28 @@ __global__ __launch_bounds__(ENC_THREADS) void k_enc_sizes(const uint32_t *__res
     uint64_t base = (uint64_t)blockIdx.x * ENC_TILE + (uint64_t)threadIdx.x * ENC_ITEMS;
     uint32_t bytes = 0, heads = 0, posts = 0;
     enc_item it[ENC_ITEMS];
-    enc_load_classify<V, B24>(keys, ids, n, base, first_id, it, bo);
+    const int path = enc_load_classify<V, B24>(keys, ids, n, base, first_id, it, bo, &bytes, &heads);
+    if (B24 && path != ENC_GENERAL) {      // workgroup-uniform.  Totals, not a scan: postings from the popcounts of the items' ballots (scalar), bytes and heads by one wave sum
+        __shared__ uint32_t sw[ENC_THREADS / 64][3];
+        uint32_t wp = 0;
 #pragma unroll
-    for (int k = 0; k < ENC_ITEMS; ++k) {
-        bytes += it[k].len;
-        heads += it[k].head;
-        posts += it[k].len ? 1u : 0u;
+        for (int k = 0; k < ENC_ITEMS; ++k) wp += (uint32_t)__popcll(__ballot(it[k].len != 0u));
+        const uint32_t mine = bytes << 16 | heads;      // below 2^16 each in a wave; heads are 0 but in a wavefront of ENC_FAST_HEADS
+        const uint32_t wbh = (uint32_t)__builtin_amdgcn_readlane((int)enc_wave_incl(mine), 63);
+        const uint32_t wb = wbh >> 16, wh = wbh & 0xffffu;
+        if ((threadIdx.x & 63) == 0) { uint32_t *w = sw[threadIdx.x >> 6]; w[0] = wb; w[1] = wh; w[2] = wp; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t t[3] = {0u, 0u, 0u};
+            for (int w = 0; w < ENC_THREADS / 64; ++w) for (int q = 0; q < 3; ++q) t[q] += sw[w][q];
+            tile_bytes[blockIdx.x] = t[0];
+            tile_heads[blockIdx.x] = t[1];
+            tile_posts[blockIdx.x] = t[2];
+        }
+        return;
     }
+#pragma unroll
+    for (int k = 0; k < ENC_ITEMS; ++k) posts += it[k].len ? 1u : 0u;
     uint64_t tot;
     block_excl_scan_packed(((uint64_t)bytes << 32) | heads, sm, &tot);
     // postings: separate reduction
@@ -245,7 +335,7 @@ __global__ __launch_bounds__(ENC_THREADS) void k_enc_write(const uint32_t *__res
                                                            uint8_t *__restrict__ value, uint32_t *__restrict__ hashes, uint64_t *__restrict__ offsets,
                                                            uint32_t *__restrict__ last_ids, const uint64_t *__restrict__ bo) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    __shared__ uint64_t sm[ENC_THREADS / 64];
+    __shared__ uint32_t sm[ENC_THREADS / 64];
     // varint bytes of the tile are assembled in LDS (pre-shifted by the global misalignment) and leave as
     // 16-byte stores instead of one global byte store per byte
     __shared__ __attribute__((aligned(16))) uint8_t s_bytes[ENC_LDS_BYTES];
@@ -254,60 +344,62 @@ __global__ __launch_bounds__(ENC_THREADS) void k_enc_write(const uint32_t *__res
     enc_item it[ENC_ITEMS];
     uint32_t bytes = 0, heads = 0;
     uint32_t run_id = 0;   // id of the element before item k (for the per-list last ids)
-    enc_load_classify<V, B24>(keys, ids, n, base, first_id, it, bo, &run_id);
-#pragma unroll
-    for (int k = 0; k < ENC_ITEMS; ++k) { bytes += it[k].len; heads += it[k].head; }
-    // block_excl_scan_packed, opened up: the tile's length is known after its first barrier, so the bytes the tile will use are zeroed
-    // between the two (the writer below ORs into them)
-    const uint64_t mine = ((uint64_t)bytes << 32) | heads;
-    const uint64_t inc = wave_incl_scan64(mine);
+    const int path = enc_load_classify<V, B24>(keys, ids, n, base, first_id, it, bo, &bytes, &heads, &run_id);
+    // one scan for both: a tile holds at most ENC_TILE * 5 bytes and ENC_TILE heads, 16 bits each (hi = bytes, lo = heads).  The tile's length is
+    // known after the scan's first barrier, so the bytes the tile will use are zeroed between the two (the writer below ORs into them)
+    static_assert(ENC_TILE * 5 < (1 << 16), "bytes and heads of a tile are scanned as the halves of one u32");
+    const uint32_t mine = bytes << 16 | heads;
+    const uint32_t inc = enc_wave_incl(mine);
     if ((threadIdx.x & 63) == 63) sm[threadIdx.x >> 6] = inc;
     const uint64_t tile_b0 = tile_byte_off[blockIdx.x];
     const uint32_t shift = (uint32_t)(tile_b0 & 15ull);
     __syncthreads();
-    uint64_t ex = inc - mine, tot = 0;
+    uint32_t ex = inc - mine, tot = 0;
 #pragma unroll
     for (uint32_t w = 0; w < ENC_THREADS / 64; ++w) {
-        const uint64_t t = sm[w];
+        const uint32_t t = sm[w];
         if (w < (threadIdx.x >> 6)) ex += t;
         tot += t;
     }
-    const uint32_t tile_len = (uint32_t)(tot >> 32);
+    const uint32_t tile_len = tot >> 16;
     const uint32_t end = shift + tile_len;                 // LDS range [shift, end) holds the tile's bytes
     for (uint32_t c = threadIdx.x * 16; c < end; c += ENC_THREADS * 16) *reinterpret_cast<u32x4 *>(s_bytes + c) = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
-    const uint32_t lo = shift + (uint32_t)(ex >> 32);      // LDS position of this thread's first byte
+    const uint32_t lo = shift + (ex >> 16);                // LDS position of this thread's first byte
     // list heads and the stream's last element: one item in ~700 of a protein index, so everything they need (64-bit offsets, the running id)
-    // stays out of the byte path
-    const bool tail = base < n && n - base <= ENC_ITEMS;
-    if (heads | (tail ? 1u : 0u)) {
-        uint64_t hoff = tile_head_off[blockIdx.x] + (uint32_t)ex;
-        const uint64_t boff = tile_b0 + (ex >> 32);
-        const uint32_t k_last = tail ? (uint32_t)(n - base) - 1u : ENC_ITEMS;
-        uint32_t pre = 0;
+    // stays out of the byte path; a wavefront of a constant tile that holds neither (ENC_FAST) does not even test for them
+    if (path != ENC_FAST) {      // wave-uniform
+        const bool tail = base < n && n - base <= ENC_ITEMS;
+        if (heads | (tail ? 1u : 0u)) {
+            uint64_t hoff = tile_head_off[blockIdx.x] + (ex & 0xffffu);
+            const uint64_t boff = tile_b0 + (ex >> 16);
+            const uint32_t k_last = tail ? (uint32_t)(n - base) - 1u : ENC_ITEMS;
+            uint32_t pre = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < ENC_ITEMS; ++k) {
-            if (it[k].head) {
-                hashes[hoff] = it[k].hash;
-                offsets[hoff] = boff + pre;
-                if (hoff) last_ids[hoff - 1] = run_id;            // the list before this head ends on the preceding element
-                ++hoff;
+            for (uint32_t k = 0; k < ENC_ITEMS; ++k) {
+                if (it[k].head) {
+                    hashes[hoff] = it[k].hash;
+                    offsets[hoff] = boff + pre;
+                    if (hoff) last_ids[hoff - 1] = run_id;            // the list before this head ends on the preceding element
+                    ++hoff;
+                }
+                run_id = it[k].head ? it[k].delta : run_id + it[k].delta;
+                if (k == k_last) last_ids[hoff - 1] = run_id;         // last element: its own id
+                pre += it[k].len;
             }
-            run_id = it[k].head ? it[k].delta : run_id + it[k].delta;
-            if (k == k_last) last_ids[hoff - 1] = run_id;         // last element: its own id
-            pre += it[k].len;
         }
     }
     // The thread's varints are adjacent in the output: each is packed in a register (fd_varint_pack) and appended to a 64-bit accumulator that
     // holds the bytes of the dword being filled (at most 3 pending + 5 new).  Every item ORs the accumulator's low dword into LDS — complete or
     // not: the bits are final, the next item's OR adds the rest — so the only branch is the second dword a five-byte varint can complete.  An OR
-    // and not a store, because a thread's first and last dwords also hold its neighbours' bytes.  A thread without bytes ORs zeros at its position.
+    // and not a store, because a thread's first and last dwords also hold its neighbours' bytes.  A thread without bytes ORs zeros at its position
+    // (a repeat or an element beyond n has len 0 AND delta 0: enc_load_classify).
     uint32_t pos = lo;
     uint64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < ENC_ITEMS; ++k) {
         const uint32_t len = it[k].len;
-        acc |= fd_varint_pack(len ? it[k].delta : 0u, len) << (8u * (pos & 3u));
+        acc |= fd_varint_pack(it[k].delta, len) << (8u * (pos & 3u));
         atomicOr(&s_dw[pos >> 2], (uint32_t)acc);
         const uint32_t npos = pos + len;
         const uint32_t filled = (npos >> 2) - (pos >> 2);          // dwords completed by this item: 0, 1, or 2
