@@ -257,6 +257,7 @@ SYMBOLS = [
     ("fdgpu_debug_merge_gathered", C.c_int, [VP, C.c_uint32, C.c_uint64, C.c_uint32, u8p, C.POINTER(C.POINTER(CountRec)), C.POINTER(u64p)]),
     ("fdgpu_debug_libm", C.c_int, [VP, C.c_int, f32p, f32p, f32p, C.c_uint64]),
     ("fdgpu_debug_last_count_path", C.c_int, [VP, u32p]),
+    ("fdgpu_debug_last_build_mask_bytes", C.c_int, [VP, u64p]),
     ("fdgpu_debug_last_retrieve_path", C.c_int, [VP, u32p]),
     ("fdgpu_debug_last_query_map_path", C.c_int, [VP, u32p]),
     ("fdgpu_debug_qm_pairs", C.c_int, [C.c_uint64, u32p, u64p, u32p, u64p, C.POINTER(u32p), C.POINTER(u32p), u64p]),

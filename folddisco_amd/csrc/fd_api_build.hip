@@ -282,7 +282,15 @@ static void ib_frames(fdgpu_ctx *c, const fdgpu_batch *b) {
 // MSD count: the residues in amino-acid order (V: the view of that order, which the emit takes too), then counts[bucket][work item] (the count pass
 // writes every entry: nothing to clear, and it makes the frames of its tile) and their exclusive scan in WS_SEGOFF, which IS the bucket-major layout —
 // every work item's slots in it are its own.  -> FDGPU_RETRY_WIDE when k_frames_perm met a residue type outside 0..19: no point in finishing this form.
-static int ib_count_msd(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_consts &C, fd_batch_view &V, uint64_t *P1) {
+// PAIR MASKS: the count pass also stores the pass mask of every (work item, partner) — one u64 per column of b->wi_col, WS_PAIR_MASKS — and the emit
+// pass replays them instead of running the distance filter a second time (k_hash.hip: fd_replay_block).  The table is a convenience, never a
+// condition: without it (FDGPU_PAIR_MASKS=0, read per call; a pair kernel other than the default one; a device that cannot hold it) the count pass
+// stores nothing and the emit pass filters, as both always did.  *masks: the table, or null.
+static bool ib_pair_masks_wanted(const fdgpu_ctx *c, const fd_hash_consts &C) {
+    const char *e = getenv("FDGPU_PAIR_MASKS");
+    return !(e && e[0] == '0') && C.use_tab == 3 && !c->pair_masks_crowded;
+}
+static int ib_count_msd(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_consts &C, fd_batch_view &V, uint64_t *P1, uint64_t **masks) {
     hipStream_t st = c->stream;
     const uint64_t R1 = std::max<uint64_t>(b->n_res, 1), NS = (uint64_t)IB_BUCKETS * b->n_work;
     HIPCHK(c, c->ws[WS_CA_PERM].ensure(R1 * 12));
@@ -301,10 +309,17 @@ static int ib_count_msd(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_consts
     HIPCHK(c, c->ws[WS_SEGOFF].ensure((NS + 2) * 8));
     HIPCHK(c, c->ws[WS_SCANTMP].ensure(fd_scan_tmp_elems(std::max<uint64_t>(NS, b->n_res)) * 8 + 64));
     HIPCHK(c, c->ws[WS_TOTAL].ensure(64));
+    *masks = nullptr;
+    if (ib_pair_masks_wanted(c, C) && b->wi_col) {
+        if (c->ws[WS_PAIR_MASKS].ensure((b->n_mask_cols + FD_MASK_SLACK_WORDS) * 8) == hipSuccess) *masks = c->ws[WS_PAIR_MASKS].as<uint64_t>();
+        else (void)hipGetLastError();      // no room for it: this call filters twice
+    }
     {
-        // per residue: CA, flag and type of the filter (14 B), the source index, N and CB (28 B) and the frame it stores; + the table
+        // per residue: CA, flag and type of the filter (14 B), the source index, N and CB (28 B) and the frame it stores; + the table.  The mask
+        // table's bytes (written here, read by the emit) are NOT in the stages' figures: tests/test_gpu_build_stage_lists.py pins those; they are
+        // reported on their own (fdgpu_debug_last_build_mask_bytes)
         StageTimer t(c, "pair_count", b->n_res * (14 + 28 + sizeof(fd_frame)) + NS * 4);
-        fd_launch_pair_count_msd(V, C, b->n_xyz, b->cb_xyz, c->ws[WS_SRC_PERM].as<uint32_t>(), c->ws[WS_FRAMES].p, c->ws[WS_COUNTS].as<uint32_t>(), st);
+        fd_launch_pair_count_msd(V, C, b->n_xyz, b->cb_xyz, c->ws[WS_SRC_PERM].as<uint32_t>(), c->ws[WS_FRAMES].p, c->ws[WS_COUNTS].as<uint32_t>(), *masks, st);
     }
     int rc = scan_counts(c, NS, P1);
     uint64_t odd = 0;
@@ -316,9 +331,10 @@ static void ib_emit_rows(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_param
     StageTimer t(c, "pair_emit", b->n_res * 37 + P * 8);
     fd_launch_row_emit(b->view(), C, c->ws[WS_MISC1].as<uint64_t>(), K.ka, p->dist_cutoff, (uint32_t *)K.ia, (uint32_t)first_id, c->stream);
 }
-static void ib_emit_msd(fdgpu_ctx *c, const fdgpu_batch *b, const fd_batch_view &V, const fd_hash_consts &C, const ib_keys &K, uint64_t P) {
+static void ib_emit_msd(fdgpu_ctx *c, const fdgpu_batch *b, const fd_batch_view &V, const fd_hash_consts &C, const ib_keys &K, uint64_t P, const uint64_t *masks) {
     StageTimer t(c, "pair_emit", b->n_res * 37 + P * 6);
-    fd_launch_pair_emit_msd(V, c->ws[WS_FRAMES].p, C, c->ws[WS_SEGOFF].as<uint64_t>(), K.ka, (uint16_t *)K.ia, c->stream);
+    c->last_build_mask_bytes = masks ? b->n_mask_cols * 8 : 0;
+    fd_launch_pair_emit_msd(V, c->ws[WS_FRAMES].p, C, c->ws[WS_SEGOFF].as<uint64_t>(), K.ka, (uint16_t *)K.ia, masks, c->stream);
 }
 // every bin pair of --multiple-bins contributes one key per ordered residue pair: one emit per pair, each from a cleared cursor
 static int ib_emit_structure_major(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_params *p, const ib_form &F, const fd_hash_consts &C, const ib_keys &K, uint64_t P,
@@ -357,6 +373,7 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
     ib_form F;
     int rc = ib_choose_form(c, b, p, first_id, force32, F);
     if (rc) return rc;
+    c->last_build_mask_bytes = 0;
     HIPCHK(c, c->ws[WS_FRAMES].ensure(std::max<uint64_t>(b->n_res, 1) * sizeof(fd_frame)));
     if ((rc = ib_clear_words(c))) return rc;
     fd_hash_consts C = fd_make_consts_cfg(p, 0);
@@ -380,11 +397,13 @@ static int index_build_impl(fdgpu_ctx *c, const fdgpu_batch *b, const fd_hash_pa
         if ((rc = ib_reserve_keys(c, F, P, K)) || (rc = ib_emit_structure_major(c, b, p, F, C, K, P, first_id))) return rc;
         cur = ib_sort(c, F, K, P);
         break;
-    case IB_MSD:
-        if ((rc = ib_count_msd(c, b, C, V, &P)) || (rc = ib_reserve_keys(c, F, P, K))) return rc;
-        ib_emit_msd(c, b, V, C, K, P);
+    case IB_MSD: {
+        uint64_t *masks = nullptr;
+        if ((rc = ib_count_msd(c, b, C, V, &P, &masks)) || (rc = ib_reserve_keys(c, F, P, K))) return rc;
+        ib_emit_msd(c, b, V, C, K, P, masks);
         if ((rc = ib_sort_msd(c, b, K, P, &cur))) return rc;
         break;
+    }
     }
     return encode_sorted_stream(c, cur ? K.kb : K.ka, cur ? K.ib : K.ia, F.codec, first_id, P, b->n_struct, F.seg_stride, out);
 }
@@ -393,7 +412,23 @@ extern "C" int fdgpu_index_build(fdgpu_ctx *c, const fdgpu_batch *b, const fd_ha
     const char *e32 = getenv("FDGPU_IDS32");   // FDGPU_IDS32=1 forces the 8-byte sort elements (read per call: tests flip it)
     int rc = index_build_impl(c, b, p, first_id, out, e32 && e32[0] == '1');
     if (rc == FDGPU_RETRY_WIDE) rc = index_build_impl(c, b, p, first_id, out, true);
+    if (rc == FDGPU_EHIP && c && c->ws[WS_PAIR_MASKS].p) {
+        // a HIP call failed with the mask table on the device — the sort buffers or the index may not fit beside it: the table goes back, this
+        // call is made again without it and so are the following ones (until fdgpu_release_workspaces)
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipGetLastError();
+        c->ws[WS_PAIR_MASKS].release();
+        c->pair_masks_crowded = true;
+        rc = index_build_impl(c, b, p, first_id, out, e32 && e32[0] == '1');
+        if (rc == FDGPU_RETRY_WIDE) rc = index_build_impl(c, b, p, first_id, out, true);
+    }
     return rc;
+}
+
+extern "C" int fdgpu_debug_last_build_mask_bytes(fdgpu_ctx *c, uint64_t *bytes) { FD_LOCK(c);
+    if (!c || !bytes) return FDGPU_EINVAL;
+    *bytes = c->last_build_mask_bytes;
+    return FDGPU_OK;
 }
 
 // ---- test-only (include/fdgpu_debug.h) ---------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ struct fd_batch_view {
     const uint32_t *res_off;     // [S+1]
     const uint32_t *wi_struct;   // [W] work item -> structure
     const uint32_t *wi_i0;       // [W] work item -> first residue (absolute) of its 64-residue i-tile
+    const uint64_t *wi_col;      // [W+1] work item -> first column of its pass masks in the MSD build's mask table (fd_pair_mask_cols.h)
     uint32_t n_struct;
     uint32_t n_work;
 };

@@ -199,6 +199,7 @@ extern "C" int fdgpu_release_workspaces(fdgpu_ctx *c) { FD_LOCK(c);
     if (!c) return FDGPU_EINVAL;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (auto &b : c->ws) b.release();
+    c->pair_masks_crowded = false;
     c->pool_drop();
     (void)hipGetLastError();
     return FDGPU_OK;
@@ -313,6 +314,7 @@ extern "C" int fdgpu_last_timings(const fdgpu_ctx *c, const char **names, float 
 int fd_build_work_items(fdgpu_ctx *c, fdgpu_batch *b, bool with_hash_ok) {
     // one work item per (structure, 64-residue i-tile)
     std::vector<uint32_t> ws, wi;
+    std::vector<uint64_t> wc;      // first column of every work item in the MSD build's mask table, + the total (fd_pair_mask_cols.h)
     std::vector<uint32_t> ro(b->n_struct + 1);
     for (uint64_t s = 0; s <= b->n_struct; ++s) ro[s] = (uint32_t)b->h_res_off[s];
     for (uint64_t s = 0; s < b->n_struct; ++s) {
@@ -322,7 +324,11 @@ int fd_build_work_items(fdgpu_ctx *c, fdgpu_batch *b, bool with_hash_ok) {
     }
     if (ws.size() > 0xfffffff0ull) FAIL(c, FDGPU_ERANGE, "too many tiles in one batch");
     b->n_work = (uint32_t)ws.size();
+    wc.resize(ws.size() + 1);
+    b->n_mask_cols = fd_mask_col_offsets(b->h_res_off.data(), b->n_struct, wc.data());
     HIPCHK(c, hipMalloc((void **)&b->res_off, ro.size() * 4));
+    HIPCHK(c, hipMalloc((void **)&b->wi_col, wc.size() * 8));
+    HIPCHK(c, hipMemcpyAsync(b->wi_col, wc.data(), wc.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMalloc((void **)&b->wi_struct, std::max<size_t>(ws.size(), 1) * 4));
     HIPCHK(c, hipMalloc((void **)&b->wi_i0, std::max<size_t>(wi.size(), 1) * 4));
     HIPCHK(c, hipMemcpyAsync(b->res_off, ro.data(), ro.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -385,6 +391,7 @@ extern "C" void fdgpu_batch_destroy(fdgpu_batch *b) {
     if (!b) return;
     if (b->owns) { (void)hipFree(b->n_xyz); (void)hipFree(b->ca_xyz); (void)hipFree(b->cb_xyz); (void)hipFree(b->aa); (void)hipFree(b->cb_valid); }
     (void)hipFree(b->hash_ok); (void)hipFree(b->res_off); (void)hipFree(b->wi_struct); (void)hipFree(b->wi_i0);
+    (void)hipFree(b->wi_col);
     delete b;
 }
 extern "C" uint64_t fdgpu_batch_num_structures(const fdgpu_batch *b) { return b ? b->n_struct : 0; }

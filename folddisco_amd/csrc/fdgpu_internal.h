@@ -14,6 +14,7 @@
 
 #include "fd_host_pool.h"
 #include "fd_match_tables.h"
+#include "fd_pair_mask_cols.h"
 
 struct fd_devbuf {
     void *p = nullptr;
@@ -43,6 +44,7 @@ enum {
     WS_CQ_KIDX, WS_CQ_NSEG, WS_CQ_WSTART, WS_CQ_SEGSUM, WS_CQ_TOPN,
     WS_QT_RANGES, WS_QT_COMPACT, WS_QT_COUNT, WS_QT_AUX, WS_RS_PLAN, WS_RS_REC, WS_RS_RECRES, WS_QT_PARTIAL, WS_QT_SURV, WS_QT_ROWBITS, WS_QT_STREAM, WS_QT_STAB, WS_QT_PIECEP, WS_QT_WIN, WS_QT_HEAD, WS_RS_SPLIT, WS_MP_QSET,
     WS_CA_PERM, WS_OK_PERM, WS_AA_PERM, WS_SRC_PERM /* MSD build: the residue that landed at every position of the amino-acid order */, WS_SEG_TAB,
+    WS_PAIR_MASKS /* MSD build: the pass masks of every (work item, partner), count pass -> emit pass (fd_pair_mask_cols.h) */,
     WS_RS_TAB, WS_RS_SEG, WS_RS_OUT, WS_RS_RES, WS_RS_KX, WS_RS_KY, WS_RS_KOFF, WS_RS_SOL, WS_RS_CNT, WS_RS_GQ, WS_MP_ACT, WS_MP_Q,
     WS_SG_TAB /* signatures of a window; table A of a compare */, WS_SG_TAB_B, WS_SG_PAIRS, WS_SG_CURSOR,
     WS_SG_NB_PART /* signature neighbours: the k-lists of every split, [split][query][k] */, WS_SG_NB_OUT /* the merged lists, [query][k] */,
@@ -74,6 +76,8 @@ struct fdgpu_ctx {
     uint32_t last_count_path = 0;          // FDGPU_PATH_* decisions of the last count call (fdgpu_debug_last_count_path: tests at the dispatch's switches)
     uint32_t last_query_map_path = 0;      // FDGPU_QMPATH_* of the last query-map call that reached qm_choose_form (fdgpu_debug_last_query_map_path)
     fd_devbuf ws[WS_COUNT];
+    uint64_t last_build_mask_bytes = 0;    // bytes of the mask table the emit pass of the last build call replayed, 0: it ran the distance filter (fdgpu_debug_last_build_mask_bytes)
+    bool pair_masks_crowded = false;       // a build call failed with WS_PAIR_MASKS resident and was made again without it: no table until the workspaces are released
     bool timing = false;
     // Every entry point that takes the context locks it: concurrent callers (the reference calls its seams from rayon workers,
     // controller/mod.rs:291, query_pdb.rs:348,415) are safe and run one at a time per context — one stream, one scratch set;
@@ -176,11 +180,13 @@ struct fdgpu_batch {
     float *n_xyz = nullptr, *ca_xyz = nullptr, *cb_xyz = nullptr;
     uint8_t *aa = nullptr, *cb_valid = nullptr, *hash_ok = nullptr;
     uint32_t *res_off = nullptr, *wi_struct = nullptr, *wi_i0 = nullptr;
+    uint64_t *wi_col = nullptr;      // [n_work + 1] work item -> first column of its pass masks (fd_pair_mask_cols.h); a property of the batch
+    uint64_t n_mask_cols = 0;        // wi_col[n_work]
     std::vector<uint64_t> h_res_off;  // host copy
     fd_batch_view view() const {
         fd_batch_view v;
         v.n_xyz = n_xyz; v.ca_xyz = ca_xyz; v.cb_xyz = cb_xyz; v.aa = aa; v.hash_ok = hash_ok; v.res_off = res_off;
-        v.wi_struct = wi_struct; v.wi_i0 = wi_i0; v.n_struct = (uint32_t)n_struct; v.n_work = n_work;
+        v.wi_struct = wi_struct; v.wi_i0 = wi_i0; v.wi_col = wi_col; v.n_struct = (uint32_t)n_struct; v.n_work = n_work;
         return v;
     }
 };
@@ -305,9 +311,9 @@ int fd_radix_sort_pairs16(uint32_t *keys_a, uint16_t *vals_a, uint32_t *keys_b, 
                           uint64_t *tot, hipStream_t st, fdgpu_ctx *timing_ctx = nullptr);
 void fd_launch_frames_perm(const fd_batch_view &B, float *ca_perm, uint8_t *ok_perm, uint8_t *aa_perm, uint32_t *src_perm, unsigned long long *wide_flag, hipStream_t st);
 void fd_launch_pair_count_msd(const fd_batch_view &B, const fd_hash_consts &C, const float *n_xyz, const float *cb_xyz, const uint32_t *src_perm, void *frames,
-                              uint32_t *counts, hipStream_t st);
+                              uint32_t *counts, uint64_t *masks, hipStream_t st);
 void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const fd_hash_consts &C, const uint64_t *seg_off, uint32_t *keys,
-                             uint16_t *ids, hipStream_t st);
+                             uint16_t *ids, const uint64_t *masks, hipStream_t st);
 uint32_t fd_rs_seg_num_tiles(uint64_t n, uint32_t n_seg);
 uint64_t fd_rs_seg_tot_words(uint64_t n, uint32_t n_seg);
 size_t fd_rs_seg_tab_bytes(uint64_t n, uint32_t n_seg);

@@ -145,6 +145,37 @@ typedef float fd_f2 __attribute__((ext_vector_type(2)));
 #define FD_NOT_HASHABLE 0x100u
 
 __device__ __forceinline__ bool fd_lane_of(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }   // the lane's bit of a wave-uniform mask, no VALU
+// v_writelane_b32: `old` with the wave-uniform val in lane `lane` (wave-uniform, < 64).  The compiler has no builtin for it; the lane select goes
+// through M0, which the compiler loads itself (the value and the lane select may not both be general scalar registers on gfx9).
+__device__ __forceinline__ uint32_t fd_writelane(uint32_t old, uint32_t val, uint32_t lane) {
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(val), "{m0}"(lane));
+    return old;
+}
+
+// The run structure of one block of 64 partners, from the lanes' kinds alone: what fd_filter_block walks, and what the replay of stored masks
+// (fd_replay_block) walks again — both take their skips, their run ends and `last` from here.
+struct fd_block_runs {
+    uint64_t starts;      // bit k: a run starts at partner k
+    uint32_t nkf;         // partners to walk: up to the last hashable one; an empty last block still makes the one step that carries `last`
+    bool last_block;
+};
+__device__ __forceinline__ fd_block_runs fd_runs_of_block(uint32_t kind, uint32_t jb, uint32_t r1) {
+    fd_block_runs R;
+    const uint64_t okm = __ballot(kind != FD_NOT_HASHABLE);
+    R.starts = __ballot(kind != (uint32_t)__shfl_up((int)kind, 1, FD_WAVE)) | 1ull;
+    R.last_block = jb + FD_WAVE >= r1;
+    const uint32_t nk = okm ? 64u - (uint32_t)__builtin_clzll(okm) : 0u;
+    R.nkf = (R.last_block && nk == 0) ? 1u : nk;
+    return R;
+}
+// the run that starts at partner k: its kind t, its end ke; run_last: nothing follows it in the work item
+__device__ __forceinline__ void fd_run_at(const fd_block_runs &R, uint32_t kind, uint32_t k, uint32_t &t, uint32_t &ke, bool &run_last) {
+    t = (uint32_t)__builtin_amdgcn_readlane((int)kind, (int)k);
+    const uint64_t rest = (R.starts >> k) >> 1;
+    ke = rest ? k + 1u + (uint32_t)__builtin_ctzll(rest) : (uint32_t)FD_WAVE;
+    ke = ke < R.nkf ? ke : R.nkf;
+    run_last = R.last_block && ke >= R.nkf;
+}
 
 template <bool TYPES, class Step, class RunEnd>
 __device__ __forceinline__ void fd_filter_block(const fd_batch_view &B, float d2_max, const fd_v3 &cai, uint64_t vim, uint32_t i0, uint32_t jb, uint32_t r1,
@@ -160,20 +191,14 @@ __device__ __forceinline__ void fd_filter_block(const fd_batch_view &B, float d2
     fd_wave_lds_fence();
     s_cj[lane] = cj.x; s_cj[FD_WAVE + lane] = cj.y; s_cj[2 * FD_WAVE + lane] = cj.z;
     fd_wave_lds_fence();
-    const uint64_t okm = __ballot(kind != FD_NOT_HASHABLE);
-    const uint64_t starts = __ballot(kind != (uint32_t)__shfl_up((int)kind, 1, FD_WAVE)) | 1ull;   // bit k: a run starts at partner k
-    const bool last_block = jb + FD_WAVE >= r1;
-    const uint32_t nk = okm ? 64u - (uint32_t)__builtin_clzll(okm) : 0u;
-    const uint32_t nkf = (last_block && nk == 0) ? 1u : nk;      // an empty last block still makes the one step that carries `last`
+    const fd_block_runs R = fd_runs_of_block(kind, jb, r1);
     const bool first = jb == i0;
     const fd_f2 ax = {cai.x, cai.x}, ay = {cai.y, cai.y}, az = {cai.z, cai.z};
     uint32_t k = 0;
-    while (k < nkf) {
-        const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)kind, (int)k);
-        const uint64_t rest = (starts >> k) >> 1;
-        uint32_t ke = rest ? k + 1u + (uint32_t)__builtin_ctzll(rest) : (uint32_t)FD_WAVE;
-        ke = ke < nkf ? ke : nkf;
-        const bool run_last = last_block && ke >= nkf;
+    while (k < R.nkf) {
+        uint32_t t, ke;
+        bool run_last;
+        fd_run_at(R, kind, k, t, ke, run_last);
         const bool dead = t == FD_NOT_HASHABLE;
         if (dead && !run_last) { k = ke; continue; }
         const uint64_t vr = dead ? 0ull : vim;
@@ -192,6 +217,38 @@ __device__ __forceinline__ void fd_filter_block(const fd_batch_view &B, float d2
         } while (k < ke);
         k = ke;
         run_end(t);
+    }
+}
+
+// REPLAY of the masks the MSD count pass stored (k_pair_count_msd<true>): the same callback contract as fd_filter_block<true> — step(k, t, m0, m1,
+// last), the same runs, the same `last` — without one distance: cols = the 64 words of this block in the mask table (fd_pair_mask_cols.h), word k =
+// the final pass mask of partner jb + k (j > i, the tile's valid lanes and the dead runs applied; zero where the count pass made no step).  The
+// partners' kinds are loaded as there, so the skips, the run ends and `last` are derived from the same ballots (fd_runs_of_block).
+// A step takes its two words with ONE scalar load (s_load_dwordx4 at a wave-uniform address, straight into the scalar registers that the queue
+// code wants them in): no VALU, no LDS, no CA for the filter.  The second word is read even where it is not the step's (the run ends at k + 1, or
+// k = 63: the word behind the block, FD_MASK_SLACK_WORDS behind the table) and dropped.  Measured against one 8-byte vector load per lane and
+// block + four v_readlane per step, and against the same scalar load requested a step ahead (HISTORY.md): this form was the fastest.
+typedef uint64_t fd_u64x2 __attribute__((ext_vector_type(2), aligned(8)));
+template <class Step>
+__device__ __forceinline__ void fd_replay_block(const fd_batch_view &B, const uint64_t *__restrict__ cols, uint32_t jb, uint32_t r1, Step &&step) {
+    const uint32_t jl = jb + threadIdx.x;
+    uint32_t kind = FD_NOT_HASHABLE;
+    if (jl < r1 && B.hash_ok[jl]) kind = (uint32_t)B.aa[jl];
+    const fd_block_runs R = fd_runs_of_block(kind, jb, r1);
+    uint32_t k = 0;
+    while (k < R.nkf) {
+        uint32_t t, ke;
+        bool run_last;
+        fd_run_at(R, kind, k, t, ke, run_last);
+        if (t == FD_NOT_HASHABLE && !run_last) { k = ke; continue; }
+        do {
+            const fd_u64x2 m = *reinterpret_cast<const fd_u64x2 *>(cols + k);      // wave-uniform address
+            const uint64_t m1 = (k + 1u < ke) ? m.y : 0ull;      // else the word belongs to the next run
+            const uint32_t k0 = k;
+            k += 2;
+            step(k0, t, m.x, m1, run_last && k >= ke);
+        } while (k < ke);
+        k = ke;
     }
 }
 
@@ -286,8 +343,15 @@ __global__ __launch_bounds__(256) void k_frames_perm(fd_batch_view B, float *__r
 // lane l gathers N and CB of the residue that landed at i0 + l (src_perm; n_xyz / cb_xyz are the batch's arrays in chain order), builds
 // the frame and stores it for the emit pass.  The kernel is bound by the filter loop's scalar instructions; the frames ride in its idle
 // vector and memory slots.
+// STORE: the pass masks of every step are kept for the emit pass (fd_replay_block), which then runs no distance test.  m0 / m1 are final words in
+// scalar registers; a step puts them into lanes k and k + 1 of one register pair (four v_writelane) and the block's 64 words leave with one
+// coalesced 8-byte vector store per lane.  The pair starts every block at zero and every lane stores, so the dead runs, the odd run tails, the partners behind the
+// last hashable one and the padding columns are zero words written by THIS call: nothing of an earlier call shows and nothing is cleared.  The
+// counts are taken from the very words that are stored.
+template <bool STORE>
 __global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_hash_consts C, const float *__restrict__ n_xyz, const float *__restrict__ cb_xyz,
-                                                            const uint32_t *__restrict__ src_perm, fd_frame *__restrict__ frames, uint32_t *__restrict__ counts) {
+                                                            const uint32_t *__restrict__ src_perm, fd_frame *__restrict__ frames, uint32_t *__restrict__ counts,
+                                                            uint64_t *__restrict__ masks) {
     __shared__ uint32_t s_cnt[FD_WAVE];
     __shared__ float s_cj[3 * FD_WAVE + 1];
     uint32_t w = fd_xcd_remap(blockIdx.x, B.n_work);
@@ -313,14 +377,28 @@ __global__ __launch_bounds__(FD_WAVE) void k_pair_count_msd(fd_batch_view B, fd_
     const uint64_t vim = __ballot(vi);
     uint32_t c_lo = 0, c_hi = 0, run = 0;
     const uint32_t hi_i = aai >> 4;
-    for (uint32_t jb = i0; jb < r1; jb += FD_WAVE)
+    uint2 *mrow = STORE ? reinterpret_cast<uint2 *>(masks + B.wi_col[w]) + lane : nullptr;      // this lane's word of the work item's first block
+    for (uint32_t jb = i0; jb < r1; jb += FD_WAVE) {
+        uint32_t c_x = 0, c_y = 0;      // lane k: the mask of partner jb + k
         fd_filter_block<true>(B, C.d2_max, cai, vim, i0, jb, r1, s_cj,
-                              [&](uint32_t, uint32_t, uint64_t m0, uint64_t m1, bool) { run += (fd_lane_of(m0) ? 1u : 0u) + (fd_lane_of(m1) ? 1u : 0u); },
+                              [&](uint32_t k, uint32_t, uint64_t m0, uint64_t m1, bool) {
+                                  run += (fd_lane_of(m0) ? 1u : 0u) + (fd_lane_of(m1) ? 1u : 0u);
+                                  if (STORE) {
+                                      // m1 first, at lane min(k + 1, 63): a step at k = 63 has m1 = 0 and no lane 64 — its zero goes where m0 follows
+                                      const uint32_t k1 = k + 1u < FD_WAVE ? k + 1u : FD_WAVE - 1u;
+                                      c_x = fd_writelane(c_x, (uint32_t)m1, k1);
+                                      c_y = fd_writelane(c_y, (uint32_t)(m1 >> 32), k1);
+                                      c_x = fd_writelane(c_x, (uint32_t)m0, k);
+                                      c_y = fd_writelane(c_y, (uint32_t)(m0 >> 32), k);
+                                  }
+                              },
                               [&](uint32_t t) {      // t: wave-uniform; FD_NOT_HASHABLE only with run == 0 in every lane
                                   if (t >= 16u) c_hi += run; else c_lo += run;
                                   if (run) atomicAdd(&s_cnt[(t * 2u + hi_i) & (FD_WAVE - 1u)], run);
                                   run = 0;
                               });
+        if (STORE) { *mrow = make_uint2(c_x, c_y); mrow += FD_WAVE; }
+    }
     if (c_lo) atomicAdd(&s_cnt[aai * 2u], c_lo);
     if (c_hi) atomicAdd(&s_cnt[aai * 2u + 1u], c_hi);
     __syncthreads();
@@ -454,12 +532,16 @@ __device__ __forceinline__ void drain2(const fd_batch_view &B, const fd_frame *_
     }
 }
 
-template <int TAB, bool IDS16, bool MSD, bool DT = false>
+// MASKS (MSD only): the pass masks come from the table the count pass stored (fd_replay_block) instead of from fd_filter_block — the kernel
+// then holds no CA of its own tile, no staged partner CAs (s_cj) and makes no distance test; the queue, the drain site and drain2 are the same.
+template <int TAB, bool IDS16, bool MSD, bool DT = false, bool MASKS = false>
 __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_view B, const fd_frame *__restrict__ frames, fd_hash_consts C,
                                                         const uint64_t *__restrict__ seg_off, uint32_t *__restrict__ cursor,
-                                                        uint32_t *__restrict__ keys, void *__restrict__ ids, uint32_t first_id) {
+                                                        uint32_t *__restrict__ keys, void *__restrict__ ids, uint32_t first_id,
+                                                        const uint64_t *__restrict__ masks) {
+    static_assert(!MASKS || MSD, "the mask table belongs to the MSD build");
     __shared__ uint32_t q[3 * FD_WAVE];      // a step queues up to 2 x 64 entries on top of the < 64 left by the drains before it
-    __shared__ float s_cj[3 * FD_WAVE + 1];
+    __shared__ float s_cj[MASKS ? 1 : 3 * FD_WAVE + 1];
     __shared__ uint32_t tab[DT ? 64 + FD_DIST_NTHR + 1 : 64];   // [0,27) exact table (bit patterns), [32,59) the same with float thresholds for the speculative path,
                                                                  // DT: [64, 64 + FD_DIST_NTHR) the squared-distance breakpoints of the two distance fields
     uint32_t w = fd_xcd_remap(blockIdx.x, B.n_work);
@@ -479,9 +561,6 @@ __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_
     const uint32_t i0 = B.wi_i0[w];
     const uint32_t lane = threadIdx.x;
     const uint32_t i = i0 + lane;
-    const bool vi = i < r1 && B.hash_ok[i];
-    fd_v3 cai = {0.f, 0.f, 0.f};
-    if (vi) cai = fd_load3(B.ca_xyz, i);
     // LDS staging of the work item's residue tile: the hot 64 bytes of the 64 frames of the i side (4 KB), plane-major so that the fill
     // is conflict-free; every drain reads its i frames from here instead of gathering them from L2 again
     __shared__ float4 s_fi[4 * FD_WAVE];
@@ -494,34 +573,39 @@ __global__ __launch_bounds__(FD_WAVE, FD_EMIT_WAVES) void k_pair_emit2(fd_batch_
     __shared__ uint64_t s_boff[MSD ? FD_MSD_BUCKETS : 1];      // forty, not 64: the workgroup stays below 8 KB, 20 of them on a CU
     if (MSD && lane < FD_MSD_BUCKETS) s_boff[lane] = seg_off[(uint64_t)lane * B.n_work + w];      // where the work item's keys of every bucket start: its cursor
     __syncthreads();
-    const uint64_t vim = __ballot(vi);
     const uint32_t lane16 = lane << 16;
     uint32_t qn = 0;  // wave-uniform
+    uint32_t jrel = i0 - r0;      // the block's first partner, relative to the structure
     // single drain site (two inlined copies of the descriptor code would not fit the I-cache): the two ballots of a step are queued one
-    // after the other in front of it, and the step that fd_filter_block marks `last` flushes what is left (up to three drains).
-    for (uint32_t jb = i0; jb < r1; jb += FD_WAVE) {
-        const uint32_t jrel = jb - r0;
-        fd_filter_block<MSD>(B, C.d2_max, cai, vim, i0, jb, r1, s_cj,
-            [&](uint32_t k, uint32_t t, uint64_t m0, uint64_t m1, bool last) {
-                // queue entry: lane << 16 | partner (relative to the structure); MSD: bits 22-26 = the partner's residue type, the run's
-                const uint32_t tag = (MSD ? t << 22 : 0u) | (jrel + k);
-                if (m0) {
-                    if (fd_lane_of(m0)) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, qn))] = lane16 | tag;
-                    qn += (uint32_t)__popcll(m0);
-                }
-                if (m1) {
-                    if (fd_lane_of(m1)) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, qn))] = lane16 | (tag + 1u);
-                    qn += (uint32_t)__popcll(m1);
-                }
-                while (qn >= FD_WAVE || (last && qn)) {
-                    fd_wave_lds_fence();
-                    uint32_t n = qn < FD_WAVE ? qn : FD_WAVE;
-                    qn -= n;
-                    drain2<TAB, IDS16, MSD, DT>(B, frames, C, tab, q + qn, n, i0, r0, s, first_id + s, seg_off, cursor, keys, ids, s_fi, s_bc, s_boff);
-                    fd_wave_lds_fence();
-                }
-            },
-            [](uint32_t) {});
+    // after the other in front of it, and the step that the filter (or the replay) marks `last` flushes what is left (up to three drains).
+    auto step = [&](uint32_t k, uint32_t t, uint64_t m0, uint64_t m1, bool last) {
+        // queue entry: lane << 16 | partner (relative to the structure); MSD: bits 22-26 = the partner's residue type, the run's
+        const uint32_t tag = (MSD ? t << 22 : 0u) | (jrel + k);
+        if (m0) {
+            if (fd_lane_of(m0)) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, qn))] = lane16 | tag;
+            qn += (uint32_t)__popcll(m0);
+        }
+        if (m1) {
+            if (fd_lane_of(m1)) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, qn))] = lane16 | (tag + 1u);
+            qn += (uint32_t)__popcll(m1);
+        }
+        while (qn >= FD_WAVE || (last && qn)) {
+            fd_wave_lds_fence();
+            uint32_t n = qn < FD_WAVE ? qn : FD_WAVE;
+            qn -= n;
+            drain2<TAB, IDS16, MSD, DT>(B, frames, C, tab, q + qn, n, i0, r0, s, first_id + s, seg_off, cursor, keys, ids, s_fi, s_bc, s_boff);
+            fd_wave_lds_fence();
+        }
+    };
+    if constexpr (MASKS) {
+        const uint64_t *cols = masks + B.wi_col[w];      // the work item's columns: whole blocks of 64 (fd_pair_mask_cols.h)
+        for (uint32_t jb = i0; jb < r1; jb += FD_WAVE, jrel += FD_WAVE, cols += FD_WAVE) fd_replay_block(B, cols, jb, r1, step);
+    } else {
+        const bool vi = i < r1 && B.hash_ok[i];
+        fd_v3 cai = {0.f, 0.f, 0.f};
+        if (vi) cai = fd_load3(B.ca_xyz, i);
+        const uint64_t vim = __ballot(vi);
+        for (uint32_t jb = i0; jb < r1; jb += FD_WAVE, jrel += FD_WAVE) fd_filter_block<MSD>(B, C.d2_max, cai, vim, i0, jb, r1, s_cj, step, [](uint32_t) {});
     }
 }
 
@@ -665,33 +749,39 @@ void fd_launch_pair_emit2(const fd_batch_view &B, const void *frames, const fd_h
     if (!B.n_work) return;
     dim3 g(grid_for(B.n_work)), b(FD_WAVE);
     const fd_frame *F = (const fd_frame *)frames;
-    if (C.use_tab >= 2 && ids16) hipLaunchKernelGGL((k_pair_emit2<2, true, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
-    else if (C.use_tab >= 2) hipLaunchKernelGGL((k_pair_emit2<2, false, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
-    else if (C.use_tab && ids16) hipLaunchKernelGGL((k_pair_emit2<1, true, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
-    else if (C.use_tab) hipLaunchKernelGGL((k_pair_emit2<1, false, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
-    else if (ids16) hipLaunchKernelGGL((k_pair_emit2<0, true, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
-    else hipLaunchKernelGGL((k_pair_emit2<0, false, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id);
+    if (C.use_tab >= 2 && ids16) hipLaunchKernelGGL((k_pair_emit2<2, true, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id, (const uint64_t *)nullptr);
+    else if (C.use_tab >= 2) hipLaunchKernelGGL((k_pair_emit2<2, false, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id, (const uint64_t *)nullptr);
+    else if (C.use_tab && ids16) hipLaunchKernelGGL((k_pair_emit2<1, true, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id, (const uint64_t *)nullptr);
+    else if (C.use_tab) hipLaunchKernelGGL((k_pair_emit2<1, false, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id, (const uint64_t *)nullptr);
+    else if (ids16) hipLaunchKernelGGL((k_pair_emit2<0, true, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id, (const uint64_t *)nullptr);
+    else hipLaunchKernelGGL((k_pair_emit2<0, false, false>), g, b, 0, st, B, F, C, seg_off, cursor, keys, ids, first_id, (const uint64_t *)nullptr);
 }
 // the MSD build (6-byte elements): B = the permuted view (ca_xyz / hash_ok / aa = the arrays k_frames_perm wrote), counts / seg_off = [40][n_work]
 void fd_launch_frames_perm(const fd_batch_view &B, float *ca_perm, uint8_t *ok_perm, uint8_t *aa_perm, uint32_t *src_perm, unsigned long long *wide_flag, hipStream_t st) {
     if (!B.n_struct) return;
     hipLaunchKernelGGL(k_frames_perm, dim3(B.n_struct), dim3(256), 0, st, B, ca_perm, ok_perm, aa_perm, src_perm, wide_flag);
 }
-// n_xyz / cb_xyz: the batch's own arrays (chain order), src_perm: what k_frames_perm wrote; the kernel fills frames (permuted order)
+// n_xyz / cb_xyz: the batch's own arrays (chain order), src_perm: what k_frames_perm wrote; the kernel fills frames (permuted order) and, where
+// masks is not null, the mask table ([B.wi_col[n_work]] words) that fd_launch_pair_emit_msd then takes
 void fd_launch_pair_count_msd(const fd_batch_view &B, const fd_hash_consts &C, const float *n_xyz, const float *cb_xyz, const uint32_t *src_perm, void *frames,
-                              uint32_t *counts, hipStream_t st) {
+                              uint32_t *counts, uint64_t *masks, hipStream_t st) {
     if (!B.n_work) return;
-    hipLaunchKernelGGL(k_pair_count_msd, dim3(grid_for(B.n_work)), dim3(FD_WAVE), 0, st, B, C, n_xyz, cb_xyz, src_perm, (fd_frame *)frames, counts);
+    dim3 g(grid_for(B.n_work)), b(FD_WAVE);
+    if (masks) hipLaunchKernelGGL(k_pair_count_msd<true>, g, b, 0, st, B, C, n_xyz, cb_xyz, src_perm, (fd_frame *)frames, counts, masks);
+    else hipLaunchKernelGGL(k_pair_count_msd<false>, g, b, 0, st, B, C, n_xyz, cb_xyz, src_perm, (fd_frame *)frames, counts, (uint64_t *)nullptr);
 }
+// masks: the table this call's count pass stored, or null: the kernel then runs the distance filter itself
 void fd_launch_pair_emit_msd(const fd_batch_view &B, const void *frames, const fd_hash_consts &C, const uint64_t *seg_off, uint32_t *keys,
-                             uint16_t *ids, hipStream_t st) {
+                             uint16_t *ids, const uint64_t *masks, hipStream_t st) {
     if (!B.n_work) return;
     dim3 g(grid_for(B.n_work)), b(FD_WAVE);
     const fd_frame *F = (const fd_frame *)frames;
-    if (C.use_tab == 3) hipLaunchKernelGGL((k_pair_emit2<2, true, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);      // + squared-distance table
-    else if (C.use_tab == 2) hipLaunchKernelGGL((k_pair_emit2<2, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);
-    else if (C.use_tab) hipLaunchKernelGGL((k_pair_emit2<1, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);
-    else hipLaunchKernelGGL((k_pair_emit2<0, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u);
+    const uint64_t *no = nullptr;
+    if (C.use_tab == 3 && masks) hipLaunchKernelGGL((k_pair_emit2<2, true, true, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u, masks);
+    else if (C.use_tab == 3) hipLaunchKernelGGL((k_pair_emit2<2, true, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u, no);      // + squared-distance table
+    else if (C.use_tab == 2) hipLaunchKernelGGL((k_pair_emit2<2, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u, no);
+    else if (C.use_tab) hipLaunchKernelGGL((k_pair_emit2<1, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u, no);
+    else hipLaunchKernelGGL((k_pair_emit2<0, true, true>), g, b, 0, st, B, F, C, seg_off, (uint32_t *)nullptr, keys, (void *)ids, 0u, no);
 }
 void fd_launch_row_count(const fd_batch_view &B, const fd_hash_consts &C, uint32_t *row_cnt, float cutoff, hipStream_t st) {
     if (!B.n_work) return;

@@ -89,6 +89,12 @@ int fdgpu_debug_match_tables(uint64_t n_queries, const fd_match_query *qs, const
 #define FDGPU_PATH_OVERFLOW 64u      /* selection overflow, ranked by the compacting path */
 int fdgpu_debug_last_count_path(fdgpu_ctx *ctx, uint32_t *flags);
 
+/* The LAST fdgpu_index_build call on this context: the bytes of the mask table its emit pass replayed (8 per column: one u64 per work item and
+ * partner, work items padded to blocks of 64 partners; written once by the count pass, read once), or 0 when the emit pass ran the distance filter
+ * itself (FDGPU_PAIR_MASKS=0, a build form or pair kernel without the table, no room on the device).  These bytes are not part of the stages'
+ * byte figures (fdgpu_last_timings). */
+int fdgpu_debug_last_build_mask_bytes(fdgpu_ctx *ctx, uint64_t *bytes);
+
 /* Which way the LAST fdgpu_retrieve / fdgpu_retrieve_batch call on this context went (tests at the dispatch's switches): stage names alone cannot
  * tell a call that the device glue declined from one that never started it.  0 = no such call yet. */
 #define FDGPU_RPATH_DEVICE_TRIED 1u  /* the device glue (k_retrieve.hip) was started */

@@ -76,7 +76,7 @@ int main(int argc, char **argv) {
     long spec_tried = 0, spec_accepted = 0;
     long rev_differ = 0, rev_taken = 0;      // tried pairs on which the oracle's two readings of one dihedral give different keys; those the speculation accepted
     std::vector<uint32_t> off32(off.begin(), off.end());
-    fd_batch_view B = {N.data(), CA.data(), CB.data(), aa.data(), ok.data(), off32.data(), nullptr, nullptr, S, 0};
+    fd_batch_view B = {N.data(), CA.data(), CB.data(), aa.data(), ok.data(), off32.data(), nullptr, nullptr, nullptr, S, 0};
     long pairs = 0, accepted = 0, bad = 0;
     for (uint32_t s = 0; s < S; ++s) {
         const uint32_t r0 = off32[s], r1 = off32[s + 1], n = r1 - r0;
