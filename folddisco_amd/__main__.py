@@ -946,6 +946,29 @@ def cmd_neighbors(a):
               f"({sum(t.nbytes for t in tabs)} bytes)" + (f", {len(jac)} rows confirmed from their rows" + _extractions(a) if jac is not None else ""), file=sys.stderr)
 
 
+def _cluster_seed_ids(a, tids2):
+    """the seeds of `cluster --against`: the ids in PREFIX2 of the tids of --against-reps FILE, ascending, or every structure of PREFIX2
+    without one.  Status 1 and a [FAIL] line for a tid PREFIX2.lookup does not hold or holds in several rows, status 2 for an unreadable file"""
+    if a.against_reps is None:
+        return np.arange(len(tids2), dtype=np.int64)
+    try:
+        with open(a.against_reps) as f:
+            asked = list(dict.fromkeys(line.strip() for line in f if line.strip()))
+    except (OSError, UnicodeDecodeError) as e:
+        print(f"[FAIL] cluster: unreadable input ({e})", file=sys.stderr)
+        sys.exit(2)
+    ids = _ids_of_tids("cluster", asked, a.against_reps, tids2, a.against)
+    if len(ids) != len(asked):
+        rows = {}
+        for t in tids2:
+            rows[t] = rows.get(t, 0) + 1
+        twice = [t for t in asked if rows[t] > 1]
+        print(f"[FAIL] cluster: {len(twice)} tid(s) of {a.against_reps} name more than one row of {a.against}.lookup: " + ", ".join(twice[:10])
+              + (" ..." if len(twice) > 10 else ""))
+        sys.exit(1)
+    return np.sort(ids)
+
+
 def cmd_cluster(a):
     """`cluster`: a non-redundant subset of the index at PREFIX.  The signatures are taken as `dups` takes them and walked in the order of
     --rep-by (hashes: the signature's n, descending; nres, plddt: that column of PREFIX.lookup, descending; id: ascending; ties by id): a
@@ -955,14 +978,33 @@ def cmd_cluster(a):
     `representative`, `identical` or `similar`.  --redundant FILE gets the members' tids, one per line in id order: what `update --remove`
     takes; it is refused when such a tid also names a kept row.  --min-jaccard F (implies --confirm) changes no cluster: it lists in --redundant
     only the members whose exact similarity with their representative reaches F; a member below it is kept, and counts among the kept rows of
-    that refusal.  It removes nothing itself.  No structure file is read."""
+    that refusal.  --representatives FILE gets the representatives' tids, one per line in id order.  It removes nothing itself.  No structure
+    file is read.
+    --against PREFIX2: the structures of PREFIX2 (or, with --against-reps FILE, those whose tids the file lists) are representatives before
+    the walk starts (fdgpu_signature_clusters_seeded): which structures of PREFIX are new?  A structure joins the nearest of the seeds and the
+    representatives chosen from PREFIX; on a full tie a seed wins.  The rows gain a column rep_from after class, `against` (rep_id, rep_tid and
+    rep_n are those of PREFIX2) or `self`, and are sorted by (against before self, rep_id, id); a seed gets no row.  --confirm intersects the
+    members of seeds across the two indices.  --redundant lists the members of either kind, --representatives the new representatives only:
+    appended to the list the seeds came from, it is the next --against-reps."""
     from folddisco_amd import indexio
     if a.rep_by not in indexio.CLUSTER_ORDER_KEYS:
         print(f"[FAIL] cluster: unknown --rep-by key '{a.rep_by}' (one of {', '.join(indexio.CLUSTER_ORDER_KEYS)})")
         sys.exit(1)
+    if a.against is not None and os.path.abspath(a.against) == os.path.abspath(a.index):
+        # status 2, not the 1 of `dups`: before `cluster` had the flag this command line ended with the parser's status 2, and it keeps it
+        print(f"[FAIL] cluster: --against {a.against} is the index itself; leave it out to cluster inside one index", file=sys.stderr)
+        sys.exit(2)
+    if a.against_reps is not None:
+        if a.against is None:
+            sys.exit("[FAIL] cluster: --against-reps lists structures of --against PREFIX2; give that too")
+        if not os.path.isfile(a.against_reps):
+            print(f"[FAIL] {a.against_reps} not found", file=sys.stderr)
+            sys.exit(2)
     _min_jaccard_plan(a, "cluster")
-    prefixes, tids = _sig_plan(a, "cluster")
-    prefix, tids = prefixes[0], tids[0]
+    prefixes, all_tids = _sig_plan(a, "cluster")
+    prefix, tids = prefixes[0], all_tids[0]
+    two = len(prefixes) == 2
+    seed_ids = _cluster_seed_ids(a, all_tids[1]) if two else None
     thr64 = indexio.signature_threshold(a.min_similarity)
     try:
         rows = indexio.read_lookup_rows(prefix + ".lookup") if a.rep_by in ("nres", "plddt") else None
@@ -971,11 +1013,18 @@ def cmd_cluster(a):
             import folddisco_amd as fd
             ctx = fd.Context(a.device)
         S = _dups_signatures(a, ctx, prefix, len(tids))
+        S2 = _dups_signatures(a, ctx, prefixes[1], len(all_tids[1])) if two else None
+        seeds = np.ascontiguousarray(S2[seed_ids]) if two else None
         order = indexio.cluster_order(S, rows, a.rep_by)
-        cl = indexio.signature_clusters_host(S, order, thr64=thr64, threads=a.threads) if a.host else ctx.signature_clusters(S, order, thr64=thr64)
+        cl = indexio.signature_clusters_host(S, order, thr64=thr64, threads=a.threads, seeds=seeds) if a.host else \
+            ctx.signature_clusters(S, order, thr64=thr64, seeds=seeds)
         ids = np.arange(len(S), dtype=np.int64)
-        rep = cl["id"] == ids
+        of_seed = (cl["flags"] & indexio.SIG_SEED) != 0                       # the record's id is a position among the seeds
+        rep = ~of_seed & (cl["id"] == ids)
         member = ~rep & (cl["id"] != indexio.SIG_NO_ID)
+        rep_id = cl["id"].astype(np.int64)                                    # in PREFIX2 for a member of a seed, in PREFIX otherwise
+        if two:
+            rep_id[of_seed] = seed_ids[rep_id[of_seed]]
         def refuse_clash(listed_rows):               # `update --remove` removes every row with a listed tid: none of them may name a kept row
             listed = {tids[p] for p in ids[listed_rows]}
             clash = sorted({tids[p] for p in ids[~listed_rows] if tids[p] in listed})
@@ -987,11 +1036,19 @@ def cmd_cluster(a):
         if a.redundant and a.min_jaccard is None:
             refuse_clash(removable)
         shown = ids[rep | member]
-        shown = shown[np.lexsort((shown, cl["id"][shown]))]
+        shown = shown[np.lexsort((shown, rep_id[shown], ~of_seed[shown]))]
         jac = None
         if a.confirm:
             mem = shown[member[shown]]
-            exact = _dups_overlaps(a, ctx, prefixes, [tids], cl["id"][mem], mem)
+            if two:                                  # members of seeds across the two indices, members of new representatives inside PREFIX
+                ms, mn = mem[of_seed[mem]], mem[~of_seed[mem]]
+                across = _dups_overlaps(a, ctx, prefixes, all_tids, ms, rep_id[ms])
+                st = dict(a.overlap_stats)
+                inside = _dups_overlaps(a, ctx, prefixes[:1], [tids], rep_id[mn], mn)
+                a.overlap_stats = {k: st[k] + v for k, v in a.overlap_stats.items()}
+                exact = tuple(np.concatenate(x) for x in zip(across, inside))      # in the order of mem: the seeds' members come first
+            else:
+                exact = _dups_overlaps(a, ctx, prefixes, [tids], cl["id"][mem], mem)
             jac = _jaccard_values(exact)
             if a.min_jaccard is not None:            # a member below the exact floor is kept: keeping a redundant structure is harmless, deleting a distinct one is not
                 below = ~indexio.jaccard_reaches(exact[0], exact[1] + exact[2] - exact[0], a.min_jaccard)
@@ -1005,10 +1062,13 @@ def cmd_cluster(a):
         sys.exit(2 if isinstance(e, OSError) else 1)
     lines, j = [], 0
     for p in shown:
-        r, rec = int(cl["id"][p]), cl[p]
-        cols = [str(r), tids[r], str(int(S["n"][r])), str(int(p)), tids[p], str(int(S["n"][p])), str(int(rec["match"])), str(int(rec["filled"])),
+        r, rec = int(rep_id[p]), cl[p]
+        rt, rs = (all_tids[1], S2) if of_seed[p] else (tids, S)
+        cols = [str(r), rt[r], str(int(rs["n"][r])), str(int(p)), tids[p], str(int(S["n"][p])), str(int(rec["match"])), str(int(rec["filled"])),
                 f"{int(rec['match']) / max(int(rec['filled']), 1):.4f}",
                 "representative" if rep[p] else "identical" if int(rec["flags"]) & indexio.SIG_IDENTICAL else "similar"]
+        if two:
+            cols.append("against" if of_seed[p] else "self")
         if jac is not None:
             cols.append("1.0000" if rep[p] else f"{jac[j]:.4f}")
             j += 0 if rep[p] else 1
@@ -1016,13 +1076,23 @@ def cmd_cluster(a):
     _write_tsv(a.output, lines, "cluster")
     if a.redundant:
         _write_tsv(a.redundant, [tids[p] + "\n" for p in ids[removable]], "cluster")
-    sizes = np.bincount(cl["id"][shown].astype(np.int64), minlength=max(len(S), 1))
+    if a.representatives:
+        _write_tsv(a.representatives, [tids[p] + "\n" for p in ids[rep]], "cluster")
+    own = shown[~of_seed[shown]]                                              # the rows of the clusters PREFIX itself started
+    sizes = np.bincount(rep_id[own], minlength=max(len(S), 1))
     n_ident = int((member & ((cl["flags"] & indexio.SIG_IDENTICAL) != 0)).sum())
-    print(f"[OK] {prefix}: {len(S)} structures, {int(rep.sum())} clusters ({int((sizes[ids[rep]] == 1).sum())} singletons), {int(member.sum())} members "
-          f"({n_ident} identical), {int((cl['id'] == indexio.SIG_NO_ID).sum())} unclustered, largest cluster {int(sizes.max())}, threshold {thr64}/64"
-          + (f", {n_below} members below the exact floor kept" if a.min_jaccard is not None else ""))
+    n_none = int((cl["id"] == indexio.SIG_NO_ID).sum())
+    floor = f", {n_below} members below the exact floor kept" if a.min_jaccard is not None else ""
+    if two:
+        print(f"[OK] {prefix} x {prefixes[1]}: {len(S)} x {len(S2)} structures, {len(seed_ids)} seeds, {int(rep.sum())} new clusters "
+              f"({int((sizes[ids[rep]] == 1).sum())} singletons), {int((member & of_seed).sum())} members of seeds, {int((member & ~of_seed).sum())} members of new "
+              f"representatives ({n_ident} identical), {n_none} unclustered, threshold {thr64}/64" + floor)
+    else:
+        print(f"[OK] {prefix}: {len(S)} structures, {int(rep.sum())} clusters ({int((sizes[ids[rep]] == 1).sum())} singletons), {int(member.sum())} members "
+              f"({n_ident} identical), {n_none} unclustered, largest cluster {int(sizes.max())}, threshold {thr64}/64" + floor)
     if a.verbose:
         print(f"[INFO] cluster on the {'host' if a.host else 'device'}: signatures of {len(S)} structures ({S.nbytes} bytes), walked by {a.rep_by}"
+              + (f", {len(seed_ids)} seeds of {prefixes[1]} ({int((seeds['n'] == 0).sum())} of them with empty rows)" if two else "")
               + (f", {len(jac)} members confirmed from their rows" + _extractions(a) if jac is not None else ""), file=sys.stderr)
 
 
@@ -1684,6 +1754,9 @@ def main(argv=None):
     pn.add_argument("-v", "--verbose", action="store_true")
     pk = sub.add_parser("cluster")                                   # one representative per group of similar structures, by signature (no counterpart in the reference)
     pk.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
+    pk.add_argument("--against", default=None, help="a second index prefix whose structures are representatives from the start: which structures of PREFIX are new?")
+    pk.add_argument("--against-reps", default=None, help="text file with one tid per line (column 2 of PREFIX2.lookup): only these structures of --against are seeds")
+    pk.add_argument("--representatives", default="", help="also write the (new) representatives' tids, one per line: appended to the seeds' list, the next --against-reps")
     pk.add_argument("--min-similarity", type=float, default=0.9, help="a structure joins a representative whose sketch agrees with its own in at least this share of their filled buckets, in (0, 1]")
     pk.add_argument("--rep-by", default="hashes", help="the walk order, earlier structures represent: hashes (the row's size, descending; default), nres or plddt "
                     "(that column of PREFIX.lookup, descending), id (ascending); ties by id")
@@ -1698,7 +1771,6 @@ def main(argv=None):
     pk.add_argument("--device", type=int, default=0)
     pk.add_argument("--verify", action="store_true", help="check the loaded index first (see `verify`) and stop with status 1 if it is damaged")
     pk.add_argument("-v", "--verbose", action="store_true")
-    pk.set_defaults(against=None)                                    # what the shared planning of `dups` and `neighbors` looks at
     pr = sub.add_parser("reshard")                                   # one index <-> shards by structure id range (no counterpart in the reference)
     pr.add_argument("-i", "--index", required=True)
     pr.add_argument("--to", type=int, required=True, help="shards to write (PREFIX.shard<r>ofW); 1 writes the single index")

@@ -217,6 +217,8 @@ SYMBOLS = [
     ("fdgpu_signature_neighbors_host", C.c_int, [VP, C.c_uint64, VP, C.c_uint64, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_signature_clusters", C.c_int, [VP, VP, C.c_uint64, VP, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_signature_clusters_host", C.c_int, [VP, C.c_uint64, VP, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
+    ("fdgpu_signature_clusters_seeded", C.c_int, [VP, VP, C.c_uint64, VP, VP, C.c_uint64, C.c_uint32, C.POINTER(VP)]),
+    ("fdgpu_signature_clusters_seeded_host", C.c_int, [VP, C.c_uint64, VP, VP, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_index_rowset", C.c_int, [VP, VP, u32p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(VP), u64p]),
     ("fdgpu_rowset_info", C.c_int, [VP, u64p, u64p]),
     ("fdgpu_rowset_lengths", C.c_int, [VP, C.POINTER(u32p)]),

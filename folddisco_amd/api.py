@@ -152,12 +152,19 @@ class Context:
                                                     None if exclude is None else exclude.ctypes.data, k, t, C.byref(op)))
         return indexio.signature_neighbors_result(self.L, op, len(Q), k)
 
-    def signature_clusters(self, S, order=None, min_similarity: float = 0.9, thr64=None) -> np.ndarray:
+    def signature_clusters(self, S, order=None, min_similarity: float = 0.9, thr64=None, seeds=None) -> np.ndarray:
         """the greedy clusters of a signature table, selected on the device (fdgpu_signature_clusters): one indexio.SIGNATURE_NEIGHBOR_DTYPE
-        record per position; the contract of indexio.signature_clusters_host, which it equals byte for byte"""
+        record per position; the contract of indexio.signature_clusters_host, which it equals byte for byte.  seeds: a signature table whose
+        non-empty records are representatives from the start (fdgpu_signature_clusters_seeded); a record with indexio.SIG_SEED in its flags
+        names a position of it"""
         from . import indexio
         S, order, t = indexio._sig_cluster_args(S, order, min_similarity, thr64)
         op = C.c_void_p()
+        if seeds is not None:
+            T = indexio._sig_table(seeds, "seeds")
+            self.check(self.L.fdgpu_signature_clusters_seeded(self.h, S.ctypes.data, len(S), None if order is None else order.ctypes.data,
+                                                              T.ctypes.data if len(T) else None, len(T), t, C.byref(op)))
+            return indexio.signature_clusters_result(self.L, op, len(S))
         self.check(self.L.fdgpu_signature_clusters(self.h, S.ctypes.data, len(S), None if order is None else order.ctypes.data, t, C.byref(op)))
         return indexio.signature_clusters_result(self.L, op, len(S))
 

@@ -190,11 +190,14 @@ uint64_t fd_sig_order_fault(const uint32_t *order, uint64_t n) {
     return n;
 }
 
-extern "C" int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, uint32_t n_threads,
-                                             fd_sig_neighbor **out) {
+// both host forms of the clusters.  During the walk res[p].id is a combined id (seed j: j, position r of S: nT + r), which is the order
+// the definition asks for; the ids are turned back at the end.  nT == 0: the unseeded walk, where the two coincide
+static int clusters_host(const fd_signature *S, uint64_t n, const uint32_t *order, const fd_signature *T, uint64_t nT, uint32_t thr64, uint32_t n_threads,
+                         fd_sig_neighbor **out) {
     if (!out) return FDGPU_EINVAL;
     *out = nullptr;
     if (thr64 < 1 || thr64 > 64 || n > 0xffffffffull || (n && !S)) return FDGPU_EINVAL;
+    if ((nT && !T) || nT > 0xffffffffull || nT + n > 0xffffffffull) return FDGPU_EINVAL;
     if (order) {
         const uint64_t w = fd_sig_order_fault(order, n);
         if (w != n) return w == FD_SIG_ORDER_NOMEM ? FDGPU_ENOMEM : FDGPU_EINVAL;
@@ -203,27 +206,39 @@ extern "C" int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, 
     if (!res) return FDGPU_ENOMEM;
     const fd_sig_neighbor none = {FD_SIG_NO_ID, 0, 0, 0};
     for (uint64_t i = 0; i < std::max<uint64_t>(n, 1); ++i) res[i] = none;
-    auto take = [&](uint64_t p, uint64_t r) {           // r, a representative, for p if the pair is reported and r is nearer than p's best
-        const sg_stat s = sig_compare(S[p], S[r]);
-        if (!fd_sig_reported(S[p].n, S[r].n, s.eq, s.E, thr64)) return;
+    auto take = [&](uint64_t p, const fd_signature &r, uint64_t id) {     // r, a representative with that combined id, for p if the pair is reported and r is nearer than p's best
+        const sg_stat s = sig_compare(S[p], r);
+        if (!fd_sig_reported(S[p].n, r.n, s.eq, s.E, thr64)) return;
         const uint32_t m = s.eq - s.E, f = 64u - s.E;
         fd_sig_neighbor &b = res[p];
-        if (!fd_sig_nearer(m, f, (uint32_t)r, b.match, b.filled, b.id)) return;
-        b.id = (uint32_t)r; b.match = (uint8_t)m; b.filled = (uint8_t)f;
-        b.flags = S[p].n == S[r].n && S[p].d0 == S[r].d0 && S[p].d1 == S[r].d1 ? FD_SIG_IDENTICAL : 0u;
+        if (!fd_sig_nearer(m, f, (uint32_t)id, b.match, b.filled, b.id)) return;
+        b.id = (uint32_t)id; b.match = (uint8_t)m; b.filled = (uint8_t)f;
+        b.flags = S[p].n == r.n && S[p].d0 == r.d0 && S[p].d1 == r.d1 ? FD_SIG_IDENTICAL : 0u;
     };
+    if (nT) {                                           // every position's nearest seed: the seeds do not change during the walk
+        const uint64_t BLK = 64, n_blk = (n + BLK - 1) / BLK;
+        const uint64_t TH = fd_host_threads(n_threads, n_blk, 1);
+        fd_over_ranges(TH, [&](uint64_t t) {
+            for (uint64_t bp = n_blk * t / TH; bp < n_blk * (t + 1) / TH; ++bp)
+                for (uint64_t j0 = 0; j0 < nT; j0 += BLK)
+                    for (uint64_t p = bp * BLK; p < std::min(n, bp * BLK + BLK); ++p) {
+                        if (!S[p].n) continue;
+                        for (uint64_t j = j0; j < std::min(nT, j0 + BLK); ++j) take(p, T[j], j);
+                    }
+        });
+    }
     std::vector<uint32_t> reps;
     const uint64_t BLK = 1024;
     try {
         for (uint64_t w0 = 0; w0 < n; w0 += BLK) {
             const uint64_t nb = std::min(BLK, n - w0), R = reps.size();
             auto at = [&](uint64_t i) { return order ? (uint64_t)order[w0 + i] : w0 + i; };
-            const uint64_t T = fd_host_threads(n_threads, nb * R, 1u << 16);      // a thread is worth starting for 65,536 compares
-            fd_over_ranges(T, [&](uint64_t t) {
-                for (uint64_t i = nb * t / T; i < nb * (t + 1) / T; ++i) {
+            const uint64_t TH = fd_host_threads(n_threads, nb * R, 1u << 16);     // a thread is worth starting for 65,536 compares
+            fd_over_ranges(TH, [&](uint64_t t) {
+                for (uint64_t i = nb * t / TH; i < nb * (t + 1) / TH; ++i) {
                     const uint64_t p = at(i);
                     if (!S[p].n) continue;
-                    for (uint64_t k = 0; k < R; ++k) take(p, reps[k]);
+                    for (uint64_t k = 0; k < R; ++k) take(p, S[reps[k]], nT + reps[k]);
                 }
             });
             for (uint64_t i = 0; i < nb; ++i) {
@@ -231,12 +246,27 @@ extern "C" int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, 
                 if (!S[p].n || res[p].id != FD_SIG_NO_ID) continue;
                 uint32_t filled = 0;
                 for (unsigned k = 0; k < 64; ++k) filled += S[p].sk[k] != FD_SIG_EMPTY ? 1u : 0u;
-                res[p].id = (uint32_t)p; res[p].match = res[p].filled = (uint8_t)filled; res[p].flags = FD_SIG_IDENTICAL;
+                res[p].id = (uint32_t)(nT + p); res[p].match = res[p].filled = (uint8_t)filled; res[p].flags = FD_SIG_IDENTICAL;
                 reps.push_back((uint32_t)p);
-                for (uint64_t j = i + 1; j < nb; ++j) if (S[at(j)].n) take(at(j), p);
+                for (uint64_t j = i + 1; j < nb; ++j) if (S[at(j)].n) take(at(j), S[p], nT + p);
             }
         }
     } catch (...) { free(res); return FDGPU_ENOMEM; }
+    for (uint64_t p = 0; nT && p < n; ++p) {
+        fd_sig_neighbor &b = res[p];
+        if (b.id == FD_SIG_NO_ID) continue;
+        if (b.id < nT) b.flags |= FD_SIG_SEED; else b.id -= (uint32_t)nT;
+    }
     *out = res;
     return FDGPU_OK;
+}
+
+extern "C" int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, uint32_t n_threads,
+                                             fd_sig_neighbor **out) {
+    return clusters_host(S, n, order, nullptr, 0, thr64, n_threads, out);
+}
+
+extern "C" int fdgpu_signature_clusters_seeded_host(const fd_signature *S, uint64_t n, const uint32_t *order, const fd_signature *T, uint64_t nT,
+                                                    uint32_t thr64, uint32_t n_threads, fd_sig_neighbor **out) {
+    return clusters_host(S, n, order, T, nT, thr64, n_threads, out);
 }

@@ -50,6 +50,8 @@ enum {
     WS_SG_NB_PART /* signature neighbours: the k-lists of every split, [split][query][k] */, WS_SG_NB_OUT /* the merged lists, [query][k] */,
     WS_SG_CL_TAB /* signature clusters: the table in walk order */, WS_SG_CL_REPS /* the representatives so far, compact, appended to */,
     WS_SG_CL_OUT /* the records in walk order */, WS_SG_CL_PART /* a block's partial bests, [split][lane] */, WS_SG_CL_COUNT /* the number of representatives */,
+    WS_SG_CL_SEEDS /* seeded clusters: the seed table */, WS_SG_CL_SEED_BEST /* every position's nearest seed, in walk order */,
+    WS_SG_CL_SEED_PART /* the seed pass's partial bests, [split][position] */,
     WS_COUNT
 };
 

@@ -458,9 +458,14 @@ extern "C" int fdgpu_signature_neighbors(fdgpu_ctx *c, const fd_signature *Q, ui
 //                    its slot of R; the lane copies its record there, writes its result record, and thread 0 moves *n_reps.
 // Nothing waits for another workgroup: no flag, no spin, no cooperative launch.  The order fd_sig_nearer is total, so neither the number of
 // splits nor the width of the block changes a byte.  Records leave in walk order; the host puts them at their positions.
+// With a seed table (fdgpu_signature_clusters_seeded) two launches precede the first block, once per call:
+//   k_sg_cl_seed     grid (blocks, splits): every position of W against the seeds, its ONE nearest seed to part[blockIdx.y][position]
+//   k_sg_cl_seed_merge  only when split: the partial bests of a position -> seed_best[position]
+// and k_sg_cl_resolve starts each lane's best from seed_best.  The seeds never enter R: the walk scans what S itself adds.
 #define SG_CL_MAX_SPLIT 256u     // splits of a scan: one workgroup per CU; bounds WS_SG_CL_PART at 256 * 256 * 8 bytes
 
-struct sg_cl_args { const uint32_t *W; uint32_t *R; uint32_t *n_reps; uint2 *part; uint2 *out; uint32_t w0, nb, thr64, splits; };
+struct sg_cl_args { const uint32_t *W; uint32_t *R; uint32_t *n_reps; uint2 *part; uint2 *out; uint32_t w0, nb, thr64, splits;
+                    const uint2 *seed_best; };       // the seeded call: every position's nearest seed (k_sg_cl_seed), NULL without a seed table
 
 // the lane's signature W[w0 + t] into registers (a lane beyond the block: n = 0, which is never a candidate and never a representative)
 #define SG_CL_LOAD_LANE(P)                                                                                                       \
@@ -480,15 +485,16 @@ struct sg_cl_args { const uint32_t *W; uint32_t *R; uint32_t *n_reps; uint2 *par
         }                                                                                                                        \
     }
 
-// entry i of the staged tile against the lane's signature: the lane's best (id, match | filled << 8 | identical << 16) takes it if the pair
-// is reported and the entry, whose position is its reserved word, is nearer
-#define SG_CL_TAKE(i)                                                                                                            \
+// entry i of the staged tile, whose id is `id`, against the lane's signature: the lane's best (id, match | filled << 8 | identical << 16)
+// takes it if the pair is reported and the entry is nearer.  SG_CL_TAKE: an entry of W or R, its id is its reserved word
+#define SG_CL_TAKE(i) SG_CL_TAKE_ID(i, a_head[i][1])
+#define SG_CL_TAKE_ID(i, id)                                                                                                     \
     {                                                                                                                            \
         uint32_t eq = 0;                                                                                                         \
         _Pragma("unroll")                                                                                                        \
         for (uint32_t k = 0; k < 64; ++k) eq += a_sk[i][k] == b[k] ? 1u : 0u;                                                    \
         const uint32_t E = (uint32_t)__popcll(a_empty[i] & b_empty);                                                             \
-        const uint32_t a = a_head[i][1], m = eq - E, f = 64u - E;                                                                \
+        const uint32_t a = (id), m = eq - E, f = 64u - E;                                                                        \
         if (fd_sig_reported(bn, a_head[i][0], eq, E, thr64) && sg_nearer_packed(m, f, a, best_mf, best_id)) {                    \
             const bool same = a_head[i][0] == bn && a_head[i][2] == bd0l && a_head[i][3] == bd0h && a_head[i][4] == bd1l && a_head[i][5] == bd1h; \
             best_id = a; best_mf = m | f << 8 | (same ? FD_SIG_IDENTICAL : 0u) << 16;                                            \
@@ -511,8 +517,46 @@ __global__ __launch_bounds__(256) void k_sg_cl_scan(sg_cl_args P) {
     P.part[blockIdx.y * SG_BLOCK_B + t] = make_uint2(best_id, best_mf);
 }
 
+// ---- the seed pass of fdgpu_signature_clusters_seeded: the seeds T[0 .. nT) never change during the walk, so every position's nearest seed is
+// found once, in one launch over all blocks of the walk.  Grid (blocks of 256 positions of W, splits): a workgroup runs its 256 signatures (one
+// per lane, in registers) against the tiles ta = blockIdx.y, + gridDim.y, ... of T; a seed's id is its position in T.  Every workgroup has a
+// tile (the host gives no more splits than tiles).  Reads W[0 .. n), T[0 .. nT); writes part[blockIdx.y * n + w] for its positions w < n:
+// seed_best itself when there is one split.
+struct sg_seed_args { const uint32_t *W; const uint32_t *T; uint32_t n, nT, thr64; uint2 *part; };
+
+__global__ __launch_bounds__(256) void k_sg_cl_seed(sg_seed_args P) {
+    __shared__ uint32_t a_sk[SG_TILE_A][64];
+    __shared__ uint32_t a_head[SG_TILE_A][6];
+    __shared__ unsigned long long a_empty[SG_TILE_A];
+    const struct { const uint32_t *W; uint32_t w0, nb; } L{P.W, blockIdx.x * SG_BLOCK_B, std::min<uint32_t>(SG_BLOCK_B, P.n - blockIdx.x * SG_BLOCK_B)};
+    const uint32_t thr64 = P.thr64, tiles = (uint32_t)(((uint64_t)P.nT + SG_TILE_A - 1) / SG_TILE_A);
+    SG_CL_LOAD_LANE(L)
+    uint32_t best_id = FD_SIG_NO_ID, best_mf = 0u;
+    for (uint32_t ta = blockIdx.y; ta < tiles; ta += gridDim.y) {
+        const uint64_t a0 = (uint64_t)ta * SG_TILE_A;
+        sg_stage_tile(P.T, P.nT, a0, a_sk, a_head, a_empty);
+        for (uint32_t i = 0; i < SG_TILE_A; ++i) SG_CL_TAKE_ID(i, (uint32_t)a0 + i)
+    }
+    if (have) P.part[(uint64_t)blockIdx.y * P.n + L.w0 + t] = make_uint2(best_id, best_mf);
+}
+
+// A thread per position w < n: the nearest of part[y * n + w], y < splits, under fd_sig_nearer (the splits saw different seeds: the order is
+// strict among candidates) -> seed_best[w].  The reads of a wavefront are consecutive for every y.
+__global__ __launch_bounds__(256) void k_sg_cl_seed_merge(const uint2 *__restrict__ part, uint32_t splits, uint32_t n, uint2 *__restrict__ seed_best) {
+    const uint64_t w = (uint64_t)blockIdx.x * SG_BLOCK_B + threadIdx.x;
+    if (w >= n) return;
+    uint32_t best_id = FD_SIG_NO_ID, best_mf = 0u;
+#pragma unroll 4
+    for (uint32_t y = 0; y < splits; ++y) {
+        const uint2 c = part[(uint64_t)y * n + w];
+        if (sg_nearer_packed(c.y & 0xffu, (c.y >> 8) & 0xffu, c.x, best_mf, best_id)) { best_id = c.x; best_mf = c.y; }
+    }
+    seed_best[w] = make_uint2(best_id, best_mf);
+}
+
 // One workgroup.  Reads part[y * 256 + t] for y < min(splits, tiles of *n_reps), W[w0 .. w0 + nb); writes out[w0 + t] for t < nb,
-// R[*n_reps .. *n_reps + new representatives) (at most nb more: the host sized R for every position) and *n_reps
+// R[*n_reps .. *n_reps + new representatives) (at most nb more: the host sized R for every position) and *n_reps.  With a seed table it
+// also reads seed_best[w0 + t] for t < nb: the lane's best starts from its nearest seed, and the walk may still find a nearer representative
 __global__ __launch_bounds__(256) void k_sg_cl_resolve(sg_cl_args P) {
     __shared__ uint32_t a_sk[SG_TILE_A][64];
     __shared__ uint32_t a_head[SG_TILE_A][6];
@@ -523,6 +567,7 @@ __global__ __launch_bounds__(256) void k_sg_cl_resolve(sg_cl_args P) {
     const uint32_t nR = *P.n_reps, valid = std::min<uint32_t>(P.splits, (nR + SG_TILE_A - 1) / SG_TILE_A);
     SG_CL_LOAD_LANE(P)
     uint32_t best_id = FD_SIG_NO_ID, best_mf = 0u;
+    if (P.seed_best && have) { const uint2 c = P.seed_best[P.w0 + t]; best_id = c.x; best_mf = c.y; }
     for (uint32_t y = 0; y < valid; ++y) {
         const uint2 c = P.part[y * SG_BLOCK_B + t];
         if (sg_nearer_packed(c.y & 0xffu, (c.y >> 8) & 0xffu, c.x, best_mf, best_id)) { best_id = c.x; best_mf = c.y; }
@@ -567,7 +612,12 @@ __global__ __launch_bounds__(256) void k_sg_cl_resolve(sg_cl_args P) {
     if (threadIdx.x == 0) *P.n_reps = nR + total;
 }
 
-static int clusters_impl(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, fd_sig_neighbor **out) {
+#define SG_CL_SEED_MAX_SPLIT 256u        // splits of the seed pass; bounds WS_SG_CL_SEED_PART at 256 * n * 8 bytes (by default: 8 MiB + 8 * n, see the header)
+
+// the ids of a seeded call on the device are the combined ones: seed j is j, position p of S is nT + p (every record of W and so of R carries
+// it in its reserved word).  The host turns them back.  T == NULL: the unseeded call, nT = 0
+static int clusters_impl(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, const fd_signature *T, uint64_t nT, uint32_t thr64,
+                         fd_sig_neighbor **out) {
     reset_timings(c);
     hipStream_t st = c->stream;
     fd_sig_neighbor *res = (fd_sig_neighbor *)fd_out_alloc(std::max<uint64_t>(n, 1) * sizeof(fd_sig_neighbor));
@@ -582,10 +632,15 @@ static int clusters_impl(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const 
     for (uint64_t w = 0; w < n; ++w) {
         const uint64_t p = order ? order[w] : w;
         W[w] = S[p];
-        W[w].reserved = (uint32_t)p;
+        W[w].reserved = (uint32_t)(nT + p);
     }
-    long long forced = 0;
+    long long forced = 0, forced_seed = 0;
     if (const char *e = getenv("FDGPU_SG_CL_SPLIT")) forced = atoll(e);
+    if (const char *e = getenv("FDGPU_SG_CL_SEED_SPLIT")) forced_seed = atoll(e);
+    // the seed pass: as neighbors_impl, enough workgroups to fill the device, no more splits than tiles; one when the blocks alone fill it
+    const uint32_t blocks = fd_grid(n, SG_BLOCK_B), seed_most = std::min<uint32_t>(fd_grid(nT, SG_TILE_A), SG_CL_SEED_MAX_SPLIT);
+    uint32_t seed_splits = nT ? std::max<uint32_t>(1u, std::min<uint32_t>(seed_most, fd_grid(4096, blocks))) : 0u;
+    if (nT && forced_seed > 0) seed_splits = (uint32_t)std::min<long long>(forced_seed, seed_most);
     hipError_t e = hipSuccess;
     do {
         if ((e = c->ws[WS_SG_CL_TAB].ensure(n * sizeof(fd_signature))) != hipSuccess) break;
@@ -593,12 +648,36 @@ static int clusters_impl(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const 
         if ((e = c->ws[WS_SG_CL_OUT].ensure(n * sizeof(fd_sig_neighbor))) != hipSuccess) break;
         if ((e = c->ws[WS_SG_CL_PART].ensure((uint64_t)SG_CL_MAX_SPLIT * SG_BLOCK_B * sizeof(uint2))) != hipSuccess) break;
         if ((e = c->ws[WS_SG_CL_COUNT].ensure(64)) != hipSuccess) break;
+        if (nT) {
+            if ((e = c->ws[WS_SG_CL_SEEDS].ensure(nT * sizeof(fd_signature))) != hipSuccess) break;
+            if ((e = c->ws[WS_SG_CL_SEED_BEST].ensure(n * sizeof(uint2))) != hipSuccess) break;
+            if (seed_splits > 1 && (e = c->ws[WS_SG_CL_SEED_PART].ensure((uint64_t)seed_splits * n * sizeof(uint2))) != hipSuccess) break;
+        }
         sg_cl_args P{c->ws[WS_SG_CL_TAB].as<uint32_t>(), c->ws[WS_SG_CL_REPS].as<uint32_t>(), c->ws[WS_SG_CL_COUNT].as<uint32_t>(),
-                     c->ws[WS_SG_CL_PART].as<uint2>(), c->ws[WS_SG_CL_OUT].as<uint2>(), 0u, 0u, thr64, 0u};
+                     c->ws[WS_SG_CL_PART].as<uint2>(), c->ws[WS_SG_CL_OUT].as<uint2>(), 0u, 0u, thr64, 0u, nT ? c->ws[WS_SG_CL_SEED_BEST].as<uint2>() : nullptr};
         {
             StageTimer t(c, "sigcl_upload", n * sizeof(fd_signature));
             if ((e = hipMemcpyAsync((void *)P.W, W, n * sizeof(fd_signature), hipMemcpyHostToDevice, st)) != hipSuccess) break;
             if ((e = hipMemsetAsync(P.n_reps, 0, 4, st)) != hipSuccess) break;
+        }
+        if (nT) {                                       // once per call, whatever n is: every block of the walk starts from seed_best
+            uint32_t *dT = c->ws[WS_SG_CL_SEEDS].as<uint32_t>();
+            uint2 *best = c->ws[WS_SG_CL_SEED_BEST].as<uint2>(), *part = seed_splits > 1 ? c->ws[WS_SG_CL_SEED_PART].as<uint2>() : best;
+            {
+                StageTimer t(c, "sigcl_seed_upload", nT * sizeof(fd_signature));
+                if ((e = hipMemcpyAsync(dT, T, nT * sizeof(fd_signature), hipMemcpyHostToDevice, st)) != hipSuccess) break;
+            }
+            {
+                StageTimer t(c, "sigcl_seed", ((uint64_t)blocks * nT + (uint64_t)seed_splits * n) * sizeof(fd_signature));
+                const sg_seed_args Q{P.W, dT, (uint32_t)n, (uint32_t)nT, thr64, part};
+                hipLaunchKernelGGL(k_sg_cl_seed, dim3(blocks, seed_splits), dim3(256), 0, st, Q);
+            }
+            if ((e = hipGetLastError()) != hipSuccess) break;
+            if (seed_splits > 1) {
+                StageTimer t(c, "sigcl_seed_merge", ((uint64_t)seed_splits + 1) * n * sizeof(uint2));
+                hipLaunchKernelGGL(k_sg_cl_seed_merge, dim3(blocks), dim3(256), 0, st, part, seed_splits, (uint32_t)n, best);
+                if ((e = hipGetLastError()) != hipSuccess) break;
+            }
         }
         for (uint64_t w0 = 0; w0 < n && e == hipSuccess; w0 += SG_BLOCK_B) {
             P.w0 = (uint32_t)w0; P.nb = (uint32_t)std::min<uint64_t>(SG_BLOCK_B, n - w0);
@@ -627,22 +706,42 @@ static int clusters_impl(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const 
         c->err = std::string("signature clusters: ") + hipGetErrorString(e);
         return FDGPU_EHIP;
     }
-    for (uint64_t w = 0; w < n; ++w) res[order ? order[w] : w] = walk[w];
+    for (uint64_t w = 0; w < n; ++w) {
+        fd_sig_neighbor r = walk[w];
+        if (nT && r.id != FD_SIG_NO_ID) { if (r.id < nT) r.flags |= FD_SIG_SEED; else r.id -= (uint32_t)nT; }
+        res[order ? order[w] : w] = r;
+    }
     free(W); free(walk);
     *out = res;
     return FDGPU_OK;
 }
 
-extern "C" int fdgpu_signature_clusters(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, fd_sig_neighbor **out) { FD_LOCK(c);
-    if (!c || !out) return FDGPU_EINVAL;
-    *out = nullptr;
+// what both entry points refuse before any device work, then the call
+static int clusters_checked(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, const fd_signature *T, uint64_t nT, uint32_t thr64,
+                            fd_sig_neighbor **out) {
     if (thr64 < 1 || thr64 > 64) FAIL(c, FDGPU_EINVAL, "signature clusters: thr64 must be 1 .. 64");
     if (n > 0xffffffffull) FAIL(c, FDGPU_EINVAL, "signature clusters: a table of 2^32 or more signatures");
     if (n && !S) FAIL(c, FDGPU_EINVAL, "signature clusters: the table is NULL");
+    if (nT && !T) FAIL(c, FDGPU_EINVAL, "signature clusters: the seed table is NULL");
+    if (nT > 0xffffffffull || nT + n > 0xffffffffull)   // the combined ids must leave 0xFFFFFFFF free
+        FAIL(c, FDGPU_EINVAL, "signature clusters: the seeds and the table together hold more than 2^32 - 1 signatures");
     if (order) {
         const uint64_t w = fd_sig_order_fault(order, n);
         if (w == FD_SIG_ORDER_NOMEM) FAIL(c, FDGPU_ENOMEM, "signature clusters: out of host memory");
         if (w != n) FAIL(c, FDGPU_EINVAL, "signature clusters: order is not a permutation of 0 .. n - 1 (entry " + std::to_string(w) + " = " + std::to_string(order[w]) + ")");
     }
-    return clusters_impl(c, S, n, order, thr64, out);
+    return clusters_impl(c, S, n, order, nT ? T : nullptr, nT, thr64, out);
+}
+
+extern "C" int fdgpu_signature_clusters(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, fd_sig_neighbor **out) { FD_LOCK(c);
+    if (!c || !out) return FDGPU_EINVAL;
+    *out = nullptr;
+    return clusters_checked(c, S, n, order, nullptr, 0, thr64, out);
+}
+
+extern "C" int fdgpu_signature_clusters_seeded(fdgpu_ctx *c, const fd_signature *S, uint64_t n, const uint32_t *order, const fd_signature *T, uint64_t nT,
+                                               uint32_t thr64, fd_sig_neighbor **out) { FD_LOCK(c);
+    if (!c || !out) return FDGPU_EINVAL;
+    *out = nullptr;
+    return clusters_checked(c, S, n, order, T, nT, thr64, out);
 }

@@ -633,6 +633,7 @@ SIGNATURE_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("match", "u1"), ("
 SIGNATURE_PAIRS_DTYPE = np.dtype(SIGNATURE_PAIR_DTYPE.descr + [("estimate", "<f8")])      # what the pair calls return: the record + match / filled
 SIG_EMPTY = 0xffffffff
 SIG_IDENTICAL = 1
+SIG_SEED = 2                                         # flags bit 1 of a cluster record: id is a position in the seed table
 assert SIGNATURE_DTYPE.itemsize == 280 and SIGNATURE_PAIR_DTYPE.itemsize == 12
 
 
@@ -838,13 +839,17 @@ def _sig_cluster_args(S, order, min_similarity, thr64):
     return S, order, t
 
 
-def signature_clusters_from_tables(S, order=None, thr64: int = 58) -> np.ndarray:
+def signature_clusters_from_tables(S, order=None, thr64: int = 58, seeds=None) -> np.ndarray:
     """THE SPECIFICATION of the signature clusters, in plain numpy: -> len(S) SIGNATURE_NEIGHBOR_DTYPE records.  The positions are visited in
     `order` (a permutation of them; None: position order).  A position with an empty row (n = 0) is unclustered: id = SIG_NO_ID and zeros.
     Any other position p looks at the representatives chosen so far that it would be reported with at thr64 (both rows non-empty, filled > 0,
     match * 64 >= thr64 * filled).  None: p becomes a representative, its record is (p, its non-empty buckets twice, SIG_IDENTICAL).  Otherwise p
     joins the nearest of them (descending match / filled, then descending filled, then ascending position in the table): (r, match, filled,
-    n, d0 and d1 agree).  The device form (Context.signature_clusters) and the host form (signature_clusters_host) agree with it byte for byte"""
+    n, d0 and d1 agree).  seeds: a second table T whose records with n > 0 are representatives before the walk starts, all of them, whether
+    or not two of them would be reported together.  The order then runs over combined ids, seed j as j and position p of S as len(T) + p, so
+    a seed wins a full tie against a representative of S; a record whose nearest is a seed holds the seed's position in T and SIG_SEED in its
+    flags.  Without non-empty seeds the records are those of the unseeded walk.  The device form (Context.signature_clusters) and the host
+    form (signature_clusters_host) agree with it byte for byte"""
     S = _sig_table(S, "S")
     n = len(S)
     order = np.arange(n, dtype=np.int64) if order is None else np.asarray(order).astype(np.int64)
@@ -852,29 +857,37 @@ def signature_clusters_from_tables(S, order=None, thr64: int = 58) -> np.ndarray
         raise ValueError(f"signature clusters: order is not a permutation of 0 .. {n - 1}")
     if not 1 <= int(thr64) <= 64:
         raise ValueError("signature clusters: thr64 must be 1 .. 64")
+    T = S[:0] if seeds is None else _sig_table(seeds, "seeds")
+    nT = len(T)
+    if nT + n > 0xffffffff:
+        raise ValueError("signature clusters: the seeds and the table together hold more than 2^32 - 1 signatures")
+    X = np.concatenate([T, S]) if nT else S          # the combined id space: the seeds, then S
     out = np.zeros(n, SIGNATURE_NEIGHBOR_DTYPE)
     out["id"] = SIG_NO_ID
-    empty = S["sk"] == SIG_EMPTY
-    reps = np.zeros(n, np.int64)
-    n_reps = 0
+    empty = X["sk"] == SIG_EMPTY
+    reps = np.zeros(nT + n, np.int64)
+    n_reps = int((T["n"] > 0).sum())
+    reps[:n_reps] = np.nonzero(T["n"] > 0)[0]
     for p in order.tolist():
         if S["n"][p] == 0:
             continue
+        x = nT + p
         r = reps[:n_reps]
-        eq = (S["sk"][r] == S["sk"][p]).sum(-1)
-        E = (empty[r] & empty[p]).sum(-1)
+        eq = (X["sk"][r] == X["sk"][x]).sum(-1)
+        E = (empty[r] & empty[x]).sum(-1)
         match, filled = eq - E, 64 - E
         c = np.nonzero((filled > 0) & (match * 64 >= int(thr64) * filled))[0]
         if not len(c):
-            k = 64 - int(empty[p].sum())
+            k = 64 - int(empty[x].sum())
             out[p] = (p, k, k, SIG_IDENTICAL)
-            reps[n_reps] = p
+            reps[n_reps] = x
             n_reps += 1
             continue
         ratio = (match[c] << 20) // np.maximum(filled[c], 1)      # as in signature_neighbors_from_tables
         b = c[np.lexsort((r[c], -filled[c], -ratio))[0]]
         q = int(r[b])
-        out[p] = (q, match[b], filled[b], int(S["n"][q] == S["n"][p] and S["d0"][q] == S["d0"][p] and S["d1"][q] == S["d1"][p]))
+        same = int(X["n"][q] == X["n"][x] and X["d0"][q] == X["d0"][x] and X["d1"][q] == X["d1"][x])
+        out[p] = (q, match[b], filled[b], same | SIG_SEED) if q < nT else (q - nT, match[b], filled[b], same)
     return out
 
 
@@ -887,14 +900,23 @@ def signature_clusters_result(L, op, n: int) -> np.ndarray:
     return _lib.owned_view(L, op, n * SIGNATURE_NEIGHBOR_DTYPE.itemsize, np.uint8).view(SIGNATURE_NEIGHBOR_DTYPE)
 
 
-def signature_clusters_host(S, order=None, min_similarity: float = 0.9, thr64=None, threads: int = 1) -> np.ndarray:
+def signature_clusters_host(S, order=None, min_similarity: float = 0.9, thr64=None, threads: int = 1, seeds=None) -> np.ndarray:
     """the greedy clusters of a signature table on the CPU (fdgpu_signature_clusters_host: no context, no device): one
     SIGNATURE_NEIGHBOR_DTYPE record per position, see signature_clusters_from_tables.  The threshold is thr64 / 64 if thr64 is given, else
-    signature_threshold(min_similarity).  The result does not depend on `threads`.  Raises ValueError for a thr64 outside 1 .. 64 and an
+    signature_threshold(min_similarity).  seeds: a signature table whose non-empty records are representatives from the start
+    (fdgpu_signature_clusters_seeded_host).  The result does not depend on `threads`.  Raises ValueError for a thr64 outside 1 .. 64 and an
     order that is not a permutation of the positions"""
     S, order, t = _sig_cluster_args(S, order, min_similarity, thr64)
     L = _lib.load()
     op = C.c_void_p()
+    if seeds is not None:
+        T = _sig_table(seeds, "seeds")
+        rc = L.fdgpu_signature_clusters_seeded_host(S.ctypes.data, len(S), None if order is None else order.ctypes.data, T.ctypes.data if len(T) else None,
+                                                    len(T), t, max(int(threads), 1), C.byref(op))
+        if rc != 0:
+            raise ValueError(f"signature clusters: fdgpu_signature_clusters_seeded_host failed ({rc}): thr64 must be 1 .. 64, the seeds and the table "
+                             "together hold fewer than 2^32 - 1 signatures and order is a permutation of 0 .. n - 1")
+        return signature_clusters_result(L, op, len(S))
     rc = L.fdgpu_signature_clusters_host(S.ctypes.data, len(S), None if order is None else order.ctypes.data, t, max(int(threads), 1), C.byref(op))
     if rc != 0:
         raise ValueError(f"signature clusters: fdgpu_signature_clusters_host failed ({rc}): thr64 must be 1 .. 64, the table holds fewer than 2^32 "

@@ -694,6 +694,32 @@ int fdgpu_signature_clusters(fdgpu_ctx *ctx, const fd_signature *S, uint64_t n, 
 int fdgpu_signature_clusters_host(const fd_signature *S, uint64_t n, const uint32_t *order, uint32_t thr64, uint32_t n_threads,
                                   fd_sig_neighbor **out);
 
+/* ---- seeded clusters: the walk above with a seed table T[0 .. nT) whose representatives already stand ("which of S is new").
+ *   seeds         every T[j] with T[j].n > 0 is a representative from the start, unconditionally: two seeds that are a reported pair both
+ *                 stand.  A seed with n == 0 is never a candidate.
+ *   candidates    of p: the seeds and the representatives chosen so far from S whose pair with p would be reported at thr64.
+ *   order         fd_sig_nearer over a combined id space: seed j has id j, position p of S has id nT + p.  So on a full tie of match / filled
+ *                 and filled a seed beats a representative of S (what is already there is kept); within one table the smaller position wins.
+ *   record        {id, match, filled, flags}; flags bit 1, FD_SIG_SEED: id is a position in T, else in S.  A new representative stays
+ *                 {p, k, k, FD_SIG_IDENTICAL}, an unclustered position {0xFFFFFFFF, 0, 0, 0}.  A member of a seed is never a candidate.
+ * Integers only and a total order: the result is unique.  nT == 0 (T may be NULL), or seeds that all have n == 0: byte for byte the result
+ * of fdgpu_signature_clusters.  FDGPU_EINVAL and *out NULL, before any device work, the message opening "signature clusters:": the refusals
+ * of the unseeded call, T == NULL with nT > 0, nT + n > 0xFFFFFFFF (the combined ids leave 0xFFFFFFFF free).
+ * On the device the seeds never enter the table of representatives.  They do not change during the walk, so k_sg_cl_seed finds every
+ * position's nearest seed in ONE launch over all blocks (grid: blocks of 256 positions x splits of the seed tiles; k_sg_cl_seed_merge reduces
+ * the splits' partial bests when there are several), and k_sg_cl_resolve starts each lane from it: the walk then scans only the
+ * representatives S itself adds, whose records carry nT + p.  Workspace beyond the unseeded call's: 280 bytes per seed, 8 per position, and
+ * 8 per position and split when split: the splits are min(tiles of 64 seeds, 256, ceil(4096 / blocks)), so at most 8 MiB + 8 * n bytes.
+ * Test switch, read per call: FDGPU_SG_CL_SEED_SPLIT=n sets the splits (clamped to 1 .. min(tiles of 64 seeds, 256): at most 2 KB per
+ * position); the result does not depend on it. */
+#define FD_SIG_SEED 2u
+int fdgpu_signature_clusters_seeded(fdgpu_ctx *ctx, const fd_signature *S, uint64_t n, const uint32_t *order, const fd_signature *T, uint64_t nT,
+                                    uint32_t thr64, fd_sig_neighbor **out);
+/* The same on the CPU: every position's nearest seed with n_threads host threads (0 = 1) over the positions, then the blocked walk of
+ * fdgpu_signature_clusters_host; the result does not depend on n_threads.  No device.  The same refusals (code only). */
+int fdgpu_signature_clusters_seeded_host(const fd_signature *S, uint64_t n, const uint32_t *order, const fd_signature *T, uint64_t nT, uint32_t thr64,
+                                         uint32_t n_threads, fd_sig_neighbor **out);
+
 /* ---- exact row overlaps ------------------------------------------------------------------------------------------------------
  * For structures a and b with rows R_a and R_b (the ascending distinct hashes whose posting lists hold them; what fdgpu_index_rows returns):
  * the overlap is the integer inter = |R_a ∩ R_b|, union = |R_a| + |R_b| - inter, jaccard = inter / max(union, 1).  Integers only: the device
