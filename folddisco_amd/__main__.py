@@ -888,8 +888,21 @@ def cmd_neighbors(a):
     agreeing filled bucket).  One TSV row per neighbour, sorted by (id, rank): id tid n rank nb_id nb_tid nb_n match filled estimate
     class[ jaccard]; rank counts from 1, nearest first: by match / filled, then by filled, then by nb_id.  A structure without a neighbour gets
     no row.  This is the order of the sketches, not an exact nearest-neighbour search: --confirm adds the exact Jaccard similarity from the rows
-    but does not reorder.  No structure file is read."""
+    but does not reorder; --exact selects by the exact similarity instead (_neighbors_exact; --min-jaccard is its floor) and is refused together
+    with --confirm or an explicit --min-similarity.  No structure file is read."""
     from folddisco_amd import indexio
+    if a.min_jaccard is not None and not a.exact:
+        sys.exit("[FAIL] neighbors: --min-jaccard is the floor of --exact; give that too")
+    if a.exact and a.confirm:
+        sys.exit("[FAIL] neighbors: --exact already reports the exact similarity; leave --confirm out")
+    if a.exact and a.min_similarity is not None:
+        sys.exit("[FAIL] neighbors: --min-similarity is a floor of the sketches; the floor of --exact is --min-jaccard")
+    if a.min_jaccard is not None and not 0.0 < a.min_jaccard <= 1.0:      # NaN fails it too
+        sys.exit(f"[FAIL] neighbors: --min-jaccard {a.min_jaccard} is outside (0, 1]")
+    if a.pool_mb < 1 or a.counter_mb < 1:
+        sys.exit("[FAIL] neighbors: --pool-mb and --counter-mb must be at least 1")
+    if a.min_similarity is None:
+        a.min_similarity = 1.0 / 64
     if not 1 <= a.k <= indexio.SIG_MAX_K:
         sys.exit(f"[FAIL] neighbors: -k {a.k} is outside 1..{indexio.SIG_MAX_K}")
     if a.tids is not None and not os.path.isfile(a.tids):
@@ -912,6 +925,8 @@ def cmd_neighbors(a):
         if not a.host:
             import folddisco_amd as fd
             ctx = fd.Context(a.device)
+        if a.exact:
+            return _neighbors_exact(a, ctx, prefixes, tids, ids)
         tabs = [_dups_signatures(a, ctx, p, len(t)) for p, t in zip(prefixes, tids)]
         A, D = tabs[0], (tabs[1] if two else tabs[0])
         if ids is None:
@@ -944,6 +959,59 @@ def cmd_neighbors(a):
     if a.verbose:
         print(f"[INFO] neighbors on the {'host' if a.host else 'device'}: {len(ids)} queries, signatures of {sum(len(t) for t in tids)} structures "
               f"({sum(t.nbytes for t in tabs)} bytes)" + (f", {len(jac)} rows confirmed from their rows" + _extractions(a) if jac is not None else ""), file=sys.stderr)
+
+
+def _neighbors_exact(a, ctx, prefixes, tids, ids):
+    """`neighbors --exact`: the k nearest of the structures `ids` (ascending; None: every structure) by the exact Jaccard similarity of their
+    rows, from one walk over the posting lists of each query's hashes (indexio.row_neighbors on the device, row_neighbors_host with --host).
+    Every index is loaded once: checked if --verify, its signatures taken for n and the row lengths of the database, then kept for the walk;
+    inside one index a structure's own id is excluded.  A damaged index is a ValueError on either path.  One TSV row per neighbour, sorted by
+    (id, rank): id tid n rank nb_id nb_tid nb_n inter union jaccard class"""
+    from folddisco_amd import indexio
+    two = len(prefixes) == 2
+    T = 0 if a.min_jaccard is None else indexio.jaccard_floor(a.min_jaccard)
+    pool, counter = a.pool_mb * (1 << 20) // 4, a.counter_mb * (1 << 20)
+    files = [indexio.read_index_files(p) + (len(t),) for p, t in zip(prefixes, tids)]
+    if a.host:
+        if a.verify:
+            for p, (v, h, o, n) in zip(prefixes, files):
+                _stop_if_unsound(indexio.verify_host(v, h, o, n, threads=a.threads), p)
+        tabs = [np.array(indexio.signatures_host(v, h, o, n, threads=a.threads)) for v, h, o, n in files]
+    else:
+        import folddisco_amd as fd
+        ixs = [fd.FolddiscoIndex.load(ctx, h, o, v, n) for v, h, o, n in files]
+        del files
+        if a.verify:
+            for p, ix in zip(prefixes, ixs):
+                _stop_if_unsound(ix.verify(), p)
+        tabs = [np.array(ix.signatures(window=a.window)) for ix in ixs]
+    A, D = tabs[0], tabs[-1]
+    ids = np.arange(len(A), dtype=np.int64) if ids is None else ids
+    d_len = np.ascontiguousarray(D["n"], dtype=np.uint32)
+    excl = None if two else ids.astype(np.uint32)
+    if a.host:
+        nb = indexio.row_neighbors_host(files[0], files[1] if two else None, ids, d_len, k=a.k, floor_e4=T, exclude=excl, window=a.window, pool_hashes=pool,
+                                        threads=a.threads)
+    else:
+        try:
+            nb = indexio.row_neighbors(ixs[0], ixs[1] if two else None, ids, d_len, k=a.k, floor_e4=T, exclude=excl, window=a.window, pool_hashes=pool,
+                                       counter_bytes=counter)
+        except fd.FdgpuError as e:                   # a damaged index: the [FAIL] line and status 1 of --host
+            raise ValueError(str(e)) from None
+    at_q, at_r = np.nonzero(nb["id"] != indexio.ROW_NO_ID)           # row-major: ascending (id, rank)
+    td = tids[1] if two else tids[0]
+    lines = []
+    for q, rank, r in zip(at_q, at_r, nb[at_q, at_r]):
+        iq, ib, inter, union = int(ids[q]), int(r["id"]), int(r["inter"]), int(r["union"])
+        lines.append("\t".join([str(iq), tids[0][iq], str(int(A["n"][iq])), str(int(rank) + 1), str(ib), td[ib], str(int(D["n"][ib])), str(inter), str(union),
+                                f"{inter / max(union, 1):.4f}", "identical" if int(r["flags"]) & indexio.ROW_EQUAL else "similar"]) + "\n")
+    _write_tsv(a.output, lines, "neighbors")
+    n_none = int((nb["id"][:, 0] == indexio.ROW_NO_ID).sum()) if len(ids) else 0
+    n_ident = int(((nb["flags"][:, 0] & indexio.ROW_EQUAL) != 0).sum()) if len(ids) else 0
+    print(f"[OK] {' x '.join(prefixes)}: {' x '.join(str(len(t)) for t in tids)} structures, k = {a.k}, exact, {len(lines)} rows, {n_none} without a neighbour, "
+          f"{n_ident} with an identical nearest, floor {T}/10000")
+    if a.verbose:
+        print(f"[INFO] neighbors --exact on the {'host' if a.host else 'device'}: {len(ids)} queries against {len(D)} structures", file=sys.stderr)
 
 
 def _cluster_seed_ids(a, tids2):
@@ -1742,7 +1810,11 @@ def main(argv=None):
     pn.add_argument("-i", "--index", required=True, help="a single (unsharded) index prefix")
     pn.add_argument("--against", default=None, help="a second index prefix: the neighbours are looked for among its structures (default: among the others of PREFIX)")
     pn.add_argument("-k", type=int, default=8, help="neighbours per structure, 1..32")
-    pn.add_argument("--min-similarity", type=float, default=1.0 / 64, help="the share of agreeing filled buckets a neighbour must reach, in (0, 1]")
+    pn.add_argument("--min-similarity", type=float, default=None, help="the share of agreeing filled buckets a neighbour must reach, in (0, 1] (default: 1 / 64)")
+    pn.add_argument("--exact", action="store_true", help="the k nearest by the exact Jaccard similarity of the rows, counted from the posting lists, instead of by signature")
+    pn.add_argument("--min-jaccard", type=float, default=None, help="with --exact: the exact Jaccard similarity a neighbour must reach, in (0, 1] (default: any shared hash)")
+    pn.add_argument("--pool-mb", type=int, default=4096, help="megabytes of rows resident at a time (4 bytes per hash)")
+    pn.add_argument("--counter-mb", type=int, default=1024, help="with --exact: megabytes of the counter table (4 bytes per query of a block and structure)")
     pn.add_argument("--tids", default=None, help="text file with one tid per line (column 2 of PREFIX.lookup): only these structures are queries")
     pn.add_argument("--confirm", action="store_true", help="add the exact Jaccard similarity of every row, from the rows of its structures")
     pn.add_argument("-o", "--output", default="", help="the TSV file to write (default: standard output)")

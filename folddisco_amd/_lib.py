@@ -226,6 +226,9 @@ SYMBOLS = [
     ("fdgpu_rowset_intersect", C.c_int, [VP, VP, VP, u32p, u32p, C.c_uint64, C.POINTER(u32p)]),
     ("fdgpu_rowset_destroy", None, [VP]),
     ("fdgpu_rows_intersect_host", C.c_int, [u32p, u64p, C.c_uint64, u32p, u64p, C.c_uint64, u32p, u32p, C.c_uint64, C.c_uint32, C.POINTER(u32p)]),
+    ("fdgpu_rowset_neighbors", C.c_int, [VP, VP, VP, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(VP)]),
+    ("fdgpu_rows_neighbors_host", C.c_int, [u32p, u64p, C.c_uint64, u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.POINTER(VP)]),
     ("fdgpu_index_verify", C.c_int, [VP, VP, C.POINTER(VerifyReportC)]),
     ("fdgpu_verify_host", C.c_int, [u32p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyReportC)]),
     ("fdgpu_posting_bytes", C.c_int, [VP, VP, u32p, C.c_uint64, u64p]),

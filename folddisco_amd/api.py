@@ -179,6 +179,22 @@ class Context:
         self.check(self.L.fdgpu_rowset_intersect(self.h, A.h, None if B is None else B.h, _ptr(ka, u32p), _ptr(kb, u32p), len(ka), C.byref(op)))
         return _lib.owned_view(self.L, op, max(len(ka), 1) * 4, np.uint32)[: len(ka)]
 
+    def rowset_neighbors(self, Q: "RowSet", D_index: "FolddiscoIndex", d_len, k: int = 8, floor=None, floor_e4: int = 0, exclude=None,
+                         counter_bytes: int = 0) -> np.ndarray:
+        """the exact neighbours on the device (fdgpu_rowset_neighbors): for every row of Q its k nearest structures of the resident index
+        D_index by the Jaccard similarity of the rows -> (Q.n_rows, k) indexio.ROW_NEIGHBOR_DTYPE records.  d_len[s] = the length of the row
+        of D_index's structure s; exclude[q] (optional) = one absolute id of D_index that is never q's neighbour, indexio.ROW_NO_ID = none;
+        the floor is floor_e4 / 10^4, or indexio.jaccard_floor(floor) if that is given; counter_bytes bounds the counter table (0: 1 GiB).
+        The contract of indexio.rows_neighbors_host, which it equals byte for byte"""
+        from . import indexio
+        d_len, k, T, exclude = indexio._row_neighbor_args(Q.n_rows, D_index.n_structures, d_len, k, floor, floor_e4, exclude)
+        if int(counter_bytes) < 0:
+            raise ValueError("row neighbors: counter_bytes is a count of bytes")
+        op = C.c_void_p()
+        self.check(self.L.fdgpu_rowset_neighbors(self.h, Q.h, D_index.h, _ptr(d_len, u32p), None if exclude is None else _ptr(exclude, u32p), k, T,
+                                                 int(counter_bytes), C.byref(op)))
+        return indexio.row_neighbors_result(self.L, op, Q.n_rows, k)
+
     # ---- batches
     def upload(self, ps: PackedStructures) -> "Batch":
         d = BatchDesc(ps.n_struct, _ptr(ps.res_off, u64p), _ptr(ps.n_xyz, f32p), _ptr(ps.ca_xyz, f32p), _ptr(ps.cb_xyz, f32p),

@@ -52,6 +52,8 @@ enum {
     WS_SG_CL_OUT /* the records in walk order */, WS_SG_CL_PART /* a block's partial bests, [split][lane] */, WS_SG_CL_COUNT /* the number of representatives */,
     WS_SG_CL_SEEDS /* seeded clusters: the seed table */, WS_SG_CL_SEED_BEST /* every position's nearest seed, in walk order */,
     WS_SG_CL_SEED_PART /* the seed pass's partial bests, [split][position] */,
+    WS_XN_CNT /* exact neighbours: the counter table of a block of queries, u32 [QB][S], zero between the blocks */,
+    WS_XN_PART /* the k-lists of every split of a block, [split][query of the block][k] */, WS_XN_OUT /* the result, [query][k] */,
     WS_COUNT
 };
 
@@ -221,6 +223,18 @@ struct fdgpu_index {
     mutable uint64_t ck_n = 0, ck_first = 0, ck_S = 0;
     mutable bool ck_failed = false;                  // the table did not fit for the id range (ck_first, ck_S): the tiled path is off until the range changes or a retry succeeds
     mutable uint32_t ck_fail_skips = 0;
+};
+
+// a row set (k_overlap.hip makes and releases it; the exact neighbours, k_exact.hip, read it)
+struct fdgpu_rowset {
+    fdgpu_ctx *ctx = nullptr;
+    uint64_t n_rows = 0, n_hashes = 0;
+    struct block { void *p; size_t cap; uint64_t n; };      // one per window: n hashes, the window's taken rows back to back
+    std::vector<block> blocks;
+    const uint32_t **row_ptr = nullptr;                     // device [n_rows]: where row k starts
+    uint32_t *row_len = nullptr;                            // device [n_rows]
+    size_t cap_ptr = 0, cap_len = 0;
+    std::vector<uint32_t> h_len;                            // the lengths on the host: the export's offsets
 };
 
 // making an index (fdgpu_api.hip): the object and its hashes / offsets blocks, last_ids if with_last, value_len value bytes + FD_VALUE_SLACK

@@ -38,17 +38,6 @@
 #define OV_TILE 64u
 #define OV_KEY_BITS 6
 
-struct fdgpu_rowset {
-    fdgpu_ctx *ctx = nullptr;
-    uint64_t n_rows = 0, n_hashes = 0;
-    struct block { void *p; size_t cap; uint64_t n; };      // one per window: n hashes, the window's taken rows back to back
-    std::vector<block> blocks;
-    const uint32_t **row_ptr = nullptr;                     // device [n_rows]: where row k starts
-    uint32_t *row_len = nullptr;                            // device [n_rows]
-    size_t cap_ptr = 0, cap_len = 0;
-    std::vector<uint32_t> h_len;                            // the lengths on the host: the export's offsets
-};
-
 extern "C" void fdgpu_rowset_destroy(fdgpu_rowset *rs) {
     if (!rs) return;
     FD_LOCK(rs->ctx);     // the blocks go back to the context's pool

@@ -627,6 +627,155 @@ def row_overlaps_host(files_a, files_b, a, b, window: int = 16384, pool_hashes: 
     return _row_overlap_tiles(take(files_a), take(files_b), lambda A, B, ka, kb: rows_intersect_host(A, B, ka, kb, threads=threads), a, b, pool_hashes, stats)
 
 
+# ---- exact neighbours (include/fdgpu.h: fd_row_neighbor, fdgpu_rowset_neighbors, fdgpu_rows_neighbors_host) ----------------------------------
+# For a query row R_q and structure s of an index D: inter = the number of hashes of R_q whose list in D holds s, union = |R_q| + d_len[s] - inter.
+# s is a candidate iff inter > 0, s != exclude[q] and inter * 10^4 >= floor_e4 * union; nearer = the larger inter / union (cross products), then
+# the larger inter, then the smaller id.  Integers only.
+ROW_NEIGHBOR_DTYPE = np.dtype([("id", "<u4"), ("inter", "<u4"), ("union", "<u4"), ("flags", "<u4")])      # 16 bytes; an empty slot: id = ROW_NO_ID, zeros
+ROW_NO_ID = 0xffffffff
+ROW_EQUAL = 1                                        # flags bit 0: inter == |R_q| == d_len, the two rows are the same set
+ROW_MAX_K = 32
+assert ROW_NEIGHBOR_DTYPE.itemsize == 16
+
+
+def _row_neighbor_args(nQ, S, d_len, k, floor, floor_e4, exclude):
+    T = int(floor_e4) if floor is None else jaccard_floor(floor)
+    if not (0 <= int(k) <= 0xffffffff and 0 <= T <= 0xffffffff):
+        raise ValueError("row neighbors: k must be 1 .. 32 and floor_e4 0 .. 10000")
+    d_len = np.ascontiguousarray(d_len, dtype=np.uint32)
+    if d_len.shape != (int(S),):
+        raise ValueError(f"row neighbors: d_len needs one row length per structure of the index ({S}), got shape {d_len.shape}")
+    if exclude is not None:
+        exclude = np.ascontiguousarray(exclude, dtype=np.uint32)
+        if exclude.shape != (nQ,):
+            raise ValueError(f"row neighbors: exclude needs one id per query ({nQ}), got shape {exclude.shape}")
+    return d_len, int(k), T, exclude
+
+
+def row_neighbors_result(L, op, nQ: int, k: int) -> np.ndarray:
+    """the library's fd_row_neighbor records as a (nQ, k) array; releases the block"""
+    if not nQ:
+        if op:
+            L.fdgpu_free(op)
+        return np.zeros((0, k), ROW_NEIGHBOR_DTYPE)
+    return _lib.owned_view(L, op, nQ * k * ROW_NEIGHBOR_DTYPE.itemsize, np.uint8).view(ROW_NEIGHBOR_DTYPE).reshape(nQ, k)
+
+
+def rows_neighbors_host(q_rows, files_d, d_len, k: int = 8, floor=None, floor_e4: int = 0, exclude=None, threads: int = 1) -> np.ndarray:
+    """the exact neighbours on the CPU (fdgpu_rows_neighbors_host: no context, no device): q_rows = the query rows as CSR (hashes, row_off),
+    files_d = (value, hashes, offsets, n_structures[, first_id]) of the index D, d_len[s] = the length of the row of D's structure s ->
+    (n_queries, k) ROW_NEIGHBOR_DTYPE records, see row_neighbors_from_rows.  The floor is floor_e4 / 10^4, or jaccard_floor(floor) if that is
+    given.  The result does not depend on `threads`.  Raises ValueError opening "row neighbors:" for k outside 1 .. 32, floor_e4 above 10000,
+    an exclude id outside D, a damaged index, or row lengths that do not belong to the index"""
+    qh, qo = _csr_rows(q_rows, "q_rows")
+    value, hashes, offsets, S = files_d[:4]
+    first = int(files_d[4]) if len(files_d) > 4 else 0
+    value, hashes, offsets = np.ascontiguousarray(value, dtype=np.uint8), np.ascontiguousarray(hashes, dtype=np.uint32), np.ascontiguousarray(offsets, dtype=np.uint64)
+    nQ = len(qo) - 1
+    d_len, k, T, exclude = _row_neighbor_args(nQ, S, d_len, k, floor, floor_e4, exclude)
+    L = _lib.load()
+    op = C.c_void_p()
+    rc = L.fdgpu_rows_neighbors_host(qh.ctypes.data_as(u32p), qo.ctypes.data_as(u64p), nQ, hashes.ctypes.data_as(u32p), offsets.ctypes.data_as(u64p), len(hashes),
+                                     value.ctypes.data_as(u8p), len(value), first, int(S), d_len.ctypes.data_as(u32p),
+                                     None if exclude is None else exclude.ctypes.data_as(u32p), k, T, max(int(threads), 1), C.byref(op))
+    if rc != 0:
+        raise ValueError(f"row neighbors: fdgpu_rows_neighbors_host failed ({rc}): k must be 1 .. 32, floor_e4 0 .. 10000, an exclude id is 0xFFFFFFFF or an "
+                         "id of the index, the index is sound and d_len holds its rows' lengths")
+    return row_neighbors_result(L, op, nQ, k)
+
+
+def row_neighbors_from_rows(q_rows, d_rows, first_id: int = 0, k: int = 8, floor_e4: int = 0, exclude=None) -> np.ndarray:
+    """THE SPECIFICATION of the exact neighbours, in plain Python: sets and a full sort.  q_rows / d_rows: the query rows and ALL rows of D as
+    CSR; structure s of D has the id first_id + s -> (n_queries, k) ROW_NEIGHBOR_DTYPE records.  s is a candidate of q iff inter = |R_q ∩ R_s|
+    > 0, first_id + s != exclude[q] and inter * 10^4 >= floor_e4 * union (union = |R_q| + |R_s| - inter).  Row q holds q's candidates by
+    descending inter / union (as exact fractions), then descending inter, then ascending id, cut at k; the slots behind them are empty
+    (id = ROW_NO_ID, zeros).  flags bit 0: inter == |R_q| == |R_s|.  The device form (Context.rowset_neighbors) and the host form
+    (rows_neighbors_host) agree with it byte for byte"""
+    qh, qo = _csr_rows(q_rows, "q_rows")
+    dh, do = _csr_rows(d_rows, "d_rows")
+    nQ, S = len(qo) - 1, len(do) - 1
+    ds = [frozenset(dh[int(do[s]):int(do[s + 1])].tolist()) for s in range(S)]
+    out = np.zeros((nQ, int(k)), ROW_NEIGHBOR_DTYPE)
+    out["id"] = ROW_NO_ID
+    for q in range(nQ):
+        rq = frozenset(qh[int(qo[q]):int(qo[q + 1])].tolist())
+        skip = ROW_NO_ID if exclude is None else int(exclude[q])
+        cand = []
+        for s, rs in enumerate(ds):
+            i = len(rq & rs)
+            u = len(rq) + len(rs) - i
+            if i > 0 and first_id + s != skip and i * 10000 >= int(floor_e4) * u:
+                cand.append((-((i << 64) // u), -i, first_id + s, u))      # fractions with denominators below 2^32: distinct -> distinct integers, equal -> equal
+        for r, (_, ni, sid, u) in enumerate(sorted(cand)[:int(k)]):
+            out[q, r] = (sid, -ni, u, ROW_EQUAL if -ni == len(rq) == len(ds[sid - first_id]) else 0)
+    return out
+
+
+def _row_neighbor_ids(ids):
+    ids = np.asarray(ids)
+    if ids.ndim != 1 or (len(ids) and (ids.dtype.kind not in "iu" or int(ids.min()) < 0 or int(ids.max()) > 0xffffffff)):
+        raise ValueError("row neighbors: ids are absolute structure ids (1-d, below 2^32)")
+    ids = ids.astype(np.int64)
+    if len(ids) > 1 and not bool((np.diff(ids) > 0).all()):
+        raise ValueError("row neighbors: the query ids ascend strictly")
+    return ids
+
+
+def _row_neighbor_chunks(take, neighbors, ids, k, exclude, pool_hashes, stats):
+    """the tiling both drivers share: take(ids, max_hashes) -> (query set, n_taken) extracts a prefix of the ascending ids, neighbors(set,
+    exclude of the chunk) -> its records; sets are released with .close() where they have one"""
+    ids = _row_neighbor_ids(ids)
+    if exclude is not None:
+        exclude = np.ascontiguousarray(exclude, dtype=np.uint32)
+        if exclude.shape != (len(ids),):
+            raise ValueError(f"row neighbors: exclude needs one id per query ({len(ids)}), got shape {exclude.shape}")
+    out = np.zeros((len(ids), int(k)), ROW_NEIGHBOR_DTYPE)
+    at, chunks = 0, 0
+    while at < len(ids):
+        Q, t = take(ids[at:], max(int(pool_hashes), 1))
+        out[at:at + t] = neighbors(Q, None if exclude is None else exclude[at:at + t])
+        if hasattr(Q, "close"):
+            Q.close()
+        at += t
+        chunks += 1
+    if stats is not None:
+        stats.update({"chunks": chunks})
+    return out
+
+
+def row_neighbors(ix_q, ix_d, ids, d_len, k: int = 8, floor_e4: int = 0, exclude=None, window: int = 16384, pool_hashes: int = OVERLAP_POOL_HASHES,
+                  counter_bytes: int = 0, stats=None) -> np.ndarray:
+    """the exact neighbours of the structures `ids` (absolute, strictly ascending) of the resident index ix_q among the structures of ix_d
+    (None or ix_q itself: one index; both on one context), on the device -> (len(ids), k) ROW_NEIGHBOR_DTYPE records.  d_len[s] = the length
+    of the row of ix_d's structure s (the n of its signature); exclude[j] (optional) = one id of ix_d that is never a neighbour of ids[j],
+    ROW_NO_ID = none.  The query rows are taken in chunks of at most pool_hashes hashes (one FolddiscoIndex.rowset call each, advancing by
+    its n_taken) and every chunk is one Context.rowset_neighbors call with a counter table of at most counter_bytes bytes (0: 1 GiB).  The
+    result does not depend on pool_hashes, window or counter_bytes"""
+    ix_d = ix_q if ix_d is None else ix_d
+    ctx = ix_q.ctx
+    return _row_neighbor_chunks(lambda rest, pool: ix_q.rowset(rest, window=window, max_hashes=pool),
+                                lambda Q, ex: ctx.rowset_neighbors(Q, ix_d, d_len, k=k, floor_e4=floor_e4, exclude=ex, counter_bytes=counter_bytes),
+                                ids, k, exclude, pool_hashes, stats)
+
+
+def row_neighbors_host(files_q, files_d, ids, d_len, k: int = 8, floor_e4: int = 0, exclude=None, window: int = 16384,
+                       pool_hashes: int = OVERLAP_POOL_HASHES, threads: int = 1, stats=None) -> np.ndarray:
+    """row_neighbors on the CPU (no context, no device): files_q / files_d = (value, hashes, offsets, n_structures[, first_id]) of the two
+    indices (files_d = None: one index).  The same chunks over rows_host windows; the same result, whatever pool_hashes, window and threads are"""
+    files_d = files_q if files_d is None else files_d
+    files_q = (np.ascontiguousarray(files_q[0], dtype=np.uint8), np.ascontiguousarray(files_q[1], dtype=np.uint32),
+               np.ascontiguousarray(files_q[2], dtype=np.uint64)) + tuple(files_q[3:])
+    first_q = int(files_q[4]) if len(files_q) > 4 else 0
+
+    def take(rest, pool):
+        if len(rest) and (int(rest[0]) < first_q or int(rest[-1]) >= first_q + int(files_q[3])):
+            raise ValueError("row neighbors: a query id is outside [first_id, first_id + n_structures)")
+        rows, _, t = _rowset_host(files_q, rest, window, pool, threads)
+        return rows, t
+    return _row_neighbor_chunks(take, lambda Q, ex: rows_neighbors_host(Q, files_d, d_len, k=k, floor_e4=floor_e4, exclude=ex, threads=threads),
+                                ids, k, exclude, pool_hashes, stats)
+
+
 # ---- index signatures (include/fdgpu.h: fd_signature, fd_sig_pair) ---------------------------------------------------------------------------
 SIGNATURE_DTYPE =np.dtype([("n", "<u4"), ("reserved", "<u4"), ("d0", "<u8"), ("d1", "<u8"), ("sk", "<u4", (64,))])      # 280 bytes
 SIGNATURE_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("match", "u1"), ("filled", "u1"), ("flags", "<u2")])      # 12 bytes; flags bit 0 = identical

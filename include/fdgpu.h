@@ -760,6 +760,45 @@ void fdgpu_rowset_destroy(fdgpu_rowset *rs);
 int fdgpu_rows_intersect_host(const uint32_t *ha, const uint64_t *off_a, uint64_t n_a, const uint32_t *hb, const uint64_t *off_b, uint64_t n_b,
                               const uint32_t *ka, const uint32_t *kb, uint64_t n_pairs, uint32_t n_threads, uint32_t **inter);
 
+/* ---- exact neighbours: for every row of a row set Q its k nearest structures of a resident index D by the Jaccard similarity of the rows.
+ * D holds the structures first_id .. first_id + S - 1; d_len[S] is the length of each one's row in D, supplied by the caller (the n of the
+ * signatures).  For query q with row R_q and structure s:
+ *   inter      the number of h in R_q whose posting list in D holds s: |R_q ∩ R_s|, counted by one walk over the lists of R_q's hashes; the
+ *              rows of D are never made
+ *   uni        |R_q| + d_len[s - first_id] - inter
+ *   candidate  s is a candidate of q iff inter > 0, s != exclude[q] (optional array of absolute ids of D, 0xFFFFFFFF = none) and
+ *              inter * 10^4 >= floor_e4 * uni in 64-bit integers (floor_e4 in 0 .. 10000; 0: any shared hash)
+ *   order      x is nearer than y iff inter_x * uni_y > inter_y * uni_x (u64), or these are equal and inter_x > inter_y, or those are equal too
+ *              and id_x < id_y (csrc/fd_row_neighbor.h).  Integers only and a total order: the result is unique and does not depend on the
+ *              launch geometry or on the order in which the lists are walked
+ *   result     nQ x k records, row q = q's nearest candidates in that order; id is the absolute id in D; flags bit 0, FD_ROW_EQUAL: inter ==
+ *              |R_q| == d_len[s], the two rows are the same set.  A slot beyond q's number of candidates holds {0xFFFFFFFF, 0, 0, 0}; a query
+ *              with an empty row has only such slots.  k is in 1 .. 32.  16 bytes. */
+typedef struct fd_row_neighbor { uint32_t id, inter, uni, flags; } fd_row_neighbor;
+#define FD_ROW_EQUAL 1u
+/* The neighbours on the device (csrc/k_exact.hip).  The queries go in blocks of QB = clamp(max_counter_bytes / (4 * S), 1, nQ) rows
+ * (max_counter_bytes == 0: 1 GiB), each block with a u32 counter table [QB][S] in a context workspace: k_xn_count (one wavefront per 64
+ * hashes of a query row: a binary search per lane in D's hash table, then the 64 lists walked in turn, one no-return atomic add per decoded
+ * id) and k_xn_select (grid: query x split of the id range; every lane keeps a k-list in LDS, the wavefront merges them; k_xn_merge reduces
+ * the splits when there are several).  Integer adds commute: the table, and with it the result, is byte-identical from run to run and for
+ * every split and counter budget.  *out holds max(nQ * k, 1) records, released with fdgpu_free.
+ * FDGPU_EINVAL with a message opening "rowset neighbors:", before any launch, no stage recorded and *out NULL: Q or D NULL, k outside
+ * 1 .. 32, floor_e4 > 10000, d_len NULL with S > 0, an exclude id that is neither 0xFFFFFFFF nor inside D, a row set of another context.
+ * nQ == 0: an empty result.  Behind the kernels, FDGPU_EINVAL and *out NULL, the context still usable: a counter above min(|R_q|, d_len)
+ * ("row lengths do not belong to this index"), or a damaged index (offsets that do not ascend inside the value bytes, a varint that leaves
+ * its list, an id outside D — such an id raises the flag and is never used as an address).
+ * Test switch, read per call: FDGPU_XN_SPLIT=n sets the splits of the selection (clamped to 1 .. min(tiles of 64 ids, 64)); the result
+ * does not depend on it.  Workspace: 4 * QB * S bytes of counters, 4 * S + 4 * nQ, 8 per 64 hashes of Q, 16 * k per query and per split. */
+int fdgpu_rowset_neighbors(fdgpu_ctx *ctx, const fdgpu_rowset *Q, const fdgpu_index *D, const uint32_t *d_len, const uint32_t *exclude, uint32_t k,
+                           uint32_t floor_e4, uint64_t max_counter_bytes, fd_row_neighbor **out);
+/* The same neighbours over host arrays: the query rows as CSR (ascending distinct hashes, as fdgpu_index_rows returns them) and the files of
+ * D.  n_threads host threads (0 = 1) over ranges of queries, each with one counter array of S that it resets where it touched it; the
+ * result does not depend on their number.  No device.  The same records and the same refusals (code only; and FDGPU_EINVAL for query
+ * offsets that descend or first_id + S above 0xFFFFFFFF). */
+int fdgpu_rows_neighbors_host(const uint32_t *q_hashes, const uint64_t *q_off, uint64_t nQ, const uint32_t *d_hashes, const uint64_t *d_offsets,
+                              uint64_t n_hashes, const uint8_t *d_value, uint64_t value_len, uint64_t first_id, uint64_t S, const uint32_t *d_len,
+                              const uint32_t *exclude, uint32_t k, uint32_t floor_e4, uint32_t n_threads, fd_row_neighbor **out);
+
 /* ---- index verification -----------------------------------------------------------------------------------------------------
  * Is an index well formed?  The definition (eight classes of damage, three on the hashes / offsets table and five on the posting
  * lists) is csrc/fd_verify.h and DESIGN.md; nothing else in the library checks the bytes it is given, every kernel uses offsets and
