@@ -73,6 +73,26 @@ class Retrieval(C.Structure):
                 ("n_cand", C.c_uint64), ("cand_qi", u64p), ("cand_i", u64p), ("cand_j", u64p)]
 
 
+class KabschTrace(C.Structure):      # fd_oracle.h fdo_kabsch_trace_t
+    _fields_ = [("spur", C.c_double), ("h", C.c_double), ("g", C.c_double), ("disc", C.c_double), ("e", C.c_double * 3),
+                ("gap01", C.c_double), ("gap12", C.c_double), ("adj", (C.c_double * 6) * 2), ("d_norm", C.c_double * 2),
+                ("p", C.c_double), ("fb_a_len", C.c_double), ("d_b", C.c_double * 2), ("p_b", C.c_double), ("fb_b_len", C.c_double),
+                ("spur_pos", C.c_int32), ("h_pos", C.c_int32), ("guard", C.c_int32), ("flushed", C.c_int32 * 2),
+                ("column", C.c_int32 * 2), ("norm_zero", C.c_int32 * 2), ("keep_first", C.c_int32), ("fb_a", C.c_int32),
+                ("fb_a_axis", C.c_int32), ("db_zero", C.c_int32 * 2), ("fb_b", C.c_int32), ("fb_b_axis", C.c_int32), ("built", C.c_int32)]
+
+    # the discrete decisions of the construction, in the order they are taken
+    DECISIONS = ("spur_pos", "h_pos", "guard", "flushed", "column", "norm_zero", "keep_first", "fb_a", "fb_a_axis", "db_zero", "fb_b",
+                 "fb_b_axis", "built")
+
+    def as_dict(self) -> dict:
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            out[name] = v if isinstance(v, (int, float)) else np.array(v).tolist()
+        return out
+
+
 _lib = None
 
 
@@ -171,6 +191,8 @@ def lib():
     L.fdo_retrieval_free.argtypes = [C.POINTER(Retrieval)]
     L.fdo_kabsch.restype = C.c_float
     L.fdo_kabsch.argtypes = [f32p, f32p, C.c_uint64, C.c_int, f32p, f32p]
+    L.fdo_kabsch_trace.restype = C.c_float
+    L.fdo_kabsch_trace.argtypes = [f32p, f32p, C.c_uint64, C.c_int, f32p, f32p, i64p, C.POINTER(KabschTrace)]
     L.fdo_set_hash_type.restype = C.c_int
     L.fdo_set_hash_type.argtypes = [C.c_uint32]
     L.fdo_get_hash_type.restype = C.c_uint32
@@ -438,6 +460,21 @@ def kabsch(x: np.ndarray, y: np.ndarray, mode=2):
     tran = (C.c_float * 3)()
     r = lib().fdo_kabsch(xp, yp, len(x.reshape(-1, 3)), mode, rot, tran)
     return float(r), np.array(list(rot), dtype=np.float32).reshape(3, 3), np.array(list(tran), dtype=np.float32)
+
+
+def kabsch_trace(x: np.ndarray, y: np.ndarray, nudge=(0, 0, 0), mode=2):
+    """kabsch() with its decision trace (a dict of fdo_kabsch_trace_t; trace["decisions"] = the discrete ones as one tuple) and
+    `nudge` signed ulps added to e[0..2] right after the trigonometric solve.  Zero nudge: the bits of kabsch()."""
+    x, xp = _f32(x)
+    y, yp = _f32(y)
+    rot = (C.c_float * 9)()
+    tran = (C.c_float * 3)()
+    tr = KabschTrace()
+    nd = (C.c_int64 * 3)(*[int(v) for v in nudge])
+    r = lib().fdo_kabsch_trace(xp, yp, len(x.reshape(-1, 3)), mode, rot, tran, nd, C.byref(tr))
+    d = tr.as_dict()
+    d["decisions"] = tuple(tuple(d[k]) if isinstance(d[k], list) else d[k] for k in KabschTrace.DECISIONS)
+    return float(r), np.array(list(rot), dtype=np.float32).reshape(3, 3), np.array(list(tran), dtype=np.float32), d
 
 
 class hash_type:

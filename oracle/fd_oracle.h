@@ -202,6 +202,21 @@ fdo_retrieval *fdo_retrieve(const fdo_structure *target, const fdo_structure *qu
 void fdo_retrieval_free(fdo_retrieval *r);
 /* kabsch(x = coords, y = reference, mode) (kabsch.rs:157-554). returns rmsd as f32 */
 float fdo_kabsch(const float *x, const float *y, uint64_t n, int mode, float rot[9], float tran[3]);
+/* every variable a decision of the eigen construction reads, and the side each decision took (zero where the construction did not
+ * get that far).  fb_a / fb_b: 0 = the Gram-Schmidt remainder was kept, 1 = the perpendicular fallback ran, 2 = it failed too. */
+typedef struct fdo_kabsch_trace_t {
+    double spur, h, g, disc, e[3], gap01, gap12;
+    double adj[2][6];          /* the six adjugate entries of e[0] and of e[2], before the EPSILON flush */
+    double d_norm[2];          /* squared length of the chosen column (after the flush) */
+    double p, fb_a_len, d_b[2], p_b, fb_b_len;
+    int32_t spur_pos, h_pos, guard;
+    int32_t flushed[2];        /* bit k: entry k was flushed */
+    int32_t column[2], norm_zero[2];
+    int32_t keep_first, fb_a, fb_a_axis, db_zero[2], fb_b, fb_b_axis, built;
+} fdo_kabsch_trace_t;
+/* fdo_kabsch IS this function with nudge = trace = NULL.  nudge: signed ulps added to e[0..2] right after the trigonometric solve. */
+float fdo_kabsch_trace(const float *x, const float *y, uint64_t n, int mode, float rot[9], float tran[3], const int64_t nudge[3],
+                       fdo_kabsch_trace_t *trace);
 void fdo_metrics(const float *ref, const float *mov, uint64_t n, const float rot[9], const float tran[3], float out[5]);
 /* LmsQcpSuperimposer (structure/lms_qcp.rs:91-249, default parameters): x = coords (moving), y = reference; returns the rms
  * over the final core; core (n slots, may be NULL) receives the core indices in insertion order. */

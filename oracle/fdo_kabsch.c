@@ -4,9 +4,34 @@
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 #include "fd_oracle.h"
 
+/* e += ulps units in the last place (the ordered-integer image of a double; 0 leaves the bits alone) */
+static double nudge_ulps(double v, int64_t ulps) {
+    if (ulps == 0) return v;
+    int64_t b;
+    memcpy(&b, &v, sizeof b);
+    if (b < 0) b = INT64_MIN - b;      /* negative doubles: descending bit patterns -> ascending integers */
+    b += ulps;
+    if (b < 0) b = INT64_MIN - b;
+    memcpy(&v, &b, sizeof b);
+    return v;
+}
+
 float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float rot[9], float tran[3]) {
+    return fdo_kabsch_trace(xf, yf, n, mode, rot, tran, NULL, NULL);
+}
+
+/* The one restatement: fdo_kabsch is this function with no trace and no nudge.  `tr` (may be NULL) receives every variable a
+ * decision of the construction reads and the side each decision took; `nudge` (may be NULL) adds signed ulps to e[0..2] right
+ * after the trigonometric solve — the only place where another libm (atan2 / cos / sin) can move a value — so that a test can
+ * ask whether a case's decisions and outputs survive a few ulps there. */
+float fdo_kabsch_trace(const float *xf, const float *yf, uint64_t n, int mode, float rot[9], float tran[3], const int64_t nudge[3],
+                       fdo_kabsch_trace_t *tr) {
+    fdo_kabsch_trace_t tr_local;
+    if (!tr) tr = &tr_local;
+    memset(tr, 0, sizeof *tr);
     static const int IP[9] = {0, 1, 3, 1, 2, 4, 3, 4, 5};
     static const int IP2312[4] = {1, 2, 0, 1};
     const double EPSILON = 1.0e-8, TOLERANCE = 0.01, SQRT3 = 1.7320508075688772;
@@ -54,15 +79,18 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
     double cof = (((rr[2] * rr[5] - rr[4] * rr[4]) + rr[0] * rr[5] - rr[3] * rr[3]) + rr[0] * rr[2] - rr[1] * rr[1]) / 3.0;
     double det = det_r * det_r;
     e[0] = e[1] = e[2] = spur;
+    tr->spur = spur; tr->spur_pos = spur > 0.0;
 
     if (spur > 0.0) {
         double d = spur * spur;
         double h = d - cof;
         double g = (spur * cof - det) / 2.0 - spur * h;
+        tr->h = h; tr->g = g; tr->h_pos = h > 0.0;
         if (h > 0.0) {
             double sqrth = sqrt(h);
             double disc = h * h * h - g * g;
             if (disc < 0.0) disc = 0.0;
+            tr->disc = disc; tr->guard = fabs(g) > 1e18;
             double sqrt_disc = sqrt(disc);
             double d_ang = fabs(g) > 1e18 ? (g > 0.0 ? M_PI / 3.0 : 0.0) : atan2(sqrt_disc, -g) / 3.0;
             double cth = sqrth * cos(d_ang);
@@ -70,6 +98,9 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
             e[0] = spur + 2.0 * cth;
             e[1] = spur - cth + sth;
             e[2] = spur - cth - sth;
+            if (nudge) for (int i = 0; i < 3; ++i) e[i] = nudge_ulps(e[i], nudge[i]);
+            for (int i = 0; i < 3; ++i) tr->e[i] = e[i];
+            tr->gap01 = e[0] - e[1]; tr->gap12 = e[1] - e[2];
             if (mode != 0) {
                 int a_failed = 0, b_failed = 0;
                 for (int li = 0; li < 2; ++li) {
@@ -81,8 +112,10 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
                     ss[3] = (dl - rr[2]) * rr[3] + rr[1] * rr[4];
                     ss[4] = (dl - rr[0]) * rr[4] + rr[1] * rr[3];
                     ss[5] = (dl - rr[0]) * (dl - rr[2]) - rr[1] * rr[1];
-                    for (int k = 0; k < 6; ++k)
-                        if (fabs(ss[k]) <= EPSILON) ss[k] = 0.0;
+                    for (int k = 0; k < 6; ++k) {
+                        tr->adj[li][k] = ss[k];
+                        if (fabs(ss[k]) <= EPSILON) { ss[k] = 0.0; tr->flushed[li] |= 1 << k; }
+                    }
                     double A = fabs(ss[0]), B = fabs(ss[2]), C = fabs(ss[5]);
                     int j = (A >= B && A >= C) ? 0 : (B >= C ? 1 : 2);
                     double dnorm = 0.0;
@@ -91,17 +124,20 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
                         a[i][l] = ss[k];
                         dnorm += ss[k] * ss[k];
                     }
+                    tr->column[li] = j; tr->d_norm[li] = dnorm; tr->norm_zero[li] = !(dnorm > EPSILON);
                     dnorm = dnorm > EPSILON ? 1.0 / sqrt(dnorm) : 0.0;
                     for (int i = 0; i < 3; ++i) a[i][l] *= dnorm;
                 }
                 double dt = a[0][0] * a[0][2] + a[1][0] * a[1][2] + a[2][0] * a[2][2];
                 int m1, mm;
                 if (e[0] - e[1] > e[1] - e[2]) { m1 = 2; mm = 0; } else { m1 = 0; mm = 2; }
+                tr->keep_first = mm == 0;
                 double p = 0.0;
                 for (int i = 0; i < 3; ++i) {
                     a[i][m1] = a[i][m1] - dt * a[i][mm];
                     p += a[i][m1] * a[i][m1];
                 }
+                tr->p = p; tr->fb_a = p <= TOLERANCE;
                 if (p <= TOLERANCE) {
                     int j = 0;
                     p = 1.0;
@@ -109,11 +145,12 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
                         if (p < fabs(a[i][mm])) { p = fabs(a[i][mm]); j = i; }
                     int k = IP2312[j], l = IP2312[j + 1];
                     p = sqrt(a[k][mm] * a[k][mm] + a[l][mm] * a[l][mm]);
+                    tr->fb_a_axis = j; tr->fb_a_len = p;
                     if (p > TOLERANCE) {
                         a[j][m1] = 0.0;
                         a[k][m1] = -a[l][mm] / p;
                         a[l][m1] = a[k][mm] / p;
-                    } else a_failed = 1;
+                    } else { a_failed = 1; tr->fb_a = 2; }
                 } else {
                     p = 1.0 / sqrt(p);
                     for (int i = 0; i < 3; ++i) a[i][m1] *= p;
@@ -128,6 +165,7 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
                             b[i][l] = r[i][0] * a[0][l] + r[i][1] * a[1][l] + r[i][2] * a[2][l];
                             db += b[i][l] * b[i][l];
                         }
+                        tr->d_b[l] = db; tr->db_zero[l] = !(db > EPSILON);
                         db = db > EPSILON ? 1.0 / sqrt(db) : 0.0;
                         for (int i = 0; i < 3; ++i) b[i][l] *= db;
                     }
@@ -138,6 +176,7 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
                         b[i][1] -= dot_b * b[i][0];
                         pb += b[i][1] * b[i][1];
                     }
+                    tr->p_b = pb; tr->fb_b = pb <= TOLERANCE;
                     if (pb <= TOLERANCE) {
                         pb = 1.0;
                         int j = 0;
@@ -145,16 +184,18 @@ float fdo_kabsch(const float *xf, const float *yf, uint64_t n, int mode, float r
                             if (pb < fabs(b[i][0])) { pb = fabs(b[i][0]); j = i; }
                         int k = IP2312[j], l = IP2312[j + 1];
                         pb = sqrt(b[k][0] * b[k][0] + b[l][0] * b[l][0]);
+                        tr->fb_b_axis = j; tr->fb_b_len = pb;
                         if (pb > TOLERANCE) {
                             b[j][1] = 0.0;
                             b[k][1] = -b[l][0] / pb;
                             b[l][1] = b[k][0] / pb;
-                        } else b_failed = 1;
+                        } else { b_failed = 1; tr->fb_b = 2; }
                     } else {
                         pb = 1.0 / sqrt(pb);
                         for (int i = 0; i < 3; ++i) b[i][1] *= pb;
                     }
                     if (!b_failed) {
+                        tr->built = 1;
                         b[0][2] = b[1][0] * b[2][1] - b[1][1] * b[2][0];
                         b[1][2] = b[2][0] * b[0][1] - b[2][1] * b[0][0];
                         b[2][2] = b[0][0] * b[1][1] - b[0][1] * b[1][0];
