@@ -9,7 +9,9 @@ lists here put those cases at the edge on purpose:
              takes two bytes
   multi      three steps with a wide delta on both edges
 
-Deltas of five bytes would need more than 2^28 structures per index and are left out; heads of five bytes are there (first_id = 2^28), also
+Deltas of five bytes would need more than 2^28 structures per index and are left out here, because remove and permute allocate per structure;
+tests/merge_cases.py reaches them (merge, load, slice and verify allocate nothing per structure) and merges the results of the operations
+here with a part that follows them, which shows the last ids they carry.  Heads of five bytes are there (first_id = 2^28), also
 where split writes the head of a piece.  The wide index holds every list over just above 2^21 structures (the four-byte delta needs them); the
 narrow one leaves the four-byte deltas out and is small enough for the bitmap of k_permute.hip to stay in LDS.  Expected results come from
 Python alone: decode, transform, delta, LEB128 (the codec of tests/rebase_cases.py)."""
